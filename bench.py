@@ -1,17 +1,22 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the Kalman/RTS/Power-EP hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5|cfg3_batch|cfg2_batch|cfg5_fill] [--segments B] [--T T] [--extras ...]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5|cfg3_batch|cfg2_batch|cfg5_fill] [--segments B] [--T T]
+                    [--dump-outputs DIR] [--full [--extras ...] [--no-cpu-baseline]]
 
 A "step" is one full pass of the hot path (all EP sweeps: forward filter, smoother, site refresh) over one batch of
 synthetic audio segments already resident in HBM.
 
 The top-level line is BASELINE.json configs[2], the configuration north_star states its target on:
 ihgp_ep_modulator_nmf, 200 000 samples, 32 channels / 6 NMF components -- ONE segment per GPU ("weak": the sequence is a
-single recursion and does not shard; with N GPUs every rank filters its own 200 k-sample segment).  The same JSON line
-carries, under `cfg5_strong`, the segment-sharded workload of configs[4] (gf_ep_modulator_nmf_constraints, 8 segments of
-100 000 samples IN TOTAL, 8/N per rank, RCCL all-reduce of the per-sweep log marginal likelihood inside the timed region)
-and, at N = 1, configs[1] under `cfg2`.
+single recursion and does not shard; with N GPUs every rank filters its own 200 k-sample segment).  A plain run measures that
+line and nothing else.  With `--full` the same JSON line also carries the timed CPU baseline (N = 1) and the extra workloads:
+under `cfg5_strong` the segment-sharded workload of configs[4] (gf_ep_modulator_nmf_constraints, 8 segments of 100 000
+samples IN TOTAL, 8/N per rank, RCCL all-reduce of the per-sweep log marginal likelihood inside the timed region) and, at
+N = 1, configs[1] under `cfg2`.
+
+`--dump-outputs DIR` writes what the last timed step of the top-level workload computed (the plan's outputs, a caller's view)
+as DIR/<name>.npy in float64; the inputs are seeded, so two builds run with the same arguments can be compared array by array.
 
 `--gpus N` with N > 1 and no RANK in the environment starts N fresh child processes (one per GPU) BEFORE anything in this
 process touches the GPU; under `python -m torch.distributed.run` (RANK set) the process is one rank.  Rank 0 prints ONE JSON line.
@@ -210,8 +215,42 @@ def source_hash():
     return L.source_hash()
 
 
-def run_workload(name, a, rank, local_rank, world, dev, with_cpu, steps, warmup):
-    """Times `steps` executes of one named workload; returns the JSON-able result dict."""
+DUMP_BUDGET_BYTES = 48 << 20     # the sampled output arrays of one --dump-outputs, all ranks together (nlZ comes on top: a few bytes)
+DUMP_ARRAYS = ('Eft', 'Varft', 'ttau', 'tnu', 'R', 'lZ')
+DUMP_MAY_BE_INF = ('R',)         # site noise: Inf for empty / clamped sites (1 / ttau with ttau = 0)
+
+
+def dump_outputs(plan, nlz_total, outdir, rank, world):
+    """What the last execute left on the device, downloaded as a caller of the plan receives it (Plan.download: per-problem
+    Eft / Varft / sites / lZ / nlZ; the S x T state means are left out, 230 MB alone at the headline size), stacked over this
+    rank's problems into (B, M, T) / (B, T) / (B, I) arrays and written as float64 .npy files.  An array larger than its share
+    of DUMP_BUDGET_BYTES is replaced by a fixed, seeded sample of its flattened entries (same shapes -> same positions).
+    Every file holds finite numbers: the non-finite entries of an array of DUMP_MAY_BE_INF are written as 0 and their kind
+    goes to <name>_nonfinite.npy (0 finite, 1 +Inf, -1 -Inf, 2 NaN), so two builds still compare entry by entry."""
+    os.makedirs(outdir, exist_ok=True)
+    outs = plan.download(want_MS=False)
+    cap = DUMP_BUDGET_BYTES // 8 // ((len(DUMP_ARRAYS) + len(DUMP_MAY_BE_INF)) * world)
+    arrs = {'nlZ': np.stack([o.nlZ for o in outs])}
+    if rank == 0:
+        arrs['nlZ_allreduced'] = np.asarray(nlz_total, dtype=np.float64)
+    for k in DUMP_ARRAYS:
+        v = np.stack([getattr(o, k) for o in outs])
+        if v.size > cap:
+            idx = np.sort(np.random.default_rng(20240601).choice(v.size, cap, replace=False))
+            v = v.reshape(-1)[idx]
+        if k in DUMP_MAY_BE_INF:
+            fin = np.isfinite(v)
+            arrs[k + '_nonfinite'] = np.where(fin, 0.0, np.where(np.isnan(v), 2.0, np.sign(v)))
+            v = np.where(fin, v, 0.0)
+        arrs[k] = v
+    prefix = '' if rank == 0 else 'rank%d_' % rank
+    for k, v in arrs.items():
+        np.save(os.path.join(outdir, prefix + k + '.npy'), np.ascontiguousarray(v, dtype=np.float64))
+
+
+def run_workload(name, a, rank, local_rank, world, dev, with_cpu, steps, warmup, dump_dir=None):
+    """Times `steps` executes of one named workload; returns the JSON-able result dict.  dump_dir: write the outputs of the last
+    timed step there (dump_outputs)."""
     import nagp
     from nagp import Mom, _lib as L, dist as nd
     import torch
@@ -270,6 +309,8 @@ def run_workload(name, a, rank, local_rank, world, dev, with_cpu, steps, warmup)
                   np.allclose(per_rank.sum(axis=0), nlz_total, rtol=1e-12, atol=0.0) if kind != L.KIND_GIEKF else np.all(np.isfinite(nlz_total)))
     if not nlz_ok:
         raise SystemExit('bench.py: %s: nlZ_allreduced %s is not finite / not the sum of the per-problem values %s' % (name, nlz_total, per_rank.sum(axis=0)))
+    if dump_dir is not None and plan is not None:
+        dump_outputs(plan, nlz_total, dump_dir, rank, world)
 
     D, N, T = wl['D'], wl['N'], wl['T']
     S = plan.S if plan else 0; M = plan.M if plan else 0
@@ -460,9 +501,13 @@ def main():
     ap.add_argument('--workload', default='cfg3', choices=sorted(WORKLOADS))
     ap.add_argument('--segments', type=int, default=0, help='diagnostics: this many segments on EVERY GPU instead of the named configuration')
     ap.add_argument('--T', type=int, default=0, help='override the segment length (diagnostics only)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--extras', default='default', help="comma list of additional workloads measured into the same line ('default': cfg5 [+ cfg2 at N=1]; 'none')")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='write the outputs of the last timed step of the top-level workload to DIR/<name>.npy')
+    ap.add_argument('--full', action='store_true', help='also the timed CPU baseline (N = 1) and the extra workloads, in the same line')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline out')
+    ap.add_argument('--extras', default='default', help="with --full: comma list of additional workloads measured into the same line ('default': cfg5 [+ cfg2 at N=1]; 'none')")
     a = ap.parse_args()
+    if not a.full and a.extras not in ('default', 'none'):
+        ap.error('--extras %s needs --full' % a.extras)
 
     if a.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(spawn_ranks(a))
@@ -484,19 +529,19 @@ def main():
         nagp.build()                                              # one rank compiles (if the library is stale), the others wait
     nd.barrier()
 
-    with_cpu = (not a.no_cpu_baseline) and world == 1             # the CPU baseline is timed at N = 1 only
-    line = run_workload(a.workload, a, rank, local_rank, world, dev, with_cpu, a.steps, a.warmup)
+    with_cpu = a.full and (not a.no_cpu_baseline) and world == 1  # the CPU baseline is timed at N = 1 only
+    line = run_workload(a.workload, a, rank, local_rank, world, dev, with_cpu, a.steps, a.warmup, dump_dir=a.dump_outputs)
     line['world_size'] = nd.world_size()                       # what the initialised process group reports
     line['collective_backend'] = nd.backend_id()                # 'nccl' (= RCCL on ROCm) | 'gloo' (rehearsal: several ranks on one card) | 'none'
     line['devices'] = nd.gather_device_ids(local_rank)          # one entry per rank: a SCALE record shows N distinct PCI bus ids
     line['launch'] = 'self-spawned ranks (file-store rendezvous)' if os.environ.get('NAGP_BENCH_SELF_SPAWNED') and world > 1 else ('torch.distributed.run' if world > 1 else 'single process')
-    extras = []
-    if a.extras == 'default':
+    extras = []                                                   # a plain run: the top-level line only
+    if a.full and a.extras == 'default':
         if a.workload == 'cfg3' and not a.T and not a.segments:
             # configs[4] sharded (strong) and in the fill-the-chip form (weak), the full-chip batch lines of both kernel families,
             # and at N = 1 the other single-GPU configurations
             extras = ['cfg5_fill', 'cfg3_batch', 'cfg2_batch', 'cfg5'] + (['cfg2', 'cfg4', 'cfg3_sqrt'] if world == 1 else [])     # (the weak series first: they are the ones that scale)
-    elif a.extras != 'none':
+    elif a.full and a.extras != 'none':
         extras = [e for e in a.extras.split(',') if e]
     for e in extras:
         # extras: one warm-up + two timed steps (the contract's K and W apply to the top-level line); CPU baseline for the BASELINE configurations

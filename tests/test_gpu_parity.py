@@ -1217,7 +1217,7 @@ def test_bench_two_ranks_rehearsal_on_one_card_prints_a_consistent_line():
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NAGP_BENCH_REHEARSAL='1'); env.pop('RANK', None); env.pop('WORLD_SIZE', None)
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--T', '400', '--steps', '1', '--warmup', '1', '--no-cpu-baseline', '--extras', 'cfg5'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--T', '400', '--steps', '1', '--warmup', '1', '--full', '--no-cpu-baseline', '--extras', 'cfg5'],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
@@ -1227,6 +1227,43 @@ def test_bench_two_ranks_rehearsal_on_one_card_prints_a_consistent_line():
     assert d['launch'].startswith('self-spawned') and d['scaling'] == 'weak' and d['cfg5_strong']['scaling'] == 'strong'
     assert '8 segment(s) in total = 8/2 per GPU' in d['cfg5_strong']['workload']
     assert np.all(np.isfinite(d['nlZ_allreduced'])) and np.all(np.isfinite(d['cfg5_strong']['nlZ_allreduced'])) and d['value'] > 0
+
+
+def test_bench_dump_outputs_are_what_the_timed_plan_computed(tmp_path):
+    """A plain `bench.py --dump-outputs DIR` run: the line carries the top-level workload only (no extras, no CPU baseline), and DIR
+    holds the float64 outputs of its last timed step -- nlZ_allreduced equal to the line's, Eft / Varft / sites / lZ / nlZ equal to
+    the same seeded problem run through a Plan in this process."""
+    import importlib.util, json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location('bench', os.path.join(root, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    out = tmp_path / 'dump'
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--T', '400', '--steps', '2', '--warmup', '1', '--dump-outputs', str(out)],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d['steps'] == 2 and d['warmup'] == 1 and d['ms_per_step'] > 0 and 'cpu_baseline' not in d
+    assert not any(k in d for k in list(bench.WORKLOADS) + ['cfg5_strong'])
+    got = {f[:-4]: np.load(str(out / f)) for f in os.listdir(str(out))}
+    assert set(got) == {'nlZ_allreduced', 'nlZ', 'Eft', 'Varft', 'ttau', 'tnu', 'R', 'R_nonfinite', 'lZ'}
+    assert all(v.dtype == np.float64 and np.all(np.isfinite(v)) for v in got.values())
+    assert np.array_equal(got['nlZ_allreduced'], np.asarray(d['nlZ_allreduced']))
+    wl = dict(bench.WORKLOADS['cfg3'], T=400)
+    probs, ys = bench.build_problems(wl, [1000])
+    plan = Plan(L.KIND_IHGP, probs, 400, mom=bench.make_mom(wl), ep_fraction=0.5, ep_damping=wl.get('damping', 0.5) * np.ones(bench.EP_ITTS),
+                ep_itts=bench.EP_ITTS, l_iter=1)
+    plan.upload(ys); plan.execute()
+    o = plan.download(want_MS=False)[0]
+    plan.close()
+    assert got['Eft'].shape == (1,) + o.Eft.shape and got['lZ'].shape == (1, 400) and got['nlZ'].shape == (1, bench.EP_ITTS)
+    for k in ('Eft', 'Varft', 'ttau', 'tnu', 'lZ', 'nlZ'):
+        assert rel(got[k][0], getattr(o, k)) < 1e-12, k
+    # R = site noise, Inf where a site is empty: written as 0 there, the kind of every non-finite entry in R_nonfinite
+    b = o.R; fin = np.isfinite(b)
+    assert np.array_equal(got['R_nonfinite'][0], np.where(fin, 0.0, np.where(np.isnan(b), 2.0, np.sign(b))))
+    assert np.all(got['R'][0][~fin] == 0.0) and rel(got['R'][0][fin], b[fin]) < 1e-12
 
 
 # ---------------------------------------------------------------------------------------------

@@ -318,6 +318,12 @@ def test_bench_refuses_a_world_size_mismatch_and_spawns_ranks_itself():
     assert r.returncode != 0 and '--gpus 2 but WORLD_SIZE=1' in (r.stderr + r.stdout)
 
 
+def test_bench_measures_extras_only_with_full():
+    """A plain bench.py run times the top-level line only: extra workloads asked for without --full are refused before any GPU work."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--extras', 'cfg5'], capture_output=True, text=True, timeout=120)
+    assert r.returncode != 0 and '--extras cfg5 needs --full' in r.stderr
+
+
 def test_c_callers_and_the_mex_gateway_compile_and_link():
     """tests/c/abi_golden.c (plain C caller of the ABI) and matlab/nagp_mex.c (against the mock MEX API of tests/c) build with
     gcc and link against libnagp.so; they run in the -m gpu tests."""

@@ -3,7 +3,7 @@ export NAGP_DEVELOPER=1      # developer tool: libnagp.so reads its switches onl
 # tools/final_measurements.sh <tag> <part> -- everything DESIGN.md section 5 cites (run from the repository root on the GPU box; two GPU calls:
 # a call is limited to twenty minutes):
 #   part 1: PMC traffic + kernel statistics (tools/pmc_run.sh) of the single-GPU configurations, instruction counters of the headline kernel
-#   part 2: PMC traffic of the fill-the-chip workloads, matrix-core counters, kernel traces -> pipeline timelines, gain kernel phase stamps, the default bench line
+#   part 2: PMC traffic of the fill-the-chip workloads, matrix-core counters, kernel traces -> pipeline timelines, gain kernel phase stamps, the full bench line (--full)
 # Outputs under gpurun_out/ (tools/collect_final.sh copies the summaries into profiles/).
 set -o pipefail
 tag=${1:-r05}; part=${2:-1}
@@ -30,5 +30,6 @@ else
   find gpurun_out/${tag}_trace_cfg5x8 -name "*kernel_stats.csv" -exec cp {} gpurun_out/${tag}_kernel_stats_cfg5x8.csv \; ; find gpurun_out/${tag}_trace_* -name "*kernel_trace.csv" -size +20M -delete
   for wl in cfg5_fill cfg2_batch; do cp profiles/${tag}_pmc_traffic_$wl.txt profiles/${tag}_kernel_stats_$wl.csv profiles/${tag}_pmc_mfma_$wl.txt gpurun_out/ 2>/dev/null; done; cp profiles/pmc_traffic.json gpurun_out/pmc_traffic.json
   { for a in "19 4096 0 1" "19 4096 0 0" "38 4096 1 1" "38 4096 1 0"; do tools/ubench/gain_check $a; done; tools/ubench/chol16; } > gpurun_out/${tag}_gain_check.txt 2>&1
-  ( time python bench.py > gpurun_out/${tag}_bench_default.json 2> gpurun_out/${tag}_bench_default.err ) 2> gpurun_out/${tag}_bench_default.time && tail -3 gpurun_out/${tag}_bench_default.time ; echo FINAL_PART2_DONE
+  res=${d%/*}      # the output folder of the traces above
+  ( time python bench.py --full > $res/${tag}_bench_default.json 2> $res/${tag}_bench_default.err ) 2> $res/${tag}_bench_default.time && tail -3 $res/${tag}_bench_default.time ; echo FINAL_PART2_DONE
 fi
