@@ -3,6 +3,159 @@
 // Plan creation: shape checks, kernel / LDS / slot policy, model packing, cubature tables, device buffers; destroy, upload.
 
 // ---------------------------------------------------------------------------------------------
+// Member and term lists of the role layout's cubature sums (nagp_momsp.hpp, msr_sums / msr_reduce), built once per plan from the
+// static cubature codes.  Bins: S_k (k = 0, 1, 2), Ck(j,c), C2(j,c; j',c'), each cut into chunks of <= 64 members on an aligned
+// group of 1, 2 or 4 lanes.  Level-2 outputs: U_j, E_j, P_jj, g1_j, G2_j, P_jj', S_k, each <= 4 MSR_KT terms bin * table * table.
+// The bins of a dimension (and its outputs), of a dimension pair and of a total go to ONE worker wave (their level 2 reads its own
+// bins), first fit by decreasing size.  Returns false when the rule does not fit the six worker waves.
+static bool msr_build_desc(int CD, int nd, int c0, int npt, const std::vector<unsigned char>& code, std::vector<int>& dsc) {
+  const MspLay l = msp_layout(CD, 1, 1);      // (the offsets used here do not depend on D)
+  const int zero = l.zero, one = l.one, mone = l.part + MSR_MONE;
+  struct Bin { int k; std::vector<int> pts; std::vector<int> slot; };      // slot: level-1 result of each chunk
+  struct Term { int bin, fa, fb; };
+  struct Out { std::vector<Term> t; int slot = -1; };
+  struct Grp { std::vector<int> bins, outs; int n1 = 0, n2 = 0; };
+  std::vector<Bin> bins; std::vector<Out> outs; std::vector<Grp> grps;
+  auto pw2 = [](int n) { return n <= 1 ? 1 : (n <= 2 ? 2 : 4); };
+  auto chunks = [](const Bin& b) { return std::max(1, ((int)b.pts.size() + 63) / 64); };
+  auto chunk_lanes = [&](const Bin& b, int q) { const int n = std::min(64, (int)b.pts.size() - 64 * q); return pw2((n + MSR_NMEM - 1) / MSR_NMEM); };
+  auto nterms = [&](const Out& o) { int n = 0; for (const Term& t : o.t) n += chunks(bins[t.bin]); return n; };
+  auto add_bin = [&](int k, std::vector<int> pts) { bins.push_back({k, std::move(pts), {}}); return (int)bins.size() - 1; };
+  auto add_out = [&](Grp& g) { outs.push_back(Out{}); g.outs.push_back((int)outs.size() - 1); return (int)outs.size() - 1; };
+  auto cd = [&](int p, int j) { return (int)code[(size_t)p * CD + j]; };
+  const int lk = l.lk, e = l.e;
+  std::vector<int> oU(CD, -1), oE(CD, -1), oPd(CD, -1), oG1(CD, -1), oG2(CD, -1), oS(3, -1);
+  std::vector<std::vector<int>> oP(CD, std::vector<int>(CD, -1));
+  for (int j = 0; j < CD; ++j) {      // dimension j: C0, C1, C2 (j, c) and the outputs U, E, P_jj, g1, G2
+    Grp g;
+    oU[j] = add_out(g); oE[j] = add_out(g); oPd[j] = add_out(g); oG1[j] = add_out(g); oG2[j] = add_out(g);
+    for (int c = 0; c < nd; ++c) {
+      if (c == c0) continue;
+      std::vector<int> pts;
+      for (int p = 0; p < npt; ++p) if (cd(p, j) == c) pts.push_back(p);
+      if (pts.empty()) continue;
+      const int t = j * nd + c;
+      const int b0 = add_bin(0, pts), b1 = add_bin(1, pts), b2 = add_bin(2, pts);
+      g.bins.insert(g.bins.end(), {b0, b1, b2});
+      outs[oU[j]].t.push_back({b1, e + t, one});
+      outs[oE[j]].t.push_back({b2, e + t, one});
+      outs[oPd[j]].t.push_back({b2, e + t, e + t});
+      outs[oG1[j]].t.push_back({b0, l.xg + t, one});
+      outs[oG2[j]].t.push_back({b0, l.xg2 + t, one});
+      outs[oG2[j]].t.push_back({b0, l.xg2 + j * nd + c0, mone});
+    }
+    grps.push_back(g);
+  }
+  for (int j = 0; j < CD; ++j)        // dimension pair j < j2: C2 (j, c; j2, c2) and P_jj2
+    for (int j2 = j + 1; j2 < CD; ++j2) {
+      Grp g;
+      oP[j][j2] = add_out(g);
+      for (int c = 0; c < nd; ++c)
+        for (int cc = 0; cc < nd; ++cc) {
+          if (c == c0 || cc == c0) continue;
+          std::vector<int> pts;
+          for (int p = 0; p < npt; ++p) if (cd(p, j) == c && cd(p, j2) == cc) pts.push_back(p);
+          if (pts.empty()) continue;
+          const int b = add_bin(2, pts);
+          g.bins.push_back(b);
+          outs[oP[j][j2]].t.push_back({b, e + j * nd + c, e + j2 * nd + cc});
+        }
+      grps.push_back(g);
+    }
+  for (int k = 0; k < 3; ++k) {       // totals
+    Grp g;
+    std::vector<int> pts(npt);
+    for (int p = 0; p < npt; ++p) pts[p] = p;
+    const int b = add_bin(k, pts);
+    g.bins.push_back(b);
+    oS[k] = add_out(g);
+    outs[oS[k]].t.push_back({b, one, one});
+    grps.push_back(g);
+  }
+  for (Grp& g : grps) {
+    for (int b : g.bins) for (int q = 0; q < chunks(bins[b]); ++q) g.n1 += chunk_lanes(bins[b], q);
+    for (int o : g.outs) {
+      const int n = nterms(outs[o]);
+      if (n > 4 * MSR_KT) return false;
+      g.n2 += pw2((n + MSR_KT - 1) / MSR_KT);
+    }
+  }
+  // first fit by decreasing level-1 lanes
+  std::vector<int> order(grps.size());
+  for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return grps[a].n1 > grps[b].n1; });
+  std::vector<std::vector<int>> wg(MSR_NWK);
+  int used1[MSR_NWK] = {0}, used2[MSR_NWK] = {0};
+  for (int gi : order) {
+    int w = 0;
+    while (w < MSR_NWK && (used1[w] + grps[gi].n1 > 64 || used2[w] + grps[gi].n2 > 64)) ++w;
+    if (w == MSR_NWK) return false;
+    wg[w].push_back(gi); used1[w] += grps[gi].n1; used2[w] += grps[gi].n2;
+  }
+  dsc.assign((size_t)msr_desc_ints(), zero);
+  for (int L = 0; L < MSR_NL; ++L) { dsc[(size_t)L * MSR_DW + MSR_NMEM] = 0; dsc[(size_t)L * MSR_DW + MSR_NMEM + 1 + 3 * MSR_KT] = 0; }
+  const int grp_flags[5] = {0, 0, 1, 0, 3};      // by group size
+  for (int w = 0; w < MSR_NWK; ++w) {
+    // level 1: chunks by decreasing group size (aligned groups)
+    struct Ch { int b, q, G; };
+    std::vector<Ch> ch;
+    for (int gi : wg[w]) for (int b : grps[gi].bins) for (int q = 0; q < chunks(bins[b]); ++q) ch.push_back({b, q, chunk_lanes(bins[b], q)});
+    std::stable_sort(ch.begin(), ch.end(), [](const Ch& a, const Ch& b) { return a.G > b.G; });
+    int lane = 0;
+    for (const Ch& c : ch) {
+      Bin& b = bins[c.b];
+      const int base = b.k == 0 ? l.c0 : (b.k == 1 ? l.c1 : l.c2);
+      const int n = std::min(64, (int)b.pts.size() - 64 * c.q);
+      for (int i = 0; i < n; ++i) {      // member i -> lane i % G, slot i / G
+        const int L = w * 64 + lane + i % c.G;
+        dsc[(size_t)L * MSR_DW + i / c.G] = base + b.pts[64 * c.q + i];
+      }
+      for (int i = 0; i < c.G; ++i) dsc[(size_t)(w * 64 + lane + i) * MSR_DW + MSR_NMEM] = grp_flags[c.G];
+      if ((int)b.slot.size() <= c.q) b.slot.resize(c.q + 1, -1);
+      b.slot[c.q] = l.part + w * 64 + lane;
+      lane += c.G;
+    }
+    // level 2: outputs by decreasing group size
+    struct Oc { int o, G; };
+    std::vector<Oc> oc;
+    for (int gi : wg[w]) for (int o : grps[gi].outs) oc.push_back({o, pw2((nterms(outs[o]) + MSR_KT - 1) / MSR_KT)});
+    std::stable_sort(oc.begin(), oc.end(), [](const Oc& a, const Oc& b) { return a.G > b.G; });
+    lane = 0;
+    for (const Oc& c : oc) {
+      std::vector<Term> ts;      // chunks expanded
+      for (const Term& t : outs[c.o].t)
+        for (int q = 0; q < chunks(bins[t.bin]); ++q) ts.push_back({bins[t.bin].slot[q], t.fa, t.fb});
+      for (size_t i = 0; i < ts.size(); ++i) {
+        int* d = &dsc[(size_t)(w * 64 + lane + (int)i / MSR_KT) * MSR_DW + MSR_NMEM + 1 + 3 * ((int)i % MSR_KT)];
+        d[0] = ts[i].bin; d[1] = ts[i].fa; d[2] = ts[i].fb;
+      }
+      for (int i = 0; i < c.G; ++i) dsc[(size_t)(w * 64 + lane + i) * MSR_DW + MSR_NMEM + 1 + 3 * MSR_KT] = grp_flags[c.G];
+      outs[c.o].slot = l.part + MSR_NL + w * 64 + lane;
+      lane += c.G;
+    }
+  }
+  // msr_reduce: acc[o] = p + c d + a b + s f g
+  auto L2 = [&](int o) { return (o >= 0 && !outs[o].t.empty()) ? outs[o].slot : zero; };
+  auto l0 = [&](int j) { return lk + j * nd + c0; };
+  const int nq = CD * (CD + 1) / 2;
+  for (int o = 0; o < msp_nacc(CD); ++o) {
+    int* r = &dsc[(size_t)MSR_NL * MSR_DW + (size_t)o * MSR_RW];      // p, a, b, c, d, s, f, g (zero word by default)
+    if (o < CD) { r[0] = L2(oU[o]); r[5] = L2(oS[1]); r[6] = l0(o); r[7] = one; }
+    else if (o < CD + nq) {
+      int q = o - CD, j = 0;
+      while (q >= CD - j) { q -= CD - j; ++j; }
+      const int j2 = j + q;
+      r[0] = (j == j2) ? L2(oPd[j]) : L2(oP[j][j2]);
+      r[1] = l0(j2); r[2] = L2(oE[j]); r[3] = l0(j); r[4] = L2(oE[j2]);
+      r[5] = L2(oS[2]); r[6] = l0(j); r[7] = l0(j2);
+    } else if (o < 2 * CD + nq) r[0] = L2(oG1[o - CD - nq]);
+    else if (o < 3 * CD + nq) { const int j = o - 2 * CD - nq; r[0] = L2(oG2[j]); r[5] = L2(oS[0]); r[6] = l.xg2 + j * nd + c0; r[7] = one; }
+    else r[0] = L2(oS[0]);
+  }
+  return true;
+}
+
+// ---------------------------------------------------------------------------------------------
 extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* models, const nagp_ihgp_tables* tables,
                                 int64_t T, const nagp_opts* o) {
   if (!out || !models || !o || B < 1 || T < 1) FAIL(NAGP_EINVAL, "null/empty argument");
@@ -250,13 +403,15 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
         PLAN_HIP(hipMemcpyAsync(dd, pdesc.data(), pdesc.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
         PLAN_HIP(hipStreamSynchronize(p->stream));
         p->sp.enabled = 1; p->sp.c0 = c0; p->sp.nzmax = nzmax; p->sp.pdesc = reinterpret_cast<const int*>(dd);
-        for (int j = 0; j < o->cub_dim; ++j)
-          for (int cc = 0; cc < (int)xd.size(); ++cc) {
-            if (cc == c0) continue;
-            int cnt = 0;
-            for (int q = 0; q < o->n_pts; ++q) cnt += (code[(size_t)q * o->cub_dim + j] == cc) ? 1 : 0;
-            p->sp_maxmem = std::max(p->sp_maxmem, cnt);
-          }
+        // the member / term lists of the role layout's cubature sums (<= one sigma point per worker lane)
+        std::vector<int> bd;
+        if (o->n_pts <= 64 * MSR_NWK && msr_build_desc(o->cub_dim, (int)xd.size(), c0, o->n_pts, code, bd)) {
+          double* db = nullptr;
+          PLAN_TRY(dalloc(p, &db, (bd.size() + 1) / 2 + 1, false));
+          PLAN_HIP(hipMemcpyAsync(db, bd.data(), bd.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
+          PLAN_HIP(hipStreamSynchronize(p->stream));
+          p->sp.bdesc = reinterpret_cast<const int*>(db);
+        }
       }
     }
     if (o->lik_kind == NAGP_LIK_POWER_NMF_SQRT && o->cub_dim <= MSQ_MAXCD && sh.D <= MSQ_MAXD && !dev_env("NAGP_NO_SPARSE")) {
@@ -585,22 +740,13 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
           case 5: PLAN_TRY(set_lds(ihgp_adf_kernel<5>, p->lds_sp)); break; case 6: PLAN_TRY(set_lds(ihgp_adf_kernel<6>, p->lds_sp)); break;
           default: PLAN_TRY(set_lds(ihgp_adf_kernel<7>, p->lds_sp)); break;
         }
-        // role-specialised waves: two serial + six worker waves, one sigma point per worker lane, <= 80 MFMA steps
+        // role-specialised waves: two serial + six worker waves, one sigma point per worker lane, the cubature sums from bin sums (msr_build_desc)
         const size_t need8 = ihgp_adf8_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16;
         const char* er = dev_env("NAGP_IH_ROLES");
-        if (o->n_pts <= 64 * MSR_NWK && (o->n_pts + 3) / 4 <= 4 * MSR_NST && need8 <= 156 * 1024 && !(er && er[0] == '0')) {
+        if (p->sp.bdesc && need8 <= 156 * 1024 && !(er && er[0] == '0')) {
           p->sp_ih8 = 1; p->lds_sp8 = need8;
-          // packed form (eight points per MFMA step, g1 / g2 from marginal sums): <= 6 components, <= 16 marginals per marginal wave, each of <= 64 members
-          {
-            const int CDp = o->cub_dim, ndp = mc.nd;
-            bool pk = CDp <= 6 && (ndp - 1) * ((CDp + 1) / 2) <= 16 && (ndp - 1) * CDp <= MSR_NMARG && (o->n_pts + 7) / 8 <= 40 && p->sp_maxmem <= 4 * MSR_NMEM;   // 3 of 8 slots <= MSR_NSTP steps
-            const char* ep = dev_env("NAGP_IH_PACK");
-            if (ep && ep[0] == '0') pk = false;
-            p->sp_pack = pk ? 1 : 0;
-          }
-#define SL8(V, PK) PLAN_TRY(set_lds(ihgp_adf8_kernel<V, PK>, need8))
-          if (p->sp_pack) switch (o->cub_dim) { case 1: SL8(1, true); break; case 2: SL8(2, true); break; case 3: SL8(3, true); break; case 4: SL8(4, true); break; case 5: SL8(5, true); break; default: SL8(6, true); break; }
-          else switch (o->cub_dim) { case 1: SL8(1, false); break; case 2: SL8(2, false); break; case 3: SL8(3, false); break; case 4: SL8(4, false); break; case 5: SL8(5, false); break; case 6: SL8(6, false); break; default: SL8(7, false); break; }
+#define SL8(V) PLAN_TRY(set_lds(ihgp_adf8_kernel<V>, need8))
+          switch (o->cub_dim) { case 1: SL8(1); break; case 2: SL8(2); break; case 3: SL8(3); break; case 4: SL8(4); break; case 5: SL8(5); break; case 6: SL8(6); break; default: SL8(7); break; }
 #undef SL8
         }
       }
@@ -622,7 +768,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
       }
     }
     if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);
-    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B), packed MFMA steps %d\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8, p->sp_pack);
+    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B)\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8);
 #define SL(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, false>, p->lds_ih))
 #define SLS(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, true>, p->lds_ih))
 #define SL8(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, false, 8>, p->lds_ih))
@@ -660,8 +806,8 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     if (p->pipeline && B <= 128 && p->lds_filter < 160 * 1024) p->lds_filter = 160 * 1024;     // (never BELOW what the kernel needs: set_lds refuses > 160 KiB)
     if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] gf filter: LDS %zu B, ring %d steps, cubature tables in LDS %d, mom LDS %zu B, sparse-point ADF %d\n", p->lds_filter, p->kb_f, p->cache_f, ekf ? (size_t)0 : mom_lds_doubles(t) * sizeof(double), p->sp_gf);
     // ADF sweep with role-specialised waves (nagp_gfadf8.hpp): 512 threads, <= 2 lower tiles per thread, the role layout's limits
-    // (one sigma point per worker lane, <= 80 MFMA steps; packed form as in the IHGP sweep)
-    if (p->sp_gf && sh.M * (sh.M + 1) / 2 <= 2 * MSR_NT && sh.S <= MSR_NT && o->n_pts <= 64 * MSR_NWK && (o->n_pts + 3) / 4 <= 4 * MSR_NST &&
+    // (one sigma point per worker lane; the cubature sums from bin sums as in the IHGP sweep)
+    if (p->sp_gf && sh.M * (sh.M + 1) / 2 <= 2 * MSR_NT && sh.S <= MSR_NT && p->sp.bdesc &&
         !dev_env("NAGP_NO_GF_ROLES")) {
       // tiles per thread / who owns them: 1 or 2 on the six worker waves (<= 384 / 768 lower tiles), else 2 on all eight waves
       const int nlow8 = sh.M * (sh.M + 1) / 2, ntw = MSR_NT - 64 * MSR_W0;
@@ -672,23 +818,17 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
       if (const char* e = dev_env("NAGP_KB_A8")) p->kb_a8 = std::max(2, std::min(16, atoi(e) & ~1));
       const size_t need = gf_adf8_lds_doubles(sh, o->cub_dim, p->kb_a8) * sizeof(double);
       if (need <= cap) {
-        const int CDp = o->cub_dim, ndp = mc.nd;
-        bool pk = CDp <= 6 && (ndp - 1) * ((CDp + 1) / 2) <= 16 && (ndp - 1) * CDp <= MSR_NMARG && (o->n_pts + 7) / 8 <= 40 && p->sp_maxmem <= 4 * MSR_NMEM;
-        const char* ep = dev_env("NAGP_IH_PACK");
-        if (ep && ep[0] == '0') pk = false;
-        p->a8_gf = 1; p->a8_pack = pk ? 1 : 0; p->lds_a8 = need;
+        p->a8_gf = 1; p->lds_a8 = need;
         if (p->pipeline && B <= 128) p->lds_a8 = 160 * 1024;      // (the whole LDS of the CU, as for the other filter launches below)
-#define SA8(TP, V, PK) do { if (p->a8_st) PLAN_TRY(set_lds((gf_adf8_kernel<2, V, PK, true>), p->lds_a8)); else PLAN_TRY(set_lds((gf_adf8_kernel<TP, V, PK, false>), p->lds_a8)); } while (0)
-#define SA8V(TP, PK) switch (o->cub_dim) { case 1: SA8(TP, 1, PK); break; case 2: SA8(TP, 2, PK); break; case 3: SA8(TP, 3, PK); break; \
-          case 4: SA8(TP, 4, PK); break; case 5: SA8(TP, 5, PK); break; default: SA8(TP, 6, PK); break; }
-        if (!pk && o->cub_dim == 7) { if (p->a8_tpt == 1) SA8(1, 7, false); else SA8(2, 7, false); }
-        else if (pk) { if (p->a8_tpt == 1) SA8V(1, true) else SA8V(2, true) }
-        else { if (p->a8_tpt == 1) SA8V(1, false) else SA8V(2, false) }
+#define SA8(TP, V) do { if (p->a8_st) PLAN_TRY(set_lds((gf_adf8_kernel<2, V, true>), p->lds_a8)); else PLAN_TRY(set_lds((gf_adf8_kernel<TP, V, false>), p->lds_a8)); } while (0)
+#define SA8V(TP) switch (o->cub_dim) { case 1: SA8(TP, 1); break; case 2: SA8(TP, 2); break; case 3: SA8(TP, 3); break; \
+          case 4: SA8(TP, 4); break; case 5: SA8(TP, 5); break; case 6: SA8(TP, 6); break; default: SA8(TP, 7); break; }
+        if (p->a8_tpt == 1) SA8V(1) else SA8V(2)
 #undef SA8V
 #undef SA8
       }
     }
-    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] gf ADF sweep with role-specialised waves: %d (tiles per thread %d, ring %d steps, LDS %zu B, packed MFMA steps %d)\n", p->a8_gf, p->a8_tpt, p->kb_a8, p->lds_a8, p->a8_pack);
+    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] gf ADF sweep with role-specialised waves: %d (tiles per thread %d, ring %d steps, LDS %zu B)\n", p->a8_gf, p->a8_tpt, p->kb_a8, p->lds_a8);
     p->lds_gain = (((p->TPT == 1) ? gain_lds_doubles_staged(sh) : gain_lds_doubles(sh)) + gain_cpl_doubles(sh)) * sizeof(double);     // (rts_gain_kernel: STAGE)
     p->lds_scan = span_lds_doubles(sh, p->LP1, p->LP2) * sizeof(double);
     if (split) {

@@ -44,13 +44,11 @@ static int launch_filter(nagp_plan* p, const FilterPar& fp_in) {
       // sweep 1 (mom at every step): role-specialised waves
       FilterPar fa = fp; fa.kb = p->kb_a8;
       MomCfg ma = mc; ma.sp = p->sp;
-#define LA8(TP, V, PK) do { if (p->a8_st) hipLaunchKernelGGL((gf_adf8_kernel<2, V, PK, true>), g, dim3(MSR_NT), p->lds_a8, p->stream, p->sh, p->b, ma, fa); \
-        else hipLaunchKernelGGL((gf_adf8_kernel<TP, V, PK, false>), g, dim3(MSR_NT), p->lds_a8, p->stream, p->sh, p->b, ma, fa); } while (0)
-#define LA8V(TP, PK) switch (mc.cdim) { case 1: LA8(TP, 1, PK); break; case 2: LA8(TP, 2, PK); break; case 3: LA8(TP, 3, PK); break; \
-        case 4: LA8(TP, 4, PK); break; case 5: LA8(TP, 5, PK); break; default: LA8(TP, 6, PK); break; }
-      if (!p->a8_pack && mc.cdim == 7) { if (p->a8_tpt == 1) LA8(1, 7, false); else LA8(2, 7, false); }
-      else if (p->a8_pack) { if (p->a8_tpt == 1) LA8V(1, true) else LA8V(2, true) }
-      else { if (p->a8_tpt == 1) LA8V(1, false) else LA8V(2, false) }
+#define LA8(TP, V) do { if (p->a8_st) hipLaunchKernelGGL((gf_adf8_kernel<2, V, true>), g, dim3(MSR_NT), p->lds_a8, p->stream, p->sh, p->b, ma, fa); \
+        else hipLaunchKernelGGL((gf_adf8_kernel<TP, V, false>), g, dim3(MSR_NT), p->lds_a8, p->stream, p->sh, p->b, ma, fa); } while (0)
+#define LA8V(TP) switch (mc.cdim) { case 1: LA8(TP, 1); break; case 2: LA8(TP, 2); break; case 3: LA8(TP, 3); break; \
+        case 4: LA8(TP, 4); break; case 5: LA8(TP, 5); break; case 6: LA8(TP, 6); break; default: LA8(TP, 7); break; }
+      if (p->a8_tpt == 1) LA8V(1) else LA8V(2)
 #undef LA8V
 #undef LA8
     } else
@@ -826,9 +824,8 @@ static int exec_ihgp(nagp_plan* p) {
       } else if (p->sp_ih) {
         IhgpPar ia = ip; ia.hph_lds = p->hph_sp; ia.kb = p->kb_sp;
 #define LA(V) hipLaunchKernelGGL((ihgp_adf_kernel<V>), dim3(B), dim3(MSP_NT), p->lds_sp, p->stream, sh, p->b, mcf, p->sp, p->tb, ia)
-#define LA8(V, PK) hipLaunchKernelGGL((ihgp_adf8_kernel<V, PK>), dim3(B), dim3(MSR_NT), p->lds_sp8, p->stream, sh, p->b, mcf, p->sp, p->tb, ia)
-        if (p->sp_ih8 && p->sp_pack) switch (mcf.cdim) { case 1: LA8(1, true); break; case 2: LA8(2, true); break; case 3: LA8(3, true); break; case 4: LA8(4, true); break; case 5: LA8(5, true); break; default: LA8(6, true); break; }
-        else if (p->sp_ih8) switch (mcf.cdim) { case 1: LA8(1, false); break; case 2: LA8(2, false); break; case 3: LA8(3, false); break; case 4: LA8(4, false); break; case 5: LA8(5, false); break; case 6: LA8(6, false); break; default: LA8(7, false); break; }
+#define LA8(V) hipLaunchKernelGGL((ihgp_adf8_kernel<V>), dim3(B), dim3(MSR_NT), p->lds_sp8, p->stream, sh, p->b, mcf, p->sp, p->tb, ia)
+        if (p->sp_ih8) switch (mcf.cdim) { case 1: LA8(1); break; case 2: LA8(2); break; case 3: LA8(3); break; case 4: LA8(4); break; case 5: LA8(5); break; case 6: LA8(6); break; default: LA8(7); break; }
         else switch (mcf.cdim) { case 1: LA(1); break; case 2: LA(2); break; case 3: LA(3); break; case 4: LA(4); break; case 5: LA(5); break; case 6: LA(6); break; default: LA(7); break; }
 #undef LA
 #undef LA8

@@ -192,6 +192,7 @@ struct MomSp {
   int c0;             // code of the coordinate value 0
   int nzmax;          // largest number of non-centre coordinates of a sigma point
   const int* pdesc;   // [n_pts][MSP_NZ]: j*nd + c of the non-centre coordinates, -1 = none
+  const int* bdesc;   // member / term lists of the role layout's cubature sums (msr_build_desc); null: the rule does not fit them
 };
 
 struct MomCfg {

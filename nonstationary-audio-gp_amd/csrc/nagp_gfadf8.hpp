@@ -22,7 +22,7 @@ __host__ __device__ inline size_t gf_adf8_lds_doubles(const Shape& s, int CD, in
 
 // ST = false: the two serial waves own NO tiles (the tiles of <= 384 * TPT lower tiles sit on the six worker waves): the serial role --
 // the tail of every step's dependence chain -- then holds its sites and nothing else
-template <int TPT, int CD, bool PACK, bool ST>
+template <int TPT, int CD, bool ST>
 __global__ void __launch_bounds__(MSR_NT) gf_adf8_kernel(Shape sh, Bufs b, MomCfg mc, FilterPar fp) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
@@ -282,8 +282,8 @@ __global__ void __launch_bounds__(MSR_NT) gf_adf8_kernel(Shape sh, Bufs b, MomCf
   if (wave >= MSR_W0) {
     // ================= worker role: covariance tiles + the parallel stages of the cubature
     const MspLay lay = msp_layout(CD, D, 1);
-    MsrW<CD, PACK> xw;
-    msr_setup_W<CD, PACK>(xw, mc, mc.sp, sW, fmu, HPH, ws);
+    MsrW<CD> xw;
+    msr_setup_W<CD>(xw, mc, mc.sp, sW, fmu, HPH, ws);
     __syncthreads();                     // (pairs with the serial role's barrier behind its set-up)
     for (int64_t k0 = fp.k_begin; k0 < fp.k_end; k0 += KB) {
       const int nb = (fp.k_end - k0 < KB) ? (int)(fp.k_end - k0) : KB;
@@ -303,8 +303,7 @@ __global__ void __launch_bounds__(MSR_NT) gf_adf8_kernel(Shape sh, Bufs b, MomCf
           lds_barrier();                 // B3
           msp_stage1b<CD>(xw, mc, mc.sp, sn2a, yk, ws);
           lds_barrier();                 // B4
-          if constexpr (PACK) { if (wave >= MSR_W0 + MSR_NWK - 2) msr_marginals<CD>(xw); }
-          msp_stage2<CD>(xw, mc, ws);
+          msr_sums(xw);
           lds_barrier();                 // B5
           // (moments, site update, gain coefficients: serial waves)
           if (fp.legacy_update) lds_barrier();
@@ -320,8 +319,8 @@ __global__ void __launch_bounds__(MSR_NT) gf_adf8_kernel(Shape sh, Bufs b, MomCf
   }
 
   // ================= serial role (waves 0 and 1): the sites (+ covariance tiles when ST)
-  MsrS<CD, PACK> x;
-  msr_setup_S<CD, PACK>(x, mc, mc.sp, fmu, HPH, ws);
+  MsrS<CD> x;
+  msr_setup_S<CD>(x, mc, mc.sp, fmu, HPH, ws);
   const int lane = tid & 63;
   const bool sub = (wave == 0) && lane < D;
   const bool act = sub || ((wave == 1) && lane < sh.N);
@@ -350,7 +349,7 @@ __global__ void __launch_bounds__(MSR_NT) gf_adf8_kernel(Shape sh, Bufs b, MomCf
         lds_barrier();                   // B3
         lds_barrier();                   // B4
         lds_barrier();                   // B5
-        msp_reduce<CD>(x);
+        msr_reduce<CD>(x);
         msp_wave_fence();
         if (act) {
           double Z, d1, d2;

@@ -546,7 +546,7 @@ __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomC
 // The same sweep with role-specialised waves (nagp_momsp.hpp, role layout): 512 threads, waves 0 / 1 as above, waves 2..7 run the
 // parallel stages of the cubature in their own loop.  A wave holds the registers of its role only, which is what lets two
 // waves share a SIMD (the sigma points take one round, the MFMA steps of two waves alternate on the matrix core).
-template <int CD, bool PACK>
+template <int CD>
 __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
@@ -603,11 +603,10 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   if (wave >= MSR_W0) {
     // ================= worker role: the parallel stages of the cubature; the same barriers as the serial role below
     const MspLay lay = msp_layout(CD, D, 1);
-    MsrW<CD, PACK> xw;
-    msr_setup_W<CD, PACK>(xw, mc, sp, sW, fmu, HPH, ws);
-    if (ip.dbg_wave & 8) xw.m_on = (wave - MSR_W0 < MSR_NWK) ? 1 : 0;   // developer A/B (NAGP_STAMP_WORKER=8): every worker runs the accumulation stage
-    // developer diagnostics (NAGP_STAMPS): time lines of worker 0 (an MFMA worker) in stamps[8..15] and of the last worker (marginal
-    // sums in the packed form) in stamps[16..23]
+    MsrW<CD> xw;
+    msr_setup_W<CD>(xw, mc, sp, sW, fmu, HPH, ws);
+    // developer diagnostics (NAGP_STAMPS): time lines of worker (NAGP_STAMP_WORKER & 7) in stamps[8..15] and of the last worker in
+    // stamps[16..23]
     const int wk_slot = (wave == MSR_W0 + (ip.dbg_wave & 7)) ? 8 : ((wave == MSR_W0 + MSR_NWK - 1) ? 16 : -1);
     const bool wk_stamp = mc.stamps && wk_slot >= 0 && (tid & 63) == 0;
     unsigned long long wk_a = 0, wk_b = 0, wk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -639,10 +638,8 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       WK_STAMP(3);
       lds_barrier();                 // B4
       WK_STAMP(4);
-      if constexpr (PACK) { if (wave >= MSR_W0 + MSR_NWK - 2) msr_marginals<CD>(xw); }
+      msr_sums(xw);                  // bin sums, then this wave's share of the 40 sums
       WK_STAMP(5);
-      msp_stage2<CD>(xw, mc, ws);
-      WK_STAMP(6);
       lds_barrier();                 // B5
       WK_STAMP(7);
     }
@@ -662,8 +659,8 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     return;
   }
   // ================= serial role (waves 0 and 1)
-  MsrS<CD, PACK> x;
-  msr_setup_S<CD, PACK>(x, mc, sp, fmu, HPH, ws);
+  MsrS<CD> x;
+  msr_setup_S<CD>(x, mc, sp, fmu, HPH, ws);
 
   // wave 0, lane d < D owns sub-band block d; wave 1, lane j < N owns modulator block D + j
   const int lane = tid & 63;
@@ -767,11 +764,11 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       // (tables, q0, s0, Gaussian weights: worker waves)
       lds_barrier();                 // B4
       IH_STAMP(1);
-      // (MFMA sums: worker waves)
+      // (bin sums: worker waves)
       lds_barrier();                 // B5
       IH_STAMP(2);
       {
-        msp_reduce<CD>(x);
+        msr_reduce<CD>(x);
         msp_wave_fence();
         if (act) {
           const int ko = kk * M;

@@ -167,13 +167,10 @@
   P void nagp::ihgp_adf_kernel<7> NAGP_SIG_IHA;
 
 #define NAGP_LIST_IHA8(P)                                                                                                  \
-  P void nagp::ihgp_adf8_kernel<1, false> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, false> NAGP_SIG_IHA;            \
-  P void nagp::ihgp_adf8_kernel<3, false> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, false> NAGP_SIG_IHA;            \
-  P void nagp::ihgp_adf8_kernel<5, false> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, false> NAGP_SIG_IHA;            \
-  P void nagp::ihgp_adf8_kernel<7, false> NAGP_SIG_IHA;                                                                  \
-  P void nagp::ihgp_adf8_kernel<1, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, true> NAGP_SIG_IHA;              \
-  P void nagp::ihgp_adf8_kernel<3, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, true> NAGP_SIG_IHA;              \
-  P void nagp::ihgp_adf8_kernel<5, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, true> NAGP_SIG_IHA;
+  P void nagp::ihgp_adf8_kernel<1> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2> NAGP_SIG_IHA;                          \
+  P void nagp::ihgp_adf8_kernel<3> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4> NAGP_SIG_IHA;                          \
+  P void nagp::ihgp_adf8_kernel<5> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6> NAGP_SIG_IHA;                          \
+  P void nagp::ihgp_adf8_kernel<7> NAGP_SIG_IHA;
 
 // the role-specialised sweep for likModulatorPreCalcwn (nagp_momsq.hpp)
 #define NAGP_LIST_IHA8Q(P)                                                                                                 \
@@ -183,13 +180,10 @@
 
 // the ADF sweep of the full-covariance filter with role-specialised waves (nagp_gfadf8.hpp): one or two lower tiles per thread
 #define NAGP_LIST_GF_A8T(P, TPT, ST)                                                                                       \
-  P void nagp::gf_adf8_kernel<TPT, 1, false, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 2, false, ST> NAGP_SIG_GF;        \
-  P void nagp::gf_adf8_kernel<TPT, 3, false, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 4, false, ST> NAGP_SIG_GF;        \
-  P void nagp::gf_adf8_kernel<TPT, 5, false, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 6, false, ST> NAGP_SIG_GF;        \
-  P void nagp::gf_adf8_kernel<TPT, 7, false, ST> NAGP_SIG_GF;                                                                \
-  P void nagp::gf_adf8_kernel<TPT, 1, true, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 2, true, ST> NAGP_SIG_GF;          \
-  P void nagp::gf_adf8_kernel<TPT, 3, true, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 4, true, ST> NAGP_SIG_GF;          \
-  P void nagp::gf_adf8_kernel<TPT, 5, true, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 6, true, ST> NAGP_SIG_GF;
+  P void nagp::gf_adf8_kernel<TPT, 1, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 2, ST> NAGP_SIG_GF;                \
+  P void nagp::gf_adf8_kernel<TPT, 3, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 4, ST> NAGP_SIG_GF;                \
+  P void nagp::gf_adf8_kernel<TPT, 5, ST> NAGP_SIG_GF; P void nagp::gf_adf8_kernel<TPT, 6, ST> NAGP_SIG_GF;                \
+  P void nagp::gf_adf8_kernel<TPT, 7, ST> NAGP_SIG_GF;
 #define NAGP_LIST_GF_A81(P) NAGP_LIST_GF_A8T(P, 1, false)
 #define NAGP_LIST_GF_A82(P) NAGP_LIST_GF_A8T(P, 2, false)
 #define NAGP_LIST_GF_A83(P) NAGP_LIST_GF_A8T(P, 2, true)

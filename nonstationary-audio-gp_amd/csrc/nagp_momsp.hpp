@@ -41,13 +41,11 @@ __host__ __device__ inline int msp_qterms(int D) { return D <= 16 ? 4 : (D <= 32
 // LDS workspace (offsets in doubles).  Tables lk | xg | xg2 | e | t1 | ve, MSP_TS entries each.
 struct MspLay { int lk, xg, xg2, e, t1, ve, one, zero, Q, Q2, v, q0, s0, c0, c1, c2, part, acc, marg, wwt, total; };
 // LAY 0: the 256-thread layout (four waves share every stage); LAY 1: the role layout of 512 threads (nagp_ihgp.hpp:
-// two serial waves, six worker waves: six partial blocks, 96 addressable MFMA steps)
+// two serial waves, six worker waves; `part` holds the results of the bin sums, msr_sums)
 constexpr int MSR_NWK = 6;     // worker waves of the role layout
-constexpr int MSR_NST = 20;    // MFMA steps of a worker wave that has its SIMD's matrix core to itself (the others take half)
-constexpr int MSR_NSTP = 16;   // ... in the packed form (eight points per step, four MFMA workers)
-constexpr int MSR_NMEM = 16;   // members of a marginal sum per lane (four lanes per marginal)
-constexpr int MSR_NMARG = 32;  // marginal sums (non-centre (dimension, coordinate) pairs)
-constexpr int MSR_CS = 8 * 48 + 8 * MSR_NSTP + 1;      // every point a (zero-padded) MFMA step can address
+constexpr int MSR_NMEM = 16;   // members of a bin sum per lane (bins of up to 64 members span 2 or 4 lanes)
+constexpr int MSR_NMARG = 32;  // marginal sums (non-centre (dimension, coordinate) pairs) of nagp_momsq.hpp
+constexpr int MSR_CS = 64 * MSR_NWK + 1;      // one weight per worker lane
 __host__ __device__ inline MspLay msp_layout(int CD, int D, int LAY = 0) {
   MspLay l;
   const int cs = LAY ? MSR_CS : MSP_CS, nparts = LAY ? MSR_NWK : MSP_NW;
@@ -84,7 +82,6 @@ __device__ __forceinline__ int opaque_zero() { int z = 0; asm volatile("" : "+v"
 template <int CD>
 struct MspCtx {
   static constexpr int NPS = MSP_NPS, NST = MSP_NST, WSTR = 4 * MSP_NW, NPART = MSP_NW, CS = MSP_CS;
-  static constexpr bool PACKED = false;
   int lw, qw;          // wave that evaluates the link tables / wave that forms q0, s0 (wave-uniform)
   // stage A / B, wave lw: lane t = j*nd + c
   double xdc; msp_rp a_mu, a_s2, a_l0[CD], a_l0own, a_qrow, a_qjj, a_v; msp_wp a_out;   // a_out[k*MSP_TS]: lk, xg, xg2, e, t1, ve
@@ -448,18 +445,17 @@ __device__ __forceinline__ void msp_stage2(const X& x, const MomCfg& c, double* 
   if (__builtin_amdgcn_readfirstlane(x.m_on) == 0) return;      // a wave outside the stage has no partial block
   const int nst = __builtin_amdgcn_readfirstlane(x.nst);
   constexpr int NST = X::NST, WS = X::WSTR;
-  constexpr bool SAMEB = X::PACKED;      // packed form: the column operand is the unweighted row operand (no second read)
   v4d acc0 = {0.0, 0.0, 0.0, 0.0}, acc1 = {0.0, 0.0, 0.0, 0.0};
   double a[4], bb[4], w[4];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) { a[u] = *x.m_a[u]; bb[u] = SAMEB ? a[u] : *x.m_b[u]; w[u] = x.m_w0[WS * u]; }
+  for (int u = 0; u < 4; ++u) { a[u] = *x.m_a[u]; bb[u] = *x.m_b[u]; w[u] = x.m_w0[WS * u]; }
 #pragma unroll
   for (int s0 = 0; s0 < NST; s0 += 4) {
     if (s0 < nst) {      // uniform; steps beyond nst inside the group of four carry zero operands
       double an[4], bn[4], wn_[4];
       if (s0 + 4 < NST) {
 #pragma unroll
-        for (int u = 0; u < 4; ++u) { an[u] = *x.m_a[s0 + 4 + u]; bn[u] = SAMEB ? an[u] : *x.m_b[s0 + 4 + u]; wn_[u] = x.m_w0[WS * (s0 + 4 + u)]; }
+        for (int u = 0; u < 4; ++u) { an[u] = *x.m_a[s0 + 4 + u]; bn[u] = *x.m_b[s0 + 4 + u]; wn_[u] = x.m_w0[WS * (s0 + 4 + u)]; }
       }
       acc0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[0] * w[0], bb[0], acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a[1] * w[1], bb[1], acc1, 0, 0, 0);
@@ -471,26 +467,15 @@ __device__ __forceinline__ void msp_stage2(const X& x, const MomCfg& c, double* 
       }
     }
   }
-  if constexpr (X::PACKED) {
-    // the two diagonal 8x8 blocks (points 8s+kq / 8s+4+kq) added in registers: element (8+r, 8+c) sits in lane i = c + 8 of the
-    // same 16-lane row, register 2 + r/4; the partial block that goes to LDS is 8 x 8
-    const v4d a = acc0 + acc1;
-    const double t0 = a[0] + dpp_mov<0x108>(a[2]), t1 = a[1] + dpp_mov<0x108>(a[3]);     // row_shl:8
-    if (((int)threadIdx.x & 15) < 8) { x.m_part[0] = t0; x.m_part[64] = t1; }
-  } else {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) x.m_part[64 * r] = acc0[r] + acc1[r];      // element (kq + 4r, i) of the block
-  }
+  for (int r = 0; r < 4; ++r) x.m_part[64 * r] = acc0[r] + acc1[r];      // element (kq + 4r, i) of the block
 }
 
 // fixed-order sum of the partials: lanes o < msp_nacc(CD) of ONE wave; the same wave may read acc after msp_wave_fence()
 template <int CD, class X>
 __device__ __forceinline__ void msp_reduce(const X& x) {
   const int lane = threadIdx.x & 63;
-  constexpr int nq = CD * (CD + 1) / 2;
-  bool on = lane < msp_nacc(CD);
-  if constexpr (X::PACKED) on = on && !(lane >= CD + nq && lane < 3 * CD + nq);     // g1, g2 come from the marginal sums
-  if (on) {
+  if (lane < msp_nacc(CD)) {
     double a = x.r_src[0];
 #pragma unroll
     for (int w = 1; w < X::NPART; ++w) a += x.r_src[256 * w];
@@ -544,37 +529,51 @@ __device__ __forceinline__ void msp_outputs(msp_rp acc, bool sub, int jmod, cons
 // =====================================================================================================================
 // Role layout (LAY = 1): 512 threads.  Waves 0 and 1 carry the serial stages of the caller (wave 1 also evaluates the link
 // tables and e / t1 / ve); waves 2 .. 7 carry the parallel ones: Q / 2Q / v on waves 2..4, q0 / s0 on wave 5, one sigma
-// point per lane of the six (<= 384 points), the MFMA steps round the six.  The two roles run in separate loops of the
+// point per lane of the six (<= 384 points), the cubature sums round the six.  The two roles run in separate loops of the
 // kernel, so a wave holds the registers of its own role only: two waves per SIMD within 256 registers each.
+//
+// The cubature sums (likModulatorNMFPower.m:59-80) from BIN SUMS over static member lists, on the VALU.  Every sigma point
+// differs from the centre in at most four coordinates, so with lk_pj = l0_j + e_j(c_pj) (e_j(centre) = 0) and
+//   S_k = sum_p c_k,p  (k = 0, 1, 2),   Ck(j,c) = sum of c_k over the points whose coordinate j is the non-centre value c,
+//   C2(j,c; j',c') = the same sum of c2 over the points that have both,
+// the 40 sums of a step (msp_nacc) are
+//   Z = S0,   u_j = S1 l0_j + U_j,   U_j = sum_c C1(j,c) e_j(c)
+//   R_jj' = S2 l0_j l0_j' + l0_j' E_j + l0_j E_j' + P_jj',   E_j = sum_c C2(j,c) e_j(c),
+//   P_jj' = sum_{c,c'} C2(j,c; j',c') e_j(c) e_j'(c')  (j != j'),   P_jj = sum_c C2(j,c) e_j(c)^2
+//   g1_j = sum_c C0(j,c) xg_j(c)  (xg of the centre is zero),   g2_j = G2_j + S0 xg2_j(centre),
+//   G2_j = sum_c C0(j,c) (xg2_j(c) - xg2_j(centre))  [the centre bin is S0 - sum_c C0(j,c)]
+// In exact arithmetic these are the dense sums sum_p c_k,p lk_pj lk_pj' ...; only the order of summation differs, and every
+// term is bounded by |c2| (|l0| + |e|)^2 -- the bound of the terms of the dense sum -- so the rounding error is of its size.
+// Level 1: each worker lane adds <= MSR_NMEM weights of one bin (bins of up to 64 members span an aligned group of 2 or 4
+// lanes, combined by DPP); level 2: each worker lane forms <= MSR_KT products bin * table * table of bins of ITS OWN wave
+// (behind msp_wave_fence, no barrier) -- U, E, P, g1, G2, S; msr_reduce on the serial waves combines them as above.  The
+// member and term lists are static: the host builds them once per plan (msr_build_desc, nagp_api_plan.hpp) into MomSp::bdesc.
 constexpr int MSR_NT = 512;
 constexpr int MSR_W0 = 2;      // first worker wave
+constexpr int MSR_KT = 4;      // level-2 terms per lane (outputs with more span an aligned group of 2 or 4 lanes)
+constexpr int MSR_DW = MSR_NMEM + 1 + 3 * MSR_KT + 1;   // descriptor ints per worker lane: members | group flags | terms | group flags
+constexpr int MSR_RW = 8;      // descriptor ints per lane of msr_reduce: p, a, b, c, d, s, f, g  ->  p + c d + a b + s f g
+constexpr int MSR_NL = 64 * MSR_NWK;                    // worker lanes; level-1 results at part + L, level-2 results at part + MSR_NL + L
+constexpr int MSR_MONE = 2 * MSR_NL;                    // part + MSR_MONE: the constant -1
+__host__ __device__ inline int msr_desc_ints() { return MSR_NL * MSR_DW + 64 * MSR_RW; }
 
-// PACK (<= 6 components): an MFMA step takes EIGHT points -- rows / columns 0..7 of the block belong to points 8s+kq, rows /
-// columns 8..15 to points 8s+4+kq; A_p = [c2 lk_0.. | c1 | c0], B_p = [lk_0.. | 1], and the two diagonal 8x8 blocks are summed.
-// Half the MFMA steps; the sums over c0 xg_j and c0 xg2_j, which no longer fit the block, come from the marginal sums
-// C0(j,c) = sum of c0 over the points with coordinate c in dimension j (static member lists, two lanes of one worker wave per
-// marginal, beside the MFMA steps):  g1_j = sum_c C0(j,c) xg(j,c),  g2_j = sum_c C0(j,c) xg2(j,c),  C0(j,centre) = sum c0 - rest.
-template <int CD, bool PACK>
+template <int CD>
 struct MsrS {
-  static constexpr int NPART = MSR_NWK;
-  static constexpr bool PACKED = PACK;
   int lw;
   double xdc; msp_rp a_mu, a_s2, a_l0[CD], a_l0own, a_qrow, a_qjj, a_v; msp_wp a_out;
-  msp_rp r_src; msp_wp r_dst; msp_rp accp;
+  msp_rp r_p[MSR_RW]; msp_wp r_dst; msp_rp accp;
 };
-template <int CD, bool PACK>
+template <int CD>
 struct MsrW {
-  static constexpr int NPS = 1, NST = PACK ? MSR_NSTP : MSR_NST, WSTR = PACK ? 8 : 4, CS = MSR_CS;
-  static constexpr bool PACKED = PACK;
+  static constexpr int NPS = 1, CS = MSR_CS;
   int q_kind; msp_rp q_ww, q_src; msp_wp q_out0, q_out1, q_out2, q_out3;
   int b_kind; msp_rp b_p0, b_p1, b_p2;
   // folded form (msr_fold): EVERY worker wave forms the tables e / t1 / ve (lanes < CD*nd) and q0, s0 for itself between B2 and the
   // weights -- no barrier B3, no wait for the serial wave
   msp_rp a_l0[CD], a_l0own, a_qrow, a_qjj, a_v; msp_wp a_out; msp_rp f_p0, f_p1, f_p2;
   msp_rp p_e[1][MSP_NZ], p_q[1][6]; msp_wp p_c[1]; double p_wn[1]; bool p_ok[1]; int p_any[1];
-  msp_rp m_a[NST], m_b[NST], m_w0; msp_wp m_part; int nst, m_on;
-  msp_rp g_mem[PACK ? MSR_NMEM : 1]; msp_wp g_out;              // last worker: members of this lane's half of a marginal
-  msp_rp h_marg, h_xg, h_xg2, h_c0p; msp_wp h_acc; int h_nd, h_c0, h_nj;   // ... lane < h_nj: g1_j, g2_j of its dimension; every lane: its share of sum c0
+  msp_rp s_mem[MSR_NMEM]; msp_wp s_out; int s_grp;                    // level 1: members, result slot, group flags (1: lane ^ 1, 2: lane ^ 2)
+  msp_rp t_bin[MSR_KT], t_fa[MSR_KT], t_fb[MSR_KT]; msp_wp t_out; int t_grp;   // level 2
 };
 
 // constants, zero entries of the tables, zero weights beyond the points (every thread of the workgroup)
@@ -583,11 +582,11 @@ __device__ __forceinline__ void msr_init(int CD, int D, double* ws) {
   for (int i = threadIdx.x; i < 6 * MSP_TS; i += MSR_NT) ws[i] = 0.0;
   if (threadIdx.x == 0) ws[l.one] = 1.0;
   for (int i = threadIdx.x; i < 3 * MSR_CS; i += MSR_NT) ws[l.c0 + i] = 0.0;
-  for (int i = threadIdx.x; i < MSR_NWK * 256; i += MSR_NT) ws[l.part + i] = 0.0;   // partial blocks of workers without MFMA steps stay zero
+  for (int i = threadIdx.x; i <= MSR_MONE; i += MSR_NT) ws[l.part + i] = (i == MSR_MONE) ? -1.0 : 0.0;
 }
 
-template <int CD, bool PACK>
-__device__ __forceinline__ void msr_setup_S(MsrS<CD, PACK>& x, const MomCfg& c, const MomSp& sp, const double* fmu, const double* HPH, double* ws) {
+template <int CD>
+__device__ __forceinline__ void msr_setup_S(MsrS<CD>& x, const MomCfg& c, const MomSp& sp, const double* fmu, const double* HPH, double* ws) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nd = c.nd, D = c.D, TN = CD * nd;
   const MspLay l = msp_layout(CD, D, 1);
@@ -608,26 +607,17 @@ __device__ __forceinline__ void msr_setup_S(MsrS<CD, PACK>& x, const MomCfg& c, 
     x.a_out = (msp_wp)(ws + t);
   }
   {
-    const int o = lane, nq = CD * (CD + 1) / 2;
-    int row = 0, col = 0;
-    if (o < CD) { row = CD; col = o; }
-    else if (o < CD + nq) { int r = o - CD, j = 0; while (r >= CD - j) { r -= CD - j; ++j; } row = j; col = j + r; }
-    else if (o < 2 * CD + nq) { row = 2 * CD + 1; col = CD + (o - CD - nq); }
-    else if (o < 3 * CD + nq) { row = CD + 1 + (o - 2 * CD - nq); col = 2 * CD; }
-    else { row = 2 * CD + 1; col = 2 * CD; }
-    if constexpr (PACK) {       // block rows [c2 lk_j | c1 | c0], columns [lk_j | 1]: u and R sit where they sat; the g1 / g2 lanes
-      if (o >= CD + nq && o < 3 * CD + nq) { row = 0; col = 7; }      // read a zero column, Z is (c0 row, column of ones)
-      else if (o >= 3 * CD + nq) { row = CD + 1; col = CD; }
-    }
-    x.r_src = (msp_rp)(ws + l.part + row * 16 + col);
+    const int* d = sp.bdesc + (size_t)MSR_NL * MSR_DW + (size_t)lane * MSR_RW;
+#pragma unroll
+    for (int i = 0; i < MSR_RW; ++i) x.r_p[i] = (msp_rp)(ws + d[i]);
     const int ab = (wave == 1) ? 64 : 0;
-    x.r_dst = (msp_wp)(ws + l.acc + ab + o);
+    x.r_dst = (msp_wp)(ws + l.acc + ab + lane);
     x.accp = (msp_rp)(ws + l.acc + ab) + oz;
   }
 }
 
-template <int CD, bool PACK>
-__device__ __forceinline__ void msr_setup_W(MsrW<CD, PACK>& x, const MomCfg& c, const MomSp& sp, const double* Wl /* LDS D x CD */,
+template <int CD>
+__device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const MomSp& sp, const double* Wl /* LDS D x CD */,
                                              const double* fmu, const double* HPH, double* ws) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave - MSR_W0;     // wr = 0 .. 5
   const int nd = c.nd, D = c.D, npt = c.n_pts;
@@ -725,144 +715,72 @@ __device__ __forceinline__ void msr_setup_W(MsrW<CD, PACK>& x, const MomCfg& c, 
     x.p_c[0] = (msp_wp)(ws + l.c0 + p);
     x.p_wn[0] = ok ? c.wn[p] : 0.0;
   }
-  // ---- stage 2: contiguous step ranges.  A wave's FP64 MFMA holds its SIMD's issue, so two workers on one SIMD gain nothing
-  // over one: waves w and w+4 share a SIMD, the serial waves 0 / 1 sit out this stage, hence workers 2 and 3 (waves 4, 5) have
-  // a matrix core to themselves and take a double share; the steps are dealt in eight slots (the first nstep % 8 one longer).
+  // ---- cubature sums: this lane's members and terms (host lists; offsets in doubles from ws, unused entries address the zero word)
   {
-    constexpr int PPS = PACK ? 8 : 4;                 // points per step
-    constexpr int NSTX = MsrW<CD, PACK>::NST;
-    const int i = lane & 15, kq = lane >> 4;
-    const int grp = PACK ? (i >> 3) : 0, f = PACK ? (i & 7) : i;
-    const int nstep = (npt + PPS - 1) / PPS;
-    const bool on = wr >= 0 && wr < MSR_NWK;
-    // PACK: the last two workers form the marginal sums instead, on the SIMDs of workers 0 and 1 -- which therefore take one
-    // slot each, workers 2 and 3 three
-    const int base = nstep >> 3, rem = nstep & 7;
-    auto slot_start = [&](int sl) { return sl * base + (sl < rem ? sl : rem); };     // first step of slot sl (sl = 8: nstep)
-    int sl0, sl1;
-    if (PACK) { sl0 = (wr <= 1) ? wr : ((wr == 2) ? 2 : 5); sl1 = (wr <= 1) ? wr + 1 : ((wr == 2) ? 5 : 8); }
-    else { sl0 = (wr <= 2) ? ((wr == 2) ? 2 : wr) : ((wr == 3) ? 4 : wr + 2); sl1 = (wr == 2 || wr == 3) ? sl0 + 2 : sl0 + 1; }
-    const bool mf = on && (!PACK || wr < 4);
-    const int st0 = mf ? slot_start(sl0) : 0, st1 = mf ? slot_start(sl1) : 0;
-    x.nst = st1 - st0;
-    x.m_on = (on && x.nst > 0) ? 1 : 0;   // a worker without steps skips the stage: its partial block was zeroed by msr_init
-    int wbase = l.c0;
-    if (PACK) { if (f < CD) wbase = l.c2; else if (f == CD) wbase = l.c1; }
-    else { if (i < CD) wbase = l.c2; else if (i == CD) wbase = l.c1; }
-    x.m_w0 = (msp_rp)(ws + wbase + PPS * st0 + 4 * grp + kq);
-    x.m_part = (msp_wp)(ws + l.part + (on ? wr : 0) * 256 + kq * 16 + i);
+    const int L = (wr >= 0 && wr < MSR_NWK) ? wr * 64 + lane : 0;
+    const int* d = sp.bdesc + (size_t)L * MSR_DW;
 #pragma unroll
-    for (int s_ = 0; s_ < NSTX; ++s_) {
-      const int p = PPS * (st0 + s_) + 4 * grp + kq;
-      const bool ok = on && (s_ < x.nst) && (p < npt);
-      int offA = l.zero, offB = l.zero;
-      if (ok) {
-        const unsigned char* cp = c.code + (size_t)p * CD;
-        if constexpr (PACK) {
-          if (f < CD) { offA = l.lk + f * nd + cp[f]; offB = offA; }
-          else if (f == CD || f == CD + 1) { offA = l.one; offB = l.one; }     // (column CD+1 duplicates the column of ones: unused sums)
-        } else {
-          if (i < CD) offA = l.lk + i * nd + cp[i];
-          else if (i == CD) offA = l.one;
-          else if (i <= 2 * CD) offA = l.xg2 + (i - CD - 1) * nd + cp[i - CD - 1];
-          else if (i == 2 * CD + 1) offA = l.one;
-          if (i < CD) offB = l.lk + i * nd + cp[i];
-          else if (i < 2 * CD) offB = l.xg + (i - CD) * nd + cp[i - CD];
-          else if (i == 2 * CD) offB = l.one;
-        }
-      }
-      x.m_a[s_] = (msp_rp)(ws + offA); x.m_b[s_] = (msp_rp)(ws + offB);
-    }
-  }
-  // ---- marginal sums (PACK): workers 4 and 5 take the dimensions below / from jsplit; lane = 4 * (local marginal) + quarter,
-  // the members of a marginal go round its four lanes
-  x.g_out = (msp_wp)(ws + l.acc + 127);
-  if constexpr (PACK) {
-    const msp_rp zero = (msp_rp)(ws + l.zero);
-    const int jsplit = (CD + 1) / 2;
-    const int jlo = (wr == MSR_NWK - 2) ? 0 : jsplit, jhi = (wr == MSR_NWK - 2) ? jsplit : CD;
-    const int ml = lane >> 2, quarter = lane & 3;
-    const int jj = jlo + ml / (nd - 1), cc = ml % (nd - 1);
-    const bool valid = (wr >= MSR_NWK - 2) && jj < jhi;
-    const int j = valid ? jj : 0;
-    const int code = (cc < sp.c0) ? cc : cc + 1;
-    if (valid && quarter == 0) x.g_out = (msp_wp)(ws + l.marg + j * (nd - 1) + cc);
-    {   // g1_j, g2_j of modulator j = jlo + lane, written into the copy of the reduced sums that wave 1 (the modulator sites) reads
-      const int nq = CD * (CD + 1) / 2;
-      const int jm = (jlo + lane < jhi) ? jlo + lane : 0;
-      x.h_nd = nd; x.h_c0 = sp.c0; x.h_nj = (wr >= MSR_NWK - 2) ? jhi - jlo : 0;
-      x.h_marg = (msp_rp)(ws + l.marg + jm * (nd - 1));
-      x.h_xg = (msp_rp)(ws + l.xg + jm * nd);
-      x.h_xg2 = (msp_rp)(ws + l.xg2 + jm * nd);
-      x.h_acc = (msp_wp)(ws + l.acc + 64 + CD + nq + jm);
-      x.h_c0p = (msp_rp)(ws + l.c0 + lane);
-    }
-    int pos = 0, cnt = 0;
+    for (int k = 0; k < MSR_NMEM; ++k) x.s_mem[k] = (msp_rp)(ws + d[k]);
+    x.s_grp = d[MSR_NMEM];
+    x.s_out = (msp_wp)(ws + l.part + L);
 #pragma unroll
-    for (int k = 0; k < MSR_NMEM; ++k) {
-      int found = -1;
-      while (valid && pos < npt && found < 0) {
-        if (c.code[(size_t)pos * CD + j] == code) {
-          if ((cnt & 3) == quarter) found = pos;
-          ++cnt;
-        }
-        ++pos;
-      }
-      x.g_mem[k] = (found >= 0) ? (msp_rp)(ws + l.c0 + found) : zero;
+    for (int t = 0; t < MSR_KT; ++t) {
+      x.t_bin[t] = (msp_rp)(ws + d[MSR_NMEM + 1 + 3 * t]);
+      x.t_fa[t] = (msp_rp)(ws + d[MSR_NMEM + 2 + 3 * t]);
+      x.t_fb[t] = (msp_rp)(ws + d[MSR_NMEM + 3 + 3 * t]);
     }
+    x.t_grp = d[MSR_NMEM + 1 + 3 * MSR_KT];
+    x.t_out = (msp_wp)(ws + l.part + MSR_NL + L);
   }
 }
 
-// marginal sums of c0, then g1_j, g2_j of this wave's dimensions (workers 4 and 5, beside the MFMA steps of the others;
-// after the barrier behind stage 1b)
-template <int CD, class X>
-__device__ __forceinline__ void msr_marginals(const X& x) {
-  const int lane = threadIdx.x & 63;
-  const int nd = __builtin_amdgcn_readfirstlane(x.h_nd), c0 = __builtin_amdgcn_readfirstlane(x.h_c0);
-  // everything that does not depend on the marginals first (one LDS round trip): members, this lane's share of sum c0, the
-  // table values of the g1 / g2 lanes (the other lanes read dimension 0's)
-  double mem[MSR_NMEM];
+// sum over the lanes of an aligned group of 1, 2 or 4 (grp bit 0: lane ^ 1 belongs to it, bit 1: lane ^ 2); every lane of the wave executes it
+__device__ __forceinline__ double msr_group_sum(double s, int grp) {
+  const double n1 = dpp_mov<0xB1>(s);
+  s = (grp & 1) ? s + n1 : s;
+  const double n2 = dpp_mov<0x4E>(s);
+  return (grp & 2) ? s + n2 : s;
+}
+
+// the cubature sums of one worker wave (after the barrier behind stage 1b; no barrier): level 1, then level 2 from this wave's own bins
+template <class X>
+__device__ __forceinline__ void msr_sums(const X& x) {
+  // every read that does not depend on the bins first -- the members and the table factors of the terms: one LDS round trip
+  double m[MSR_NMEM], fa[MSR_KT], fb[MSR_KT];
 #pragma unroll
-  for (int k = 0; k < MSR_NMEM; ++k) mem[k] = *x.g_mem[k];
-  const double z0 = x.h_c0p[0] + x.h_c0p[64], z1 = x.h_c0p[128] + x.h_c0p[192], z2 = x.h_c0p[256] + x.h_c0p[320];
-  const bool small = nd <= 5;
-  double a[4], b[4];
+  for (int k = 0; k < MSR_NMEM; ++k) m[k] = *x.s_mem[k];
 #pragma unroll
-  for (int cc = 0; cc < 4; ++cc) {
-    const int ci = (cc < nd - 1) ? cc : 0;
-    const int code = (ci < c0) ? ci : ci + 1;
-    a[cc] = x.h_xg[code]; b[cc] = x.h_xg2[code];
-  }
-  const double bc = x.h_xg2[c0];
+  for (int t = 0; t < MSR_KT; ++t) { fa[t] = *x.t_fa[t]; fb[t] = *x.t_fb[t]; }
+#pragma unroll
+  for (int k = 0; k < MSR_NMEM; ++k) asm volatile("" : "+v"(m[k]));
   double s0 = 0.0, s1 = 0.0;
 #pragma unroll
-  for (int k = 0; k < MSR_NMEM; k += 2) { s0 += mem[k]; s1 += mem[k + 1]; }
-  double s_ = s0 + s1;
-  s_ += dpp_mov<0xB1>(s_);
-  s_ += dpp_mov<0x4E>(s_);            // the four lanes of the marginal
-  *x.g_out = s_;                      // lanes other than the first of a marginal: scratch slot
-  const double zraw = wave_sum((z0 + z1) + z2);      // the weights beyond n_pts are zero; MSR_CS >= 384
+  for (int k = 0; k < MSR_NMEM; k += 2) { s0 += m[k]; s1 += m[k + 1]; }
+  *x.s_out = msr_group_sum(s0 + s1, x.s_grp);
   msp_wave_fence();
-  if (lane < __builtin_amdgcn_readfirstlane(x.h_nj)) {
-    double g1 = 0.0, g2 = 0.0, ms = 0.0;
-    if (small) {
-      double m[4];
+  double bv[MSR_KT];
 #pragma unroll
-      for (int cc = 0; cc < 4; ++cc) m[cc] = x.h_marg[(cc < nd - 1) ? cc : 0];
+  for (int t = 0; t < MSR_KT; ++t) bv[t] = *x.t_bin[t];
 #pragma unroll
-      for (int cc = 0; cc < 4; ++cc) {
-        const double mm = (cc < nd - 1) ? m[cc] : 0.0;
-        g1 = fma(mm, a[cc], g1); g2 = fma(mm, b[cc], g2); ms += mm;
-      }
-    } else {
-      for (int cc = 0; cc < nd - 1; ++cc) {
-        const int code = (cc < c0) ? cc : cc + 1;
-        const double mm = x.h_marg[cc];
-        g1 = fma(mm, x.h_xg[code], g1); g2 = fma(mm, x.h_xg2[code], g2); ms += mm;
-      }
-    }
-    g2 = fma(zraw - ms, bc, g2);      // xg of the centre coordinate is zero
-    x.h_acc[0] = g1; x.h_acc[CD] = g2;
+  for (int t = 0; t < MSR_KT; ++t) asm volatile("" : "+v"(bv[t]));
+  double v0 = 0.0, v1 = 0.0;
+#pragma unroll
+  for (int t = 0; t < MSR_KT; t += 2) { v0 = fma(bv[t] * fa[t], fb[t], v0); v1 = fma(bv[t + 1] * fa[t + 1], fb[t + 1], v1); }
+  *x.t_out = msr_group_sum(v0 + v1, x.t_grp);
+}
+
+// the 40 sums (acc layout of msp_outputs) from the level-2 results: lanes o < msp_nacc(CD) of ONE serial wave, after the barrier
+// behind msr_sums; the same wave may read acc after msp_wave_fence().  p + c d + a b + s f g, every operand one LDS read.
+template <int CD, class X>
+__device__ __forceinline__ void msr_reduce(const X& x) {
+  const int lane = threadIdx.x & 63;
+  if (lane < msp_nacc(CD)) {
+    double r[MSR_RW];
+#pragma unroll
+    for (int i = 0; i < MSR_RW; ++i) r[i] = *x.r_p[i];
+#pragma unroll
+    for (int i = 0; i < MSR_RW; ++i) asm volatile("" : "+v"(r[i]));
+    *x.r_dst = fma(r[5] * r[6], r[7], fma(r[1], r[2], fma(r[3], r[4], r[0])));
   }
 }
 
