@@ -6,7 +6,11 @@ linear, SURVEY C-12) and :148-191 (steady-state smoother gain G and covariance P
 MATLAB's Control-System-Toolbox `dare` is stood in for by a structure-preserving doubling iteration that solves all
 (channel, grid point) Riccati equations of one block size in one batched NumPy sweep (1 216 equations at cfg3: 0.03 s
 instead of 1.0 s with one scipy.linalg.solve_discrete_are call each); any equation the doubling does not converge on
-falls back to SciPy's QZ solver, and a point that fails there is dropped as the reference drops it (:118-126).
+falls back to SciPy's QZ solver, and a point that fails there is dropped as the reference drops it (:118-126).  One Newton
+step on the residual follows.  The steady-state covariances of 6- and 8-state sub-band blocks are conditioned 1e8 .. 1e12, and
+the smoother's QQ = P - G*PP*G' (:167) is down to 1e-12 of P there: QQ is formed from a sum of positive semi-definite terms
+that equals it in exact arithmetic, not by that subtraction.  tests/test_dare_fixture.py holds PP, G and PS2 to a
+60-digit solution of the same equations (tests/golden/dare_sixeight_states.npz).
 """
 import numpy as np
 import scipy.linalg as sla
@@ -45,6 +49,37 @@ def _dare_batch(At, h, Q, rr, iters=60, tol=1e-15):
     return H, ok
 
 
+def _stein_batch(F, C):
+    """X = F X F' + C for a batch, as the b^2 x b^2 linear system (I - F (x) F) vec X = vec C."""
+    B, b, _ = F.shape
+    KK = np.einsum('qij,qkl->qikjl', F, F).reshape(B, b * b, b * b)
+    return np.linalg.solve(np.broadcast_to(np.eye(b * b), (B, b * b, b * b)) - KK, C.reshape(B, b * b, 1)).reshape(B, b, b)
+
+
+def _dare_residual(A, Q, h, rr, P):
+    """R = A (P - P h'(h P h' + r)^-1 h P) A' + Q - P and the predictor gain L = A P h' / (h P h' + r)."""
+    Ph = np.einsum('qij,qj->qi', P, h)
+    S = np.einsum('qi,qi->q', h, Ph) + rr
+    R = A @ (P - Ph[:, :, None] * Ph[:, None, :] / S[:, None, None]) @ np.swapaxes(A, 1, 2) + Q - P
+    return R, np.einsum('qij,qj->qi', A, Ph) / S[:, None]
+
+
+def _newton_dare(A, Q, h, rr, P):
+    """One Newton step on the predictive DARE: E = Ac E Ac' + R(P) with Ac = A - L h, P + E kept where its residual is smaller."""
+    with np.errstate(all='ignore'):
+        R, Lg = _dare_residual(A, Q, h, rr, P)
+        Ac = A - Lg[:, :, None] * h[:, None, :]
+        fin = np.isfinite(R).all(axis=(1, 2)) & np.isfinite(Ac).all(axis=(1, 2))
+        try:
+            E = _stein_batch(np.where(fin[:, None, None], Ac, 0.0), np.where(fin[:, None, None], R, 0.0))
+        except np.linalg.LinAlgError:
+            return P
+        Pn = P + (E + np.swapaxes(E, 1, 2)) / 2
+        Rn, _ = _dare_residual(A, Q, h, rr, Pn)
+        better = np.isfinite(Rn).all(axis=(1, 2)) & (np.abs(Rn).max(axis=(1, 2)) < np.abs(R).max(axis=(1, 2)))
+    return np.where(better[:, None, None], Pn, P)
+
+
 def build_tables(A, Q, offsets, h_val, n_grid=200, n_knots=32):
     """Returns (r, PPlist, pp_offsets, PGlist, pg_offsets) in the flat layout of nagp_ihgp_tables."""
     M = len(h_val)
@@ -66,6 +101,7 @@ def build_tables(A, Q, offsets, h_val, n_grid=200, n_knots=32):
                 PP[q] = sla.solve_discrete_are(Ar[q].T, hr[q][:, None], Qr[q], np.array([[rr[q]]])); ok[q] = True
             except Exception:
                 pass
+        PP = _newton_dare(Ar, Qr, hr, rr, PP)
         S = hr[:, 0] ** 2 * PP[:, 0, 0] + rr                              # H PP H' + r
         K = PP[:, :, 0] * hr[:, 0][:, None] / S[:, None]                  # PP H' / S
         P = PP - rr[:, None, None] * (K[:, :, None] * K[:, None, :])      # :163  (C-23: K r K', not K S K')
@@ -77,7 +113,14 @@ def build_tables(A, Q, offsets, h_val, n_grid=200, n_knots=32):
                 G = np.swapaxes(np.linalg.solve(PSkp, np.swapaxes(PAt, 1, 2)), 1, 2)    # P*A'/L'/L
             except np.linalg.LinAlgError:
                 G = np.full_like(P, np.nan)
-        QQ = P - G @ PP @ np.swapaxes(G, 1, 2); QQ = (QQ + np.swapaxes(QQ, 1, 2)) / 2
+        # QQ = P - G PP G' (:167) without the subtraction: G PSkp = P A' gives P - G PSkp G' = (I - G A) P (I - G A)' + G Q G',
+        # and the DARE gives PSkp - PP = (S - r) A K K' A', so QQ = (I - G A) P (I - G A)' + G Q G' + (S - r) (G A K)(G A K)'
+        with np.errstate(all='ignore'):
+            GA = G @ Ar
+            IGA = np.eye(b) - GA
+            GAK = np.einsum('qij,qj->qi', GA, K)
+            QQ = IGA @ P @ np.swapaxes(IGA, 1, 2) + G @ Qr @ np.swapaxes(G, 1, 2) + (S - rr)[:, None, None] * (GAK[:, :, None] * GAK[:, None, :])
+        QQ = (QQ + np.swapaxes(QQ, 1, 2)) / 2
         fin = np.isfinite(QQ).all(axis=(1, 2))
         QQ[~fin] = 0.0
         lam, V = np.linalg.eigh(QQ)                                        # cholcov-style projection on the PSD cone (:169-175)
@@ -85,10 +128,8 @@ def build_tables(A, Q, offsets, h_val, n_grid=200, n_knots=32):
         QQ = (V * lam[:, None, :]) @ np.swapaxes(V, 1, 2)
         # PS2 = dare(G',0,QQ): the Stein equation X = G X G' + QQ as a b^2 x b^2 linear system
         Gs = np.where(np.isfinite(G), G, 0.0)
-        KK = np.einsum('qij,qkl->qikjl', Gs, Gs).reshape(B, b * b, b * b)
-        rhs = QQ.reshape(B, b * b, 1)
         try:
-            PS2 = np.linalg.solve(np.broadcast_to(np.eye(b * b), (B, b * b, b * b)) - KK, rhs).reshape(B, b, b)
+            PS2 = _stein_batch(Gs, QQ)
         except np.linalg.LinAlgError:
             PS2 = np.full_like(P, np.nan)
         ok &= fin & np.isfinite(G).all(axis=(1, 2)) & np.isfinite(PS2).all(axis=(1, 2))

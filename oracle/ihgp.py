@@ -12,6 +12,11 @@ Follows (file:line under /root/reference/matlab):
   apxGrid.m:448-498, 555-565, 695-707  ('interp' on a non-equispaced grid = linear weights, C-12)
 MATLAB `dare` (Control System Toolbox, closed source) -> scipy.linalg.solve_discrete_are /
 solve_discrete_lyapunov.
+Deviation for blocks of more than 4 states (Matern-5/2 and -7/2 sub-bands, steady-state covariances conditioned 1e8 .. 1e12):
+SciPy's DARE solution is off by up to 3e-6 of its size there and is followed by Newton steps on the residual (_newton_dare),
+and the smoother's QQ = P - G*PP*G' (:167), down to 1e-12 of P, is formed as the positive semi-definite sum that equals it in
+exact arithmetic (_smoother_qq).  Without both, PS2 is off by up to 1e-4 of its size; with them the tables meet a 60-digit
+solution of the same equations (tests/golden/dare_sixeight_states.npz, tests/test_dare_fixture.py) to 1e-9.
 Quirks reproduced: C-3, C-4, C-10, C-12, C-18, C-21, C-22.
 """
 import numpy as np
@@ -52,6 +57,8 @@ def forward_tables(A, Q, H, ilist, r_grid_n=200, ro_n=32):
         for j in range(ro.size):
             try:
                 PP = sla.solve_discrete_are(Aii.T, Hn.T, Qii, np.array([[ro[j]]]))
+                if Aii.shape[0] > 4:
+                    PP = _newton_dare(Aii, Qii, Hn, ro[j], PP)
                 rows.append(PP.flatten(order='F')); keep.append(j)
             except Exception:                                   # :118-126 drop failed grid points
                 pass
@@ -80,7 +87,8 @@ def smoother_tables(A, Q, H, ilist, r, PPlisto, ro_list):
             L = np.linalg.cholesky(_lower_sym(Aii @ P @ Aii.T + Qii))   # :165 (non-PD branch is broken, C-14)
             B = P @ Aii.T
             G = np.linalg.solve(L.T, np.linalg.solve(L, B.T)).T           # P*A'/L'/L
-            QQ = P - G @ PP @ G.T; QQ = (QQ + QQ.T) / 2
+            QQ = _smoother_qq(Aii, Qii, P, PP, G, K, Sx - ro[j]) if b > 4 else P - G @ PP @ G.T
+            QQ = (QQ + QQ.T) / 2
             DD, V = np.linalg.eigh(QQ); ind = DD > 0
             QQ = (V[:, ind] * DD[ind][None, :]) @ V[:, ind].T
             try:
@@ -93,6 +101,26 @@ def smoother_tables(A, Q, H, ilist, r, PPlisto, ro_list):
         U = neqinterp_matrix(ro, r)
         PGlist.append(U @ np.array(rows))
     return PGlist
+
+
+def _newton_dare(A, Q, H, r, P, steps=2):
+    """Newton steps on P = A (P - P H'(H P H' + r)^-1 H P) A' + Q: with L = A P H' / (H P H' + r) and Ac = A - L H, the correction E
+    solves E = Ac E Ac' + residual(P)."""
+    for _ in range(steps):
+        S = (H @ P @ H.T)[0, 0] + r
+        res = A @ (P - P @ H.T @ H @ P / S) @ A.T + Q - P
+        Ac = A - (A @ P @ H.T / S) @ H
+        E = sla.solve_discrete_lyapunov(Ac, res)
+        P = P + (E + E.T) / 2
+    return P
+
+
+def _smoother_qq(A, Q, P, PP, G, K, hPPh):
+    """QQ = P - G PP G' as a sum of positive semi-definite terms: G PSkp = P A' gives P - G PSkp G' = (I - G A) P (I - G A)' + G Q G',
+    and the DARE gives PSkp - PP = (H PP H') A K K' A'."""
+    IGA = np.eye(A.shape[0]) - G @ A
+    GAK = G @ A @ K
+    return IGA @ P @ IGA.T + G @ Q @ G.T + hPPh * (GAK @ GAK.T)
 
 
 def _lower_sym(X):

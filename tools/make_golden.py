@@ -65,7 +65,8 @@ def sixstate():
     e3, _ = ogf.gf_ep_modulator_nmf(pr['w'], t, y, None, om, None, k1, k2, 1, D, N, 0.5, d, 3)
     oi = oih.ihgp_ep_modulator_nmf(pr['w'], t, y, None, om, t, k1, k2, 1, D, N, 0.5, d, 3)
     # the same sweeps on the look-up tables the HOST builds (nagp/ihgp_tables.py, batched doubling; the oracle's own come from SciPy's DARE solver):
-    # a 6-state block's steady-state covariances are conditioned ~1e8, the two sets of tables agree to 1e-8 .. 1e-6, and this run isolates the kernels
+    # a 6-state block's steady-state covariances are conditioned ~1e8; both sets of tables meet a 60-digit solution to 1e-9 (tests/test_dare_fixture.py),
+    # and this run isolates the kernels
     from nagp import ihgp_tables, ss as pss
     from oracle import ss as oss
     lik, p1, p2, W = oss.unpack_log(pr['w'], 1, D, N)
