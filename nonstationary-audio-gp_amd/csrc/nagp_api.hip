@@ -33,18 +33,78 @@ static thread_local std::string g_last_error;
 // in that environment must not change what it computes, so NONE of them is read unless NAGP_DEVELOPER=1 is set as well (tests/conftest.py
 // and the scripts under tools/ set it; bench.py and the MEX gateway never do).  The switches that make results meaningless (phase-skipping
 // timing probes) and the test hooks that replace devices or fail allocations say so on stderr once when they are active.
-static const char* dev_env(const char* name) {
+// read_dev_switches() is the only reader of the environment: nagp_plan_create takes one snapshot into the plan (nagp_plan::dev), which
+// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run one per call.
+struct DevSwitches {
+  // presence switches: on when the variable is set to anything
+  bool no_wide = false;          // NAGP_NO_WIDE
+  bool no_sparse = false;        // NAGP_NO_SPARSE
+  bool no_sparse_ep = false;     // NAGP_NO_SPARSE_EP
+  bool no_src = false;           // NAGP_NO_SRC
+  bool no_mfma = false;          // NAGP_NO_MFMA
+  bool no_mfma_big = false;      // NAGP_NO_MFMA_BIG
+  bool dense_delta = false;      // NAGP_DENSE_DELTA
+  bool no_pipeline = false;      // NAGP_NO_PIPELINE
+  bool no_recycle = false;       // NAGP_NO_RECYCLE
+  bool no_xsweep = false;        // NAGP_NO_XSWEEP
+  bool no_cache_tabs = false;    // NAGP_NO_CACHE_TABS
+  bool no_gf_roles = false;      // NAGP_NO_GF_ROLES
+  bool no_gain768 = false;       // NAGP_NO_GAIN768
+  bool no_gain_mfma = false;     // NAGP_NO_GAIN_MFMA
+  bool ih_seq = false;           // NAGP_IH_SEQ
+  bool fb_sequential = false;    // NAGP_FB_SEQUENTIAL
+  bool force_rccl = false;       // NAGP_FORCE_RCCL
+  bool stamps = false;           // NAGP_STAMPS
+  bool ih_roles = true;          // NAGP_IH_ROLES: off when the value starts with '0'
+  int gain_form = 0;             // NAGP_GAIN_FORM: 0 = the plan's rule, 1 = solve, 2 = inv
+  // numeric switches (0: not set, unless said otherwise)
+  int chunks = 12;               // NAGP_CHUNKS (>= 1): smoother chunks per sweep
+  int pipeline_slots = 0;        // NAGP_PIPELINE_SLOTS (>= 1; at most nc - 1 at the use)
+  int mom_chunk = 0;             // NAGP_MOM_CHUNK (>= 64)
+  int kb_f = 0;                  // NAGP_KB_F (1 .. 16)
+  int filter_dbg = 0;            // NAGP_FILTER_DBG
+  int gainm_dbg = 0;             // NAGP_GAINM_DBG
+  int stamp_worker = 0;          // NAGP_STAMP_WORKER
+  int test_fake_devices = 0;     // NAGP_TEST_FAKE_DEVICES (>= 0)
+  int test_fail_device = -1;     // NAGP_TEST_FAIL_DEVICE (-1: none)
+  int test_slot_enomem = -1;     // NAGP_TEST_SLOT_ENOMEM (>= 0; -1: not set)
+};
+
+static DevSwitches read_dev_switches() {
   static const bool on = [] { const char* d = getenv("NAGP_DEVELOPER"); return d && d[0] == '1' && d[1] == 0; }();
-  if (!on) return nullptr;
-  const char* v = getenv(name);
-  if (v && (!strcmp(name, "NAGP_FILTER_DBG") || !strncmp(name, "NAGP_TEST_", 10))) {
-    static std::mutex mu; static std::set<std::string> said;
-    std::lock_guard<std::mutex> lk(mu);
-    if (said.insert(name).second)
-      fprintf(stderr, "[nagp] developer switch %s=%s is active (%s)\n", name, v,
-              !strcmp(name, "NAGP_FILTER_DBG") ? "phases of the filter step are skipped: results are garbage, timing only" : "test hook: devices / allocations are not the real ones");
-  }
-  return v;
+  DevSwitches s;
+  if (!on) return s;
+  auto env = [](const char* name) -> const char* {
+    const char* v = getenv(name);
+    if (v && (!strcmp(name, "NAGP_FILTER_DBG") || !strncmp(name, "NAGP_TEST_", 10))) {
+      static std::mutex mu; static std::set<std::string> said;
+      std::lock_guard<std::mutex> lk(mu);
+      if (said.insert(name).second)
+        fprintf(stderr, "[nagp] developer switch %s=%s is active (%s)\n", name, v,
+                !strcmp(name, "NAGP_FILTER_DBG") ? "phases of the filter step are skipped: results are garbage, timing only" : "test hook: devices / allocations are not the real ones");
+    }
+    return v;
+  };
+  s.no_wide = env("NAGP_NO_WIDE"); s.no_sparse = env("NAGP_NO_SPARSE"); s.no_sparse_ep = env("NAGP_NO_SPARSE_EP"); s.no_src = env("NAGP_NO_SRC");
+  s.no_mfma = env("NAGP_NO_MFMA"); s.no_mfma_big = env("NAGP_NO_MFMA_BIG"); s.dense_delta = env("NAGP_DENSE_DELTA");
+  s.no_pipeline = env("NAGP_NO_PIPELINE"); s.no_recycle = env("NAGP_NO_RECYCLE"); s.no_xsweep = env("NAGP_NO_XSWEEP");
+  s.no_cache_tabs = env("NAGP_NO_CACHE_TABS"); s.no_gf_roles = env("NAGP_NO_GF_ROLES"); s.no_gain768 = env("NAGP_NO_GAIN768");
+  s.no_gain_mfma = env("NAGP_NO_GAIN_MFMA"); s.ih_seq = env("NAGP_IH_SEQ"); s.fb_sequential = env("NAGP_FB_SEQUENTIAL");
+  s.force_rccl = env("NAGP_FORCE_RCCL"); s.stamps = env("NAGP_STAMPS");
+  const char* v;
+  if ((v = env("NAGP_IH_ROLES"))) s.ih_roles = v[0] != '0';
+  if ((v = env("NAGP_GAIN_FORM"))) s.gain_form = !strcmp(v, "solve") ? 1 : (!strcmp(v, "inv") ? 2 : 0);
+  if ((v = env("NAGP_CHUNKS"))) s.chunks = std::max(1, atoi(v));
+  if ((v = env("NAGP_PIPELINE_SLOTS"))) s.pipeline_slots = std::max(1, atoi(v));
+  if ((v = env("NAGP_MOM_CHUNK"))) s.mom_chunk = std::max(64, atoi(v));
+  if ((v = env("NAGP_KB_F"))) s.kb_f = std::max(1, std::min(16, atoi(v)));
+  if ((v = env("NAGP_FILTER_DBG"))) s.filter_dbg = atoi(v);
+  if ((v = env("NAGP_GAINM_DBG"))) s.gainm_dbg = atoi(v);
+  if ((v = env("NAGP_STAMP_WORKER"))) s.stamp_worker = atoi(v);
+  if ((v = env("NAGP_TEST_FAKE_DEVICES"))) s.test_fake_devices = std::max(0, atoi(v));
+  if ((v = env("NAGP_TEST_FAIL_DEVICE"))) s.test_fail_device = atoi(v);
+  if ((v = env("NAGP_TEST_SLOT_ENOMEM"))) s.test_slot_enomem = std::max(0, atoi(v));
+  return s;
 }
 
 #define HIP_TRY(expr)                                                                         \
@@ -74,6 +134,7 @@ struct nagp_plan {
   std::vector<int> perm;   // plans with split blocks: device state index -> the caller's state index (empty otherwise)
   int Mu = 0;              // ... and the caller's number of sites (sh.Ms)
   nagp_opts opts{};
+  DevSwitches dev{};       // developer switches, read once at plan creation
   std::vector<double> damping;
   int B = 0;
   int TPT = 1, TPT_f = 1, NT = 256, NT_f = 256, NT_ih = 256;
@@ -88,8 +149,6 @@ struct nagp_plan {
   int gain_mfma = 0;    // dense (G, Delta) output through rts_gain_mfma_kernel<Sp/16> (nagp_gain_mfma.hpp)
   int gain_inv = 0;     // ... in its explicit-inverse form G = A^-1 - (A^-1 Q) PSkp^-1 (every block of A comfortably invertible)
   double* d_ainv = nullptr;      // [B][M][32]: per block A^-1 and A^-1 Q (GainPar::ainv)
-  int lin_mfma = 0;     // fixed-site filter launches through gf_filter_lin_mfma_kernel<NTL> (nagp_filter_mfma.hpp); = NTL
-  size_t lds_lin = 0;
   size_t gbuf_doubles = 0;
   MfmaPar mpar{};
   size_t lds_mfma = 0;
@@ -228,9 +287,9 @@ static void dfree(nagp_plan* p, double* ptr) {
 // component range) blocks that holds the non-zeros of every problem of the plan; the tables of MomSrc (nagp_dev.hpp).
 // Returns false (unstructured) whenever anything does not fit the table formats.
 static bool build_mom_src(int B, const nagp_model* models, int D, int N, int n_pts, const std::vector<unsigned char>& code,
-                          MomSrc& sc, std::vector<unsigned char>& blob) {
+                          MomSrc& sc, std::vector<unsigned char>& blob, const DevSwitches& dev) {
   sc = MomSrc{};
-  if (N < 2 || D < 2 || n_pts > 65535 || dev_env("NAGP_NO_SRC")) return false;
+  if (N < 2 || D < 2 || n_pts > 65535 || dev.no_src) return false;
   std::vector<int> par(D + N);
   for (int i = 0; i < D + N; ++i) par[i] = i;
   auto find = [&](int x) { while (par[x] != x) { par[x] = par[par[x]]; x = par[x]; } return x; };

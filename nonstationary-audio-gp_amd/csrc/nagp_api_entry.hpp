@@ -1,5 +1,5 @@
 // nagp_api_entry.hpp -- part of the ONE translation unit nagp_api.hip (included there, in this order: nagp_api_plan.hpp, nagp_api_sweep.hpp,
-// nagp_api_entry.hpp; the plan struct, the error helpers and the developer-switch accessor live in nagp_api.hip itself).
+// nagp_api_entry.hpp; the plan struct, the error helpers and the developer switches live in nagp_api.hip itself).
 // The one-shot entry points (ep / ihgp / giekf run), mom on its own, iekf_update1, the stationary filterbank, nagp_batch_run (RCCL), reconstruction.
 
 // ---------------------------------------------------------------------------------------------
@@ -165,7 +165,7 @@ extern "C" int nagp_fastfb_run(int32_t S, const double* A, const double* AKHA, c
   // spans of the parallel-in-time form (needs two more S x S work matrices in LDS: S <= 64); short series run as one span
   const size_t lds_c = fb_compose_lds_doubles(S) * sizeof(double);
   int ns = 1;
-  if (lds_c <= 160 * 1024 && T >= 2048 && !dev_env("NAGP_FB_SEQUENTIAL")) ns = (int)std::min<int64_t>(512, T / 128);
+  if (lds_c <= 160 * 1024 && T >= 2048 && !read_dev_switches().fb_sequential) ns = (int)std::min<int64_t>(512, T / 128);
   const int64_t L = (T + ns - 1) / ns;
   ns = (int)((T + L - 1) / L);
   const size_t SS = (size_t)S * S, SP = (size_t)S + 4;
@@ -314,8 +314,10 @@ extern "C" int nagp_batch_run(int32_t n_problems, const nagp_model* models, cons
   // propagation run for n devices; device d's plan lives on physical device d mod (real devices) (every worker stops at its first device
   // call on a machine without one) and the nlZ sums are added on the host in device order instead of by RCCL (one card cannot hold two
   // ranks of a communicator).  NAGP_TEST_FAIL_DEVICE=d -- worker d reports NAGP_EHIP before it creates its plan.
-  const int fake = dev_env("NAGP_TEST_FAKE_DEVICES") ? std::max(0, atoi(dev_env("NAGP_TEST_FAKE_DEVICES"))) : 0;
-  const int fail_dev = dev_env("NAGP_TEST_FAIL_DEVICE") ? atoi(dev_env("NAGP_TEST_FAIL_DEVICE")) : -1;
+  // One snapshot of the developer switches for the whole run: the workers' plans are created from it as well.
+  const DevSwitches dev = read_dev_switches();
+  const int fake = dev.test_fake_devices;
+  const int fail_dev = dev.test_fail_device;
   ndev = fake ? fake : ndev_real;
   if (ndev < 1) FAIL(NAGP_ENODEVICE, "no HIP device visible");
   if (n_gpus > ndev) FAIL(NAGP_EINVAL, "n_gpus = %d but %d device(s) visible", n_gpus, ndev);
@@ -348,7 +350,7 @@ extern "C" int nagp_batch_run(int32_t n_problems, const nagp_model* models, cons
     nagp_plan* p = nullptr;
     int st = NAGP_OK;
     if (d == fail_dev) { g_last_error = "injected failure (NAGP_TEST_FAIL_DEVICE)"; st = NAGP_EHIP; }
-    if (st == NAGP_OK) st = nagp_plan_create(&p, (int32_t)idx.size(), ms.data(), tables ? ts.data() : nullptr, T, &o);
+    if (st == NAGP_OK) st = plan_create(&p, (int32_t)idx.size(), ms.data(), tables ? ts.data() : nullptr, T, &o, dev);
     if (st == NAGP_OK) st = nagp_plan_upload_y(p, yv.data());
     if (st == NAGP_OK) st = nagp_plan_execute(p);
     if (st == NAGP_OK) st = nagp_plan_download(p, os.data());
@@ -371,7 +373,7 @@ extern "C" int nagp_batch_run(int32_t n_problems, const nagp_model* models, cons
   std::vector<double> total(I, 0.0);
   if (fake && G > 1) {
     for (int d = 0; d < G; ++d) for (int i = 0; i < I; ++i) total[i] += part[d][i];
-  } else if (G > 1 || dev_env("NAGP_FORCE_RCCL")) {
+  } else if (G > 1 || dev.force_rccl) {
     const int st = allreduce_nlz(G, I, part, total);
     if (st != NAGP_OK) return st;
   } else {

@@ -1,5 +1,5 @@
 // nagp_api_plan.hpp -- part of the ONE translation unit nagp_api.hip (included there, in this order: nagp_api_plan.hpp, nagp_api_sweep.hpp,
-// nagp_api_entry.hpp; the plan struct, the error helpers and the developer-switch accessor live in nagp_api.hip itself).
+// nagp_api_entry.hpp; the plan struct, the error helpers and the developer switches live in nagp_api.hip itself).
 // Plan creation: shape checks, kernel / LDS / slot policy, model packing, cubature tables, device buffers; destroy, upload.
 
 // ---------------------------------------------------------------------------------------------
@@ -156,8 +156,8 @@ static bool msr_build_desc(int CD, int nd, int c0, int npt, const std::vector<un
 }
 
 // ---------------------------------------------------------------------------------------------
-extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* models, const nagp_ihgp_tables* tables,
-                                int64_t T, const nagp_opts* o) {
+static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, const nagp_ihgp_tables* tables,
+                       int64_t T, const nagp_opts* o, const DevSwitches& dev) {
   if (!out || !models || !o || B < 1 || T < 1) FAIL(NAGP_EINVAL, "null/empty argument");
   *out = nullptr;
   const nagp_model& m0 = models[0];
@@ -187,6 +187,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
 
   nagp_plan* p = new nagp_plan();
   p->opts = *o;
+  p->dev = dev;
   p->B = B;
   Shape& sh = p->sh;
   sh.S = m0.S; sh.M = m0.M; sh.D = m0.D; sh.N = (o->lik_kind == NAGP_LIK_POWER && !ekf) ? m0.D : m0.N;
@@ -301,7 +302,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     // ADF launches: <= 256 threads (512 registers per lane) whenever the tiles fit
     if (slots <= 1024 && sh.S <= 256) { p->TPT_a = slots <= 256 ? 1 : (slots <= 512 ? 2 : (slots <= 768 ? 3 : 4)); p->NT_a = 256; p->LB_a = 256; }
     else { p->TPT_a = 4; p->NT_a = std::max(roundup64((slots + 3) / 4), roundup64(sh.S)); p->LB_a = 512; }
-    p->wide_l = (!ekf && slots > 512 && slots <= 1024 && !dev_env("NAGP_NO_WIDE")) ? 1 : 0;
+    p->wide_l = (!ekf && slots > 512 && slots <= 1024 && !dev.no_wide) ? 1 : 0;
     p->NT_l = p->wide_l ? roundup64(slots) : p->NT_f;
     // fixed-site launches with one tile per thread: whole waves beyond the tile threads for the state lanes (gf_filter_kernel: soff)
     p->NT_fl = p->NT_f;
@@ -380,7 +381,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     mc.n_pts = o->n_pts; mc.cdim = o->cub_dim; mc.D = sh.D; mc.wn = p->d_wn;
     mc.jitter = (o->lik_kind == NAGP_LIK_POWER) ? 1e-8 : 1e-10;
     mc.DG = 1; mc.cache_tabs = 0; mc.store_a = 0; mc.stamps = nullptr;
-    if (o->lik_kind == NAGP_LIK_POWER_NMF && o->cub_dim <= MSP_MAXCD && !dev_env("NAGP_NO_SPARSE")) {
+    if (o->lik_kind == NAGP_LIK_POWER_NMF && o->cub_dim <= MSP_MAXCD && !dev.no_sparse) {
       // sparse-point form: needs the coordinate value 0 and <= MSP_NZ non-centre coordinates per sigma point
       int c0 = -1;
       for (size_t ci = 0; ci < xd.size(); ++ci) if (xd[ci] == 0.0) c0 = (int)ci;
@@ -414,7 +415,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
         }
       }
     }
-    if (o->lik_kind == NAGP_LIK_POWER_NMF_SQRT && o->cub_dim <= MSQ_MAXCD && sh.D <= MSQ_MAXD && !dev_env("NAGP_NO_SPARSE")) {
+    if (o->lik_kind == NAGP_LIK_POWER_NMF_SQRT && o->cub_dim <= MSQ_MAXCD && sh.D <= MSQ_MAXD && !dev.no_sparse) {
       // staged form of the square-root amplitudes: needs the coordinate value 0 (the marginal sums leave the centre to a difference),
       // the marginal lists of the packed form (<= 16 per marginal wave, <= 64 members each) and <= 320 sigma points
       int c0 = -1;
@@ -434,7 +435,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     if (o->lik_kind != NAGP_LIK_POWER) {
       std::vector<unsigned char> blob;
       MomSrc sc;
-      if (build_mom_src(B, models, sh.D, sh.N, o->n_pts, code, sc, blob)) {
+      if (build_mom_src(B, models, sh.D, sh.N, o->n_pts, code, sc, blob, dev)) {
         double* dsrc = nullptr;
         PLAN_TRY(dalloc(p, &dsrc, (blob.size() + 7) / 8, false));
         PLAN_HIP(hipMemcpyAsync(dsrc, blob.data(), blob.size(), hipMemcpyHostToDevice, p->stream));
@@ -468,7 +469,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
   // smoother chunk: the unit of the (G, Delta) buffers and of the filter -> smoother pipeline.  About a dozen chunks per sweep
   // (the tail the pipeline cannot hide is one chunk's gain + compose), at least 2048 steps each, at most what one buffer may take.
   {
-    const int64_t n_ch = dev_env("NAGP_CHUNKS") ? std::max(1, atoi(dev_env("NAGP_CHUNKS"))) : 12;     // developer switch
+    const int64_t n_ch = dev.chunks;     // developer switch NAGP_CHUNKS (default 12)
     p->chunk = (o->chunk > 0) ? o->chunk : (int)std::min<int64_t>(T, std::max<int64_t>(2048, (T + n_ch - 1) / n_ch));
   }
   if (p->chunk > T) p->chunk = (int)T;
@@ -480,18 +481,17 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
       // Sp >= 80 (five tile columns and more): the column-owner kernels of nagp_mfma_big.hpp -- one wave per tile column, the symmetric state
       // in LDS as its lower tiles, G streamed, two workgroups per CU at Sp = 80 / 96; below that the four-wave kernels with G and the state
       // side by side in LDS.  (Round 5: at Sp = 80 the column-owner passes take cfg2_batch from 508 to 444 ms, span passes 428 -> 235 ms, once
-      // their span count knows that a CU holds two of their workgroups; NAGP_BIG_MIN_SP=97 restores the round-4 split.)
-      const int big_min = dev_env("NAGP_BIG_MIN_SP") ? std::max(80, atoi(dev_env("NAGP_BIG_MIN_SP"))) : 80;
-      if (Sp < big_min && Sp <= 96 && !dev_env("NAGP_NO_MFMA")) p->mfma_sp = Sp;
+      // their span count knows that a CU holds two of their workgroups.)
+      if (Sp < 80 && !dev.no_mfma) p->mfma_sp = Sp;
       // Sp <= 160: state and G do not fit LDS side by side (or, from Sp = 80, are better off apart); column-owner kernels
       // (a sweep that stores the smoothed covariances runs the VALU passes instead: see run_smoother)
-      else if (Sp <= 160 && !dev_env("NAGP_NO_MFMA") && !dev_env("NAGP_NO_MFMA_BIG")) { p->mfma_sp = Sp; p->big_sp = 1; }
+      else if (Sp <= 160 && !dev.no_mfma && !dev.no_mfma_big) { p->mfma_sp = Sp; p->big_sp = 1; }
     }
     const size_t mat = p->mfma_sp ? (size_t)p->mfma_sp * p->mfma_sp : (size_t)nt * 16;     // (4M)^2 <= Sp^2: the tile-major form fits the dense slot
     // column-owner passes (96 < Sp <= 160) read the symmetric Delta through its lower 16x16 tiles only: the slots hold it packed
     // (Sp = 160: 315 KB per step instead of 410 -- eight chunks of the 8-segment cfg5 plan keep their slot where six did).  Not when a
     // sweep stores smoothed covariances (its VALU passes use the tile-major layout of the same slots) or with the opt-in MFMA gain kernel.
-    p->dpacked = (p->big_sp && !p->want_PS && !dev_env("NAGP_DENSE_DELTA")) ? 1 : 0;
+    p->dpacked = (p->big_sp && !p->want_PS && !dev.dense_delta) ? 1 : 0;
     p->gstep = p->mfma_sp ? gd_step_doubles(p->mfma_sp, p->dpacked) : 2 * mat;
     const double per_step = (double)B * ((double)p->gstep + sh.S) * 8.0;                   // one step of a (G, Delta, delta) chunk buffer
     {
@@ -530,7 +530,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     // Chunk-pipelined schedule: needs >= 2 chunks and >= 2 chunk buffers.  The compose results (Phi, C, c of every span) are kept
     // per chunk; the (G, Delta, delta) buffers are kept for as many chunks as the free memory holds, the rest recompute their
     // gains after the filter (slot 0 is the scratch).
-    p->pipeline = p->need_PF && p->nc >= 2 && !dev_env("NAGP_NO_PIPELINE");
+    p->pipeline = p->need_PF && p->nc >= 2 && !dev.no_pipeline;
     const int n_sets = p->pipeline ? p->nc : 1;
     for (int c = 0; c < n_sets; ++c) {
       double *a1 = nullptr, *a2 = nullptr, *a3 = nullptr, *a4 = nullptr, *a5 = nullptr;
@@ -560,13 +560,12 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
         const double avail = (double)free_b - 2.0 * 1073741824.0 - 0.03 * (double)total_b;     // head-room for the runtime, RCCL, other plans
         n_slots = (int)std::max(1.0, std::min((double)(p->nc - 1), std::floor((avail - slot_bytes / 8.0) / slot_bytes)));   // full chunks: nc - 1
       }
-      if (const char* e = dev_env("NAGP_PIPELINE_SLOTS")) n_slots = std::max(1, std::min(p->nc - 1, atoi(e)));   // developer switch (tests: partial retention)
+      if (dev.pipeline_slots) n_slots = std::max(1, std::min(p->nc - 1, dev.pipeline_slots));   // developer switch (tests: partial retention)
       if (n_slots < 2) { p->pipeline = false; n_slots = 1; }
     }
     p->mat_doubles = mat;
     auto add_slot = [&](int cap_steps) -> int {
-      if (const char* e = dev_env("NAGP_TEST_SLOT_ENOMEM"))          // test hook: the (n+1)-th slot allocation of a plan fails
-        if ((int)p->slotG.size() >= atoi(e)) return NAGP_ENOMEM;
+      if (dev.test_slot_enomem >= 0 && (int)p->slotG.size() >= dev.test_slot_enomem) return NAGP_ENOMEM;   // test hook: the (n+1)-th slot allocation of a plan fails
       double *g = nullptr, *d = nullptr;
       int st = dalloc(p, &g, (size_t)B * cap_steps * p->gstep, true);
       if (st == NAGP_OK) st = dalloc(p, &d, (size_t)B * cap_steps * sh.S, false);
@@ -607,7 +606,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     // per chunk, the chunks the filter finishes LAST take theirs from there -- recycled slot j (the chunk with n_slots + j full chunks
     // before it in time) occupies doubles [pf_step + j * chunk * gstep, pf_step + (j+1) * chunk * gstep) of every problem's PF; all of
     // it must lie below the first step of that chunk.  All-or-nothing: a chunk left without a slot would read PF again.
-    if (p->pipeline && p->dpacked && n_slots < p->nc - 1 && !dev_env("NAGP_NO_RECYCLE")) {
+    if (p->pipeline && p->dpacked && n_slots < p->nc - 1 && !dev.no_recycle) {
       std::vector<int64_t> k0s;      // first step of the chunks, latest first (the cuts of sweep_begin)
       for (int64_t k1 = T - 1; k1 > 0;) { const int nk = chunk_len(p, k1, k0s.empty()); k0s.push_back(k1 - nk); k1 -= nk; }
       const int ncs = (int)k0s.size(), need = (ncs - 1) - n_slots;
@@ -649,7 +648,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
       PLAN_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_tab), (size_t)(p->nc + 1) * sizeof(ChunkTab), hipHostMallocMapped | hipHostMallocCoherent));
       PLAN_HIP(hipEventCreateWithFlags(&p->ev_filter, hipEventDisableTiming));
       PLAN_HIP(hipEventCreateWithFlags(&p->ev_s2, hipEventDisableTiming));
-      if (p->opts.kind == NAGP_KIND_GF_EP && !dev_env("NAGP_NO_XSWEEP")) {
+      if (p->opts.kind == NAGP_KIND_GF_EP && !dev.no_xsweep) {
         for (int c = 0; c < p->nc + 1; ++c) { hipEvent_t e = nullptr; PLAN_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); p->ev_chunk.push_back(e); }
         PLAN_HIP(hipEventCreateWithFlags(&p->ev_red, hipEventDisableTiming));
         p->xsweep = true;
@@ -657,7 +656,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
       PLAN_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->h_progress), (size_t)B * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
       std::memset(p->h_progress, 0, (size_t)B * sizeof(unsigned long long));
     }
-    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] smoother: chunk %d, %d chunk(s) per sweep, %d (G,Delta) buffer(s) of %.2f GiB (+ %d recycled from PF), pipelined %d\n", p->chunk, p->nc, n_slots, per_step * p->chunk / 1073741824.0, p->n_recycled, (int)p->pipeline);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] smoother: chunk %d, %d chunk(s) per sweep, %d (G,Delta) buffer(s) of %.2f GiB (+ %d recycled from PF), pipelined %d\n", p->chunk, p->nc, n_slots, per_step * p->chunk / 1073741824.0, p->n_recycled, (int)p->pipeline);
   } else {
     PLAN_TRY(dalloc(p, &p->d_lZs, BT));
     PLAN_TRY(dalloc(p, &p->d_vprev, (size_t)B * sh.M));
@@ -723,12 +722,11 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     if (ihgp_filter_lds_doubles(sh, t, p->tb.NG, p->hph_lds, p->kb_ih) * sizeof(double) > 156 * 1024) t.cache_tabs = 0;
     p->cache_f = t.cache_tabs; p->sta_f = t.store_a;
     p->lds_ih = ihgp_filter_lds_doubles(sh, t, p->tb.NG, p->hph_lds, p->kb_ih) * sizeof(double);
-    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] ihgp filter: LDS %zu B, hph table in LDS %d, cubature tables in LDS %d, block-structured mom %d, mom LDS %zu B\n", p->lds_ih, p->hph_lds, p->cache_f, p->src_f, mom_lds_doubles(t) * sizeof(double));
+    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp filter: LDS %zu B, hph table in LDS %d, cubature tables in LDS %d, block-structured mom %d, mom LDS %zu B\n", p->lds_ih, p->hph_lds, p->cache_f, p->src_f, mom_lds_doubles(t) * sizeof(double));
     // the ADF sweep in the sparse-point form (ihgp_adf_kernel): plain NMF likelihood, <= 320 sigma points, unstructured Wnmf
     // (plans with a block of 5 .. 8 states, BS = 8: the general ADF kernel ihgp_filter_kernel<MV, false, 8>; the affine scans are instantiated for both strides)
     if (sh.BS == 4 && p->sp.enabled && !p->src_f && sh.M <= 64 && sh.D <= 4 * MSP_DT && o->n_pts <= MSP_NT + 64 && (o->n_pts + 3) / 4 <= MSP_NW * MSP_NST) {
       p->kb_sp = IH_KB; p->hph_sp = 1;
-      if (const char* e = dev_env("NAGP_IH_KB")) p->kb_sp = std::max(1, std::min(IH_KB, atoi(e)));   // developer switch: steps per I/O block
       auto need = [&]() { return ihgp_adf_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16; };
       if (need() > 156 * 1024) p->kb_sp = 8;
       if (need() > 156 * 1024) p->hph_sp = 0;
@@ -742,8 +740,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
         }
         // role-specialised waves: two serial + six worker waves, one sigma point per worker lane, the cubature sums from bin sums (msr_build_desc)
         const size_t need8 = ihgp_adf8_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16;
-        const char* er = dev_env("NAGP_IH_ROLES");
-        if (p->sp.bdesc && need8 <= 156 * 1024 && !(er && er[0] == '0')) {
+        if (p->sp.bdesc && need8 <= 156 * 1024 && dev.ih_roles) {
           p->sp_ih8 = 1; p->lds_sp8 = need8;
 #define SL8(V) PLAN_TRY(set_lds(ihgp_adf8_kernel<V>, need8))
           switch (o->cub_dim) { case 1: SL8(1); break; case 2: SL8(2); break; case 3: SL8(3); break; case 4: SL8(4); break; case 5: SL8(5); break; case 6: SL8(6); break; default: SL8(7); break; }
@@ -754,7 +751,6 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     // likModulatorPreCalcwn: the role-specialised sweep of nagp_momsq.hpp
     if (sh.BS == 4 && p->sq_ok && !p->src_f && sh.M <= 64) {
       p->kb_sq = IH_KB; p->hph_sq = 1;
-      if (const char* e = dev_env("NAGP_IH_KB")) p->kb_sq = std::max(1, std::min(IH_KB, atoi(e)));
       auto needq = [&]() { return ihgp_adf8sq_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sq, p->kb_sq) * sizeof(double) + 16; };
       if (needq() > 156 * 1024) p->kb_sq = 8;
       if (needq() > 156 * 1024) p->hph_sq = 0;
@@ -767,8 +763,8 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
         }
       }
     }
-    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);
-    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B)\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B)\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8);
 #define SL(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, false>, p->lds_ih))
 #define SLS(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, true>, p->lds_ih))
 #define SL8(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, false, 8>, p->lds_ih))
@@ -795,27 +791,25 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
     if (filter_lds_doubles(sh, t, ekf ? 1 : 0, p->kb_f) * sizeof(double) > cap) p->kb_f = 2;      // 59 .. 63 sites: the W panel alone is 110 - 127 KB
     if (filter_lds_doubles(sh, t, ekf ? 1 : 0, p->kb_f) * sizeof(double) > cap) p->kb_f = 1;
     if (filter_lds_doubles(sh, t, ekf ? 1 : 0, p->kb_f) * sizeof(double) > cap) t.chunk_cap = 256;   // ut7 / ut9 in nine dimensions at 57 sites: 256 points per pass
-    if (const char* e = dev_env("NAGP_MOM_CHUNK")) t.chunk_cap = std::max(64, atoi(e));      // developer switch
+    if (dev.mom_chunk) t.chunk_cap = dev.mom_chunk;      // developer switch
     p->chunk_cap_f = t.chunk_cap;
-    if (const char* e = dev_env("NAGP_KB_F")) p->kb_f = std::max(1, std::min(16, atoi(e)));      // developer switches: the fall-backs of LDS-tight shapes
-    if (dev_env("NAGP_NO_CACHE_TABS")) { t.cache_tabs = 0; t.store_a = 0; }
+    if (dev.kb_f) p->kb_f = dev.kb_f;      // developer switches: the fall-backs of LDS-tight shapes
+    if (dev.no_cache_tabs) { t.cache_tabs = 0; t.store_a = 0; }
     p->cache_f = t.cache_tabs; p->sta_f = t.store_a;
     p->lds_filter = (filter_lds_doubles(sh, t, ekf ? 1 : 0, p->kb_f) + filter_cpl_doubles(sh)) * sizeof(double);
     // pipelined plans: the filter's workgroup asks for the whole LDS of its CU, so that no workgroup of the smoother kernels running
     // beside it on the second stream is placed on the same CU (the filter is the critical path; its time is latency, not occupancy)
     if (p->pipeline && B <= 128 && p->lds_filter < 160 * 1024) p->lds_filter = 160 * 1024;     // (never BELOW what the kernel needs: set_lds refuses > 160 KiB)
-    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] gf filter: LDS %zu B, ring %d steps, cubature tables in LDS %d, mom LDS %zu B, sparse-point ADF %d\n", p->lds_filter, p->kb_f, p->cache_f, ekf ? (size_t)0 : mom_lds_doubles(t) * sizeof(double), p->sp_gf);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] gf filter: LDS %zu B, ring %d steps, cubature tables in LDS %d, mom LDS %zu B, sparse-point ADF %d\n", p->lds_filter, p->kb_f, p->cache_f, ekf ? (size_t)0 : mom_lds_doubles(t) * sizeof(double), p->sp_gf);
     // ADF sweep with role-specialised waves (nagp_gfadf8.hpp): 512 threads, <= 2 lower tiles per thread, the role layout's limits
     // (one sigma point per worker lane; the cubature sums from bin sums as in the IHGP sweep)
     if (p->sp_gf && sh.M * (sh.M + 1) / 2 <= 2 * MSR_NT && sh.S <= MSR_NT && p->sp.bdesc &&
-        !dev_env("NAGP_NO_GF_ROLES")) {
+        !dev.no_gf_roles) {
       // tiles per thread / who owns them: 1 or 2 on the six worker waves (<= 384 / 768 lower tiles), else 2 on all eight waves
       const int nlow8 = sh.M * (sh.M + 1) / 2, ntw = MSR_NT - 64 * MSR_W0;
       p->a8_tpt = (nlow8 <= ntw) ? 1 : 2; p->a8_st = (nlow8 <= 2 * ntw) ? 0 : 1;
-      if (dev_env("NAGP_A8_ST")) { p->a8_tpt = 2; p->a8_st = 1; }       // developer switch: tiles on all eight waves
       p->kb_a8 = 16;
       while (p->kb_a8 > 2 && gf_adf8_lds_doubles(sh, o->cub_dim, p->kb_a8) * sizeof(double) > cap) p->kb_a8 /= 2;
-      if (const char* e = dev_env("NAGP_KB_A8")) p->kb_a8 = std::max(2, std::min(16, atoi(e) & ~1));
       const size_t need = gf_adf8_lds_doubles(sh, o->cub_dim, p->kb_a8) * sizeof(double);
       if (need <= cap) {
         p->a8_gf = 1; p->lds_a8 = need;
@@ -828,7 +822,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
 #undef SA8
       }
     }
-    if (dev_env("NAGP_STAMPS")) fprintf(stderr, "[nagp plan] gf ADF sweep with role-specialised waves: %d (tiles per thread %d, ring %d steps, LDS %zu B)\n", p->a8_gf, p->a8_tpt, p->kb_a8, p->lds_a8);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] gf ADF sweep with role-specialised waves: %d (tiles per thread %d, ring %d steps, LDS %zu B)\n", p->a8_gf, p->a8_tpt, p->kb_a8, p->lds_a8);
     p->lds_gain = (((p->TPT == 1) ? gain_lds_doubles_staged(sh) : gain_lds_doubles(sh)) + gain_cpl_doubles(sh)) * sizeof(double);     // (rts_gain_kernel: STAGE)
     p->lds_scan = span_lds_doubles(sh, p->LP1, p->LP2) * sizeof(double);
     if (split) {
@@ -907,7 +901,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
 #undef SL4
 #undef SL5
     }
-    if (!split && nt > 1024 && nt <= 1536 && sh.M * (sh.M + 1) / 2 <= 768 && sh.S <= 768 && !dev_env("NAGP_NO_GAIN768")) {
+    if (!split && nt > 1024 && nt <= 1536 && sh.M * (sh.M + 1) / 2 <= 768 && sh.S <= 768 && !dev.no_gain768) {
       p->gain768 = 1;
       p->lds_gain = gain_lds_doubles_staged(sh) * sizeof(double);
       PLAN_TRY(set_lds(rts_gain_kernel<2, 768>, p->lds_gain));
@@ -920,21 +914,9 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
       default: PLAN_TRY(set_lds(rts_gain_kernel<8>, p->lds_gain)); PLAN_TRY(set_lds(rts_compose_kernel<8>, p->lds_scan)); PLAN_TRY(set_lds(rts_boundary_kernel<8>, p->lds_scan)); PLAN_TRY(set_lds(rts_apply_kernel<8>, p->lds_scan)); break;
     }
   }
-  if (!split && !ekf && o->kind == NAGP_KIND_GF_EP && o->mode == NAGP_MODE_PREDICT && !(o->flags & NAGP_FLAG_MIXTURE_RULE) && 4 * sh.M <= 160 && dev_env("NAGP_LIN_MFMA")) {
-    // fixed-site steps (sweeps >= 2) on the matrix cores: the plain predict-mode rule only.  Opt-in: measured on MI355X the step is
-    // 13.7 us against 10.4 us of the 4x4-tile VALU kernel at S = 146 (6.2 against 3.85 at S = 73) -- DESIGN section 8
-    const int ntl = (4 * sh.M + 15) / 16;
-    p->lin_mfma = ntl;
-    p->lds_lin = flm_lds_doubles(sh, ntl, 16) * sizeof(double);
-    if (p->pipeline && B <= 128 && p->lds_lin < 160 * 1024) p->lds_lin = 160 * 1024;      // (the CU to itself, as for the other filter launches)
-#define SETF(N, W) PLAN_TRY(set_lds((gf_filter_lin_mfma_kernel<N, W>), p->lds_lin))
-    switch (ntl) { case 1: SETF(1, 4); break; case 2: SETF(2, 4); break; case 3: SETF(3, 4); break; case 4: SETF(4, 4); break; case 5: SETF(5, 4); break;
-                   case 6: SETF(6, 8); break; case 7: SETF(7, 8); break; case 8: SETF(8, 8); break; case 9: SETF(9, 8); break; default: SETF(10, 8); break; }
-#undef SETF
-  }
   // rts_gain_mfma_kernel (16x16 tiles on the matrix cores, the dependence chain of the blocked Cholesky on a wave of its own) serves every
   // plan whose smoother passes take dense (G, Delta); NAGP_NO_GAIN_MFMA=1 (developer switch) keeps the 4x4-tile VALU kernel
-  if (p->mfma_sp && !split && !dev_env("NAGP_NO_GAIN_MFMA")) {      // (split blocks: the VALU kernel knows the cross tiles of A)
+  if (p->mfma_sp && !split && !dev.no_gain_mfma) {      // (split blocks: the VALU kernel knows the cross tiles of A)
     p->gain_mfma = 1;
     const size_t lg = gainm_lds_doubles(p->mfma_sp / 16, sh) * sizeof(double);
     // The explicit-inverse form needs A^-1 per block.  It is used when EVERY block of every problem of the plan is comfortably
@@ -974,9 +956,8 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
             worst = std::max(worst, rs);
           }
         }
-      const char* form = dev_env("NAGP_GAIN_FORM");
-      p->gain_inv = (!singular && std::isfinite(worst) && (worst <= 8.0 || (form && !strcmp(form, "inv")))) ? 1 : 0;
-      if (form && !strcmp(form, "solve")) p->gain_inv = 0;
+      p->gain_inv = (!singular && std::isfinite(worst) && (worst <= 8.0 || dev.gain_form == 2)) ? 1 : 0;
+      if (dev.gain_form == 1) p->gain_inv = 0;
       if (p->gain_inv) {
         PLAN_TRY(dalloc(p, &p->d_ainv, ha.size(), false));
         PLAN_HIP(hipMemcpyAsync(p->d_ainv, ha.data(), ha.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
@@ -1014,7 +995,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
 #undef SL
     // site refresh in the staged sparse-point form (the conditions of the ADF launches: likModulatorNMFPower on a fully symmetric rule)
     if (!split && p->sp.enabled && !p->src_ep && sh.M <= 64 && sh.D <= 4 * MSP_DT && o->cub_dim <= MSP_MAXCD && o->n_pts <= MSP_NT + 64 &&
-        (o->n_pts + 3) / 4 <= MSP_NW * MSP_NST && !dev_env("NAGP_NO_SPARSE_EP")) {
+        (o->n_pts + 3) / 4 <= MSP_NW * MSP_NST && !dev.no_sparse_ep) {
       p->sp_ep = 1;
       p->lds_ep_sp = ep_sp_lds_doubles(sh, o->cub_dim) * sizeof(double);
 #define SLS(V) PLAN_TRY(set_lds(ep_site_sp_kernel<V>, p->lds_ep_sp))
@@ -1022,7 +1003,7 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
 #undef SLS
     }
     // ... and with likModulatorPreCalcwn in the staged form of nagp_momsq.hpp
-    if (!split && p->sq_ok && !p->src_ep && sh.M <= 64 && !dev_env("NAGP_NO_SPARSE_EP")) {
+    if (!split && p->sq_ok && !p->src_ep && sh.M <= 64 && !dev.no_sparse_ep) {
       p->sq_ep = 1;
       p->lds_ep_sq = ep_sq_lds_doubles(sh, o->cub_dim) * sizeof(double);
 #define SLQ(V) PLAN_TRY(set_lds(ep_site_sq_kernel<V>, p->lds_ep_sq))
@@ -1036,6 +1017,11 @@ extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* mo
   PLAN_HIP(hipStreamSynchronize(p->stream));
   *out = p;
   return NAGP_OK;
+}
+
+extern "C" int nagp_plan_create(nagp_plan** out, int32_t B, const nagp_model* models, const nagp_ihgp_tables* tables,
+                                int64_t T, const nagp_opts* o) {
+  return plan_create(out, B, models, tables, T, o, read_dev_switches());
 }
 
 extern "C" void nagp_plan_destroy(nagp_plan* p) {

@@ -1,5 +1,5 @@
 // nagp_api_sweep.hpp -- part of the ONE translation unit nagp_api.hip (included there, in this order: nagp_api_plan.hpp, nagp_api_sweep.hpp,
-// nagp_api_entry.hpp; the plan struct, the error helpers and the developer-switch accessor live in nagp_api.hip itself).
+// nagp_api_entry.hpp; the plan struct, the error helpers and the developer switches live in nagp_api.hip itself).
 // The sweep scheduler: filter launches, the chunk-pipelined smoother (gain, compose, boundary, apply), site refresh, the three execute loops, download.
 
 // ---------------------------------------------------------------------------------------------
@@ -7,12 +7,12 @@ static int launch_filter(nagp_plan* p, const FilterPar& fp_in) {
   FilterPar fp = fp_in;
   fp.kb = p->kb_f;
   if (p->pipeline && fp.store_PF) { fp.progress = p->h_progress; fp.progress_every = 256; }
-  if (const char* e = dev_env("NAGP_FILTER_DBG")) fp.dbg = atoi(e);   // developer switch: see FilterPar::dbg
+  fp.dbg = p->dev.filter_dbg;   // developer switch: see FilterPar::dbg
   const bool ekf = p->opts.kind == NAGP_KIND_GIEKF;
   MomCfg mc = p->mc; mc.DG = p->DG_f; mc.cache_tabs = p->cache_f; mc.store_a = p->sta_f; mc.chunk_cap = p->chunk_cap_f;
   mc.sp = p->sp_gf ? p->sp : MomSp{};
   if (p->sq_gf) { mc.sq_form = 1; mc.sp.c0 = p->sq_c0; mc.store_a = 0; }
-  if (dev_env("NAGP_STAMPS")) mc.stamps = reinterpret_cast<unsigned long long*>(p->d_stamps);   // developer diagnostics
+  if (p->dev.stamps) mc.stamps = reinterpret_cast<unsigned long long*>(p->d_stamps);   // developer diagnostics
   const bool adf = ekf || fp.mom_all || fp.k_end == p->sh.T;   // launches that may call mom (or the EKF filter)
   int nt_ekf = p->NT_f;
   if (ekf && p->NT_f + 64 <= 512 && p->sh.N <= 64) { nt_ekf = p->NT_f + 64; fp.spl_wave = 1; }   // one extra wave for the link
@@ -81,12 +81,6 @@ static int launch_filter(nagp_plan* p, const FilterPar& fp_in) {
 #undef LF3
 #undef LF4
 #undef LF5
-    } else if (p->lin_mfma && !fp.legacy_update && !fp.clamp_always && !fp.R_raw) {
-      FilterPar fl = fp; fl.kb = 16;
-#define LFM(N, W) hipLaunchKernelGGL((gf_filter_lin_mfma_kernel<N, W>), g, dim3(64 * W), p->lds_lin, p->stream, p->sh, p->b, fl)
-      switch (p->lin_mfma) { case 1: LFM(1, 4); break; case 2: LFM(2, 4); break; case 3: LFM(3, 4); break; case 4: LFM(4, 4); break; case 5: LFM(5, 4); break;
-                             case 6: LFM(6, 8); break; case 7: LFM(7, 8); break; case 8: LFM(8, 8); break; case 9: LFM(9, 8); break; default: LFM(10, 8); break; }
-#undef LFM
     } else if (p->wide_l) {
       if (p->NT_l <= 768) hipLaunchKernelGGL((gf_filter_kernel<1, 0, -1, 768>), g, dim3(p->NT_l), p->lds_filter, p->stream, p->sh, p->b, mc, fp);
       else hipLaunchKernelGGL((gf_filter_kernel<1, 0, -1, 1024>), g, dim3(p->NT_l), p->lds_filter, p->stream, p->sh, p->b, mc, fp);
@@ -162,8 +156,7 @@ static void sweep_begin(nagp_plan* p, SweepCtx& sc, bool write_PSs) {
       const int per_cu = std::max(1, (int)((160 * 1024) / std::max<size_t>(p->lds_mfma, 1)));      // workgroups of the column-owner passes a CU holds (LDS)
       // resident workgroups a launch can count on: the CUs the filter's workgroups do not hold (one workgroup per CU), or -- where two fit a CU --
       // two on every CU (measured at 128 segments: 243 -> 180 ms against 225 with 384; the filter launches are short beside the passes there)
-      int n_cu = (per_cu >= 2) ? 256 * per_cu : std::max(32, 256 - p->B);
-      if (dev_env("NAGP_BIG_NCU")) n_cu = std::max(1, atoi(dev_env("NAGP_BIG_NCU")));      // developer switch
+      const int n_cu = (per_cu >= 2) ? 256 * per_cu : std::max(32, 256 - p->B);
       double best = 1e300; ns = 1;
       for (int c = 1; c <= std::max(1, std::min(p->ns_max, (nk + 7) / 8)); ++c) {
         const int L = (nk + c - 1) / c, cc = (nk + L - 1) / L;
@@ -202,48 +195,12 @@ static void sweep_begin(nagp_plan* p, SweepCtx& sc, bool write_PSs) {
   sc.s2_used = false;
 }
 
-// Ownership map of rts_gain_kernel<2, 768> (GainPar::gmapB / gmapL): the B groups (64 column-major tiles each) are paired early with
-// late -- group g with group nB-1-g -- so that every wave's two slots together take part in about M trailing updates of the
-// factorisation AND about M of the backward solve; the lower-triangle groups (their cost grows with the column) go heaviest first to the
-// wave with the lightest load of its SIMD (waves w, w+4, w+8 share one).
-static void gain_map(const Shape& sh, GainPar& gp) {
-  const int M = sh.M, nB = (sh.ntiles + 63) / 64, nlow = M * (M + 1) / 2, nL = (nlow + 63) / 64;
-  gp.use_map = 0;
-  if (nB > 24 || nL > 12 || !dev_env("NAGP_GAIN_MAP")) return;      // opt-in: measured without effect (profiles/r04_gain_phases.txt)
-  for (int w = 0; w < 12; ++w) { gp.gmapB[0][w] = gp.gmapB[1][w] = gp.gmapL[w] = -1; }
-  double load[12];
-  auto colB = [&](int g) { return ((double)g * 64 + 32) / M; };                 // column of the middle tile of a B group
-  auto colL = [&](int g) {                                                        // ... of a lower-triangle group
-    const int t = std::min(g * 64 + 32, nlow - 1);
-    int J = 0;
-    while (J + 1 < M && (J + 1) * M - (J + 1) * J / 2 <= t) ++J;
-    return (double)J;
-  };
-  int lo = 0, hi = nB - 1, w = 0;
-  for (; lo < hi && w < 12; ++lo, --hi, ++w) { gp.gmapB[0][w] = (signed char)lo; gp.gmapB[1][w] = (signed char)hi; load[w] = colB(lo) + colB(hi); }
-  if (lo == hi && w < 12) { gp.gmapB[0][w] = (signed char)lo; load[w] = colB(lo); ++w; }
-  for (; w < 12; ++w) load[w] = 0.0;
-  for (int g = nL - 1; g >= 0; --g) {                                             // heaviest lower group first
-    int best = -1; double bl = 0.0;
-    for (int v = 0; v < 12; ++v) {
-      if (gp.gmapL[v] >= 0) continue;
-      const double simd = load[v] + load[(v + 4) % 12] + load[(v + 8) % 12];    // the SIMD's load decides, the wave's own breaks ties
-      const double key = simd * 16.0 + load[v];
-      if (best < 0 || key < bl) { best = v; bl = key; }
-    }
-    gp.gmapL[best] = (signed char)g; load[best] += colL(g);
-  }
-  gp.use_map = 1;
-}
-
 static int launch_gain_chunk(nagp_plan* p, const SweepCtx& sc, int c, int slot, hipStream_t st) {
   const Shape& sh = p->sh; const ChunkGeom& g = sc.ch[c];
   GainPar gp{};
   gp.k0 = g.k0; gp.nk = g.nk; gp.chunk = p->slot_cap[slot]; gp.dense_sp = (sc.mode != SM_VALU) ? p->mfma_sp : 0;
-  gp.dbg = dev_env("NAGP_GAINM_DBG") ? atoi(dev_env("NAGP_GAINM_DBG")) : 0;
-  if (dev_env("NAGP_STAMPS") && p->d_gstamps) gp.stamps = reinterpret_cast<unsigned long long*>(p->d_gstamps);
-  gp.use_map = 0;
-  if (p->gain768) gain_map(sh, gp);
+  gp.dbg = p->dev.gainm_dbg;
+  if (p->dev.stamps && p->d_gstamps) gp.stamps = reinterpret_cast<unsigned long long*>(p->d_gstamps);
   gp.dpacked = (sc.mode == SM_BIG) ? p->dpacked : 0;
   if (gp.dense_sp && p->slot_tiled[slot]) {
     HIP_TRY(hipMemsetAsync(p->slotG[slot], 0, (size_t)p->B * p->slot_cap[slot] * p->gstep * sizeof(double), st)); p->slot_tiled[slot] = 0;
@@ -784,7 +741,7 @@ static int exec_ihgp(nagp_plan* p) {
   }
   MomCfg mcf = p->mc; mcf.DG = p->DG_f; mcf.cache_tabs = p->cache_f; mcf.store_a = p->sta_f;
   if (p->src_f) mcf.src = p->src_all;
-  if (dev_env("NAGP_STAMPS")) mcf.stamps = reinterpret_cast<unsigned long long*>(p->d_stamps);   // developer diagnostics
+  if (p->dev.stamps) mcf.stamps = reinterpret_cast<unsigned long long*>(p->d_stamps);   // developer diagnostics
   auto affine = [&](int mode, int64_t kend, int itt) -> int {
     if (kend <= 0) return NAGP_OK;
     AffPar ap{};
@@ -805,11 +762,11 @@ static int exec_ihgp(nagp_plan* p) {
     // forward: sweep 1 is the sequential ADF filter; later sweeps have fixed sites for k < T-1 (an affine
     // recursion, run parallel in time) and one ADF step at k = T-1
     const bool seq8 = sh.BS == 8;     // blocks of 5 .. 8 states: the general ADF kernel at block stride 8
-    const bool seq = dev_env("NAGP_IH_SEQ") && !p->sq_ih && !p->sp_ih && !p->src_f;      // developer switch: the sequential kernels (general ADF filter, ihgp_scan_kernel) for every sweep instead of the affine scans
+    const bool seq = p->dev.ih_seq && !p->sq_ih && !p->sp_ih && !p->src_f;      // developer switch: the sequential kernels (general ADF filter, ihgp_scan_kernel) for every sweep instead of the affine scans
     if (itt > 1 && !seq) RUN(affine(0, sh.T - 1, itt));
     IhgpPar ip{itt, p->damping[itt - 1], itt == 1 ? 1 : 0, (itt == 1 || seq) ? (int64_t)0 : (int64_t)(sh.T - 1)};
     ip.hph_lds = p->hph_lds; ip.kb = p->kb_ih;
-    if (const char* e = dev_env("NAGP_STAMP_WORKER")) ip.dbg_wave = atoi(e);
+    ip.dbg_wave = p->dev.stamp_worker;
     ip.w_old = 1.0 - ip.ep_damp; ip.w_new = mix ? ip.ep_damp / o.ep_fraction : ip.ep_damp; ip.mom_alpha = mix ? o.ep_fraction : 1.0;
     {
       Timed t(p, itt == 1 ? NAGP_K_FILTER : NAGP_K_FILTER_LIN);
@@ -905,7 +862,7 @@ extern "C" int nagp_plan_execute(nagp_plan* p) {
   }
   HIP_TRY(hipEventRecord(p->ev_t1, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
-  if (dev_env("NAGP_STAMPS") && p->d_gstamps && p->opts.kind != NAGP_KIND_IHGP) {
+  if (p->dev.stamps && p->d_gstamps && p->opts.kind != NAGP_KIND_IHGP) {
     unsigned long long g[32];
     if (hipMemcpy(g, p->d_gstamps, sizeof g, hipMemcpyDeviceToHost) == hipSuccess && p->gain_mfma && g[12]) {
       static const char* nm[12] = {"staging", "prologue barriers", "B' | delta_k", "PSkp", "Delta | tile 0", "trailing | 4 products", "factor+invert", "forward row", "interval barrier", "retry check", "backward", "G store"};
@@ -919,7 +876,7 @@ extern "C" int nagp_plan_execute(nagp_plan* p) {
       fprintf(stderr, "[nagp stamps] rts_gain_kernel, cycles per workgroup (thread 0 of %llu sampled): prologue %llu | diagonal tiles %llu | column solves %llu | trailing updates %llu | backward solve %llu | G store %llu\n",
               g[6], g[0] / g[6], g[1] / g[6], g[2] / g[6], g[3] / g[6], g[4] / g[6], g[5] / g[6]);
   }
-  if (dev_env("NAGP_STAMPS") && p->d_stamps) {
+  if (p->dev.stamps && p->d_stamps) {
     unsigned long long st[24];
     if (hipMemcpy(st, p->d_stamps, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
       if (p->opts.kind == NAGP_KIND_IHGP)

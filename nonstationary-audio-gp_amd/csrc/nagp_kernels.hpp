@@ -920,13 +920,6 @@ struct GainPar {
   int dbg;      // developer switch of rts_gain_mfma_kernel (NAGP_GAINM_DBG): skip phases to time the others (results are garbage)
   int dpacked;  // dense_sp > 0: Delta is stored as its lower-triangular 16x16 tiles, tile (TI,TJ), TI >= TJ, at [TI(TI+1)/2+TJ][16][16]
                 // (all the column-owner smoother passes read of it): a step of the slot is Sp^2 + NTL(NTL+1)/2*256 doubles instead of 2 Sp^2
-  // Ownership map of the 768-thread instantiation: slot q of wave w holds the 64 consecutive (column-major) tiles of group gmapB[q][w]
-  // (B = PS A', two slots) / gmapL[w] (lower triangle of PSkp); -1 = none; use_map = 0: group = w + 12 q (tile = tid + q * 768).
-  // A tile of column J takes part in J trailing updates of the factorisation and in M - J of the backward solve: with the groups in
-  // column order the last waves work through every column (94 slot-columns on the last wave against 22 on the first); the host can pair
-  // early with late groups (nagp_api.hip: gain_map, NAGP_GAIN_MAP=1).  Measured WITHOUT effect -- the trailing phase is bound by the LDS
-  // operand reads and the SIMDs' FP64 issue of ALL active tiles, not by the slowest wave (profiles/r04_gain_phases.txt): opt-in.
-  signed char gmapB[2][12], gmapL[12]; int use_map;
   int cpl_doubles;              // split blocks (Shape::part): doubles of the extra LDS region in front of everything else (gain_cpl_doubles)
   const double* ainv;           // rts_gain_mfma_kernel<.., true>: [B][M][32] per block A^-1 (16) and A^-1 Q (16), zero padded (host: gain_inverse_blocks)
   unsigned long long* stamps;   // developer diagnostics (NAGP_STAMPS): cycles of thread 0 of every 64th workgroup per phase of rts_gain_kernel:
@@ -1056,11 +1049,9 @@ __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(LB > 51
   // columns behind it (the trailing updates) -- consecutive threads, so whole waves skip a phase they have no tile in.  With the
   // row-major order of the span kernels every wave executed every phase for one or two active lanes.
   TileOwner<TPT> own;
-  const bool mapped = (LB > 512) && gp.use_map != 0;      // (the 768-thread instantiation only)
 #pragma unroll
   for (int q = 0; q < TPT; ++q) {
-    int t = tid + q * NT;
-    if (mapped) { const int g = (q < 2) ? gp.gmapB[q < 2 ? q : 0][tid >> 6] : -1; t = (g >= 0) ? g * 64 + (tid & 63) : sh.ntiles; }
+    const int t = tid + q * NT;
     own.ok[q] = t < sh.ntiles;
     const int tt_ = own.ok[q] ? t : 0;
     own.J[q] = tt_ / M; own.I[q] = tt_ - own.J[q] * M;
@@ -1071,8 +1062,7 @@ __global__ void __launch_bounds__(LB) __attribute__((amdgpu_waves_per_eu(LB > 51
     if constexpr (SPLIT) {
       // lower triangle, column by column: column J holds rows J .. M-1 and starts at J*M - J(J-1)/2
       const int nlow = M * (M + 1) / 2;
-      int t = tid + q * NT;
-      if (mapped) { const int g = (q == 0) ? gp.gmapL[tid >> 6] : -1; t = (g >= 0) ? g * 64 + (tid & 63) : nlow; }
+      const int t = tid + q * NT;
       low.ok[q] = t < nlow;
       const int tt_ = low.ok[q] ? t : 0;
       int J = 0;

@@ -469,8 +469,8 @@ def test_ekf_with_two_tiles_per_thread_S146():
 def test_ihgp_adf_sites_of_underflow_size():
     """Draw 8 of seed 99 of tools/gpu_fuzz.py (7 channels / 6 components, p = 7): from step 27 on the likelihood underflows, the sites
     are denormal (ttau ~ 6e-310), R = 1/ttau overflows to inf while ys = tnu/ttau stays finite.  The reciprocal-based tail of the
-    staged IHGP ADF kernels multiplied a denormal by inf there (NaN); the reference's own divisions give gain 0.  All three kernel
-    forms against the oracle."""
+    staged IHGP ADF kernels multiplied a denormal by inf there (NaN); the reference's own divisions give gain 0.  Both kernel
+    forms (role-specialised waves, and the four-wave kernel of NAGP_IH_ROLES=0) against the oracle."""
     fz = _fuzz_module()
     rng = np.random.default_rng(99)
     for _ in range(9):
@@ -479,9 +479,8 @@ def test_ihgp_adf_sites_of_underflow_size():
     t = np.arange(1, T + 1.0); mom, omom = fz.moms(c)
     o = oih.ihgp_ep_modulator_nmf(pr['w'], t, pr['y'], None, omom, t, k1, k2, 1, D, N, alpha, damp[:1], 1)
     assert np.nanmin(np.abs(o[5]['ttau'][o[5]['ttau'] != 0])) < 1e-300          # the case is what it claims to be
-    for env in ({}, {'NAGP_IH_PACK': '0'}, {'NAGP_IH_ROLES': '0'}):
-        for k_ in ('NAGP_IH_PACK', 'NAGP_IH_ROLES'):
-            os.environ.pop(k_, None)
+    for env in ({}, {'NAGP_IH_ROLES': '0'}):
+        os.environ.pop('NAGP_IH_ROLES', None)
         os.environ.update(env)
         try:
             r = nagp.ihgp_ep_modulator_nmf(pr['w'], t, pr['y'], SSHandle(), mom, t, k1, k2, 1, D, N, alpha, damp[:1], 1, nargout=6)
@@ -1082,23 +1081,20 @@ def test_sparse_point_cubature_equals_the_generic_form_and_the_oracle(fn, shape,
     f = nagp.ihgp_ep_modulator_nmf if fn == 'ihgp' else nagp.gf_ep_modulator_nmf
     of = oih.ihgp_ep_modulator_nmf if fn == 'ihgp' else ogf.gf_ep_modulator_nmf
     res = {}
-    modes = ('generic', 'sparse', 'sparse16', 'sparse4') if fn == 'ihgp' else ('generic', 'sparse')
-    # sparse: IHGP runs the role-specialised 512-thread kernel, eight points per MFMA step where the rule allows it;
-    # sparse16: the same with four points per step (NAGP_IH_PACK=0); sparse4: the four-wave kernel (NAGP_IH_ROLES=0)
+    modes = ('generic', 'sparse', 'sparse4') if fn == 'ihgp' else ('generic', 'sparse')
+    # sparse: IHGP runs the role-specialised 512-thread kernel; sparse4: the four-wave kernel (NAGP_IH_ROLES=0)
     for mode in modes:
-        for k_ in ('NAGP_NO_SPARSE', 'NAGP_IH_ROLES', 'NAGP_IH_PACK'):
+        for k_ in ('NAGP_NO_SPARSE', 'NAGP_IH_ROLES'):
             monkeypatch.delenv(k_, raising=False)
         if mode == 'generic': monkeypatch.setenv('NAGP_NO_SPARSE', '1')
         if mode == 'sparse4': monkeypatch.setenv('NAGP_IH_ROLES', '0')
-        if mode == 'sparse16': monkeypatch.setenv('NAGP_IH_PACK', '0')
         res[mode] = f(pr['w'], t, y, SSHandle(), mom, t, 'matern32', 'matern52', 1, D, N, 0.5, d, 1, nargout=6)
-    for k_ in ('NAGP_NO_SPARSE', 'NAGP_IH_ROLES', 'NAGP_IH_PACK'):
+    for k_ in ('NAGP_NO_SPARSE', 'NAGP_IH_ROLES'):
         monkeypatch.delenv(k_, raising=False)
     ref = of(pr['w'], t, y, None, olik.Mom(olik.LIK_POWER_NMF, p=p), t, 'matern32', 'matern52', 1, D, N, 0.5, d, 1)
     if fn == 'ihgp':
-        for other in ('sparse4', 'sparse16'):
-            a, b = res[other], res['sparse']
-            assert rel(a[0], b[0]) < 1e-10 and rel(a[5]['ttau'], b[5]['ttau']) < 1e-9 and relz(a[5]['nlZ'], b[5]['nlZ']) < 1e-12, other
+        a, b = res['sparse4'], res['sparse']
+        assert rel(a[0], b[0]) < 1e-10 and rel(a[5]['ttau'], b[5]['ttau']) < 1e-9 and relz(a[5]['nlZ'], b[5]['nlZ']) < 1e-12, 'sparse4'
     for mode in modes:
         Eft, Varft, out = res[mode][0], res[mode][1], res[mode][5]
         assert rel(Eft, ref[0]) < TOL_MEAN and relz(out['nlZ'], ref[5]['nlZ']) < TOL_LOGZ, mode
@@ -1874,35 +1870,6 @@ def test_gain_kernel_keeps_the_solve_form_when_a_block_of_A_is_badly_conditioned
     with np.errstate(all='ignore'):      # (here A_b ~ 1e-36: A_b^-1 overflows the products and the forced inverse form returns NaN)
         bad = np.max(np.abs(out['inv'].Eft - o[0])) / np.max(np.abs(o[0]))
     assert not (bad < TOL_MEAN)
-
-
-@pytest.mark.parametrize('D,N,k1', [(3, 2, 'matern32'), (16, 3, 'matern32'), (22, 4, 'exp'), (32, 6, 'matern32')])
-def test_mfma_fixed_site_filter_equals_the_valu_filter(D, N, k1):
-    """gf_filter_lin_mfma_kernel (covariance in the MFMA accumulator layout, rank-M update on the matrix cores; opt-in:
-    NAGP_LIN_MFMA=1) against the default 4x4-tile kernel: the sweeps >= 2 of the same plans -- 5, 19, 26, 38 sites (1, 4, 8 waves'
-    worth of tiles; 2-state sub-band blocks in the third case), missing observations, a continuation chunk -- to rounding."""
-    T = 70
-    probs, ys = [], []
-    for q in range(2):
-        pr = harness.nmf_problem(D, N, T, 8800 + q, 'constraints')
-        blk = pss.balance_blocks(pss.ss_blocks_nmf(pr['param1'], pr['param2'], k1, 'matern52'))
-        y = pr['y'].copy(); y[13 + q] = np.nan; y[T - 2] = np.nan
-        probs.append((blk, pr['W'], np.log(pr['w_lik']))); ys.append(y)
-    mom = Mom('likModulatorNMFPower', p_cubature=3); d = np.array([0.6, 0.5, 0.5])
-    res = {}
-    for mode in ('mfma', 'valu'):
-        if mode == 'mfma': os.environ['NAGP_LIN_MFMA'] = '1'
-        try:
-            plan = Plan(L.KIND_GF_EP, probs, T, mom=mom, ep_fraction=0.5, ep_damping=d, ep_itts=3, chunk=24)
-            plan.upload(ys); plan.execute(); res[mode] = plan.download(want_MF=True); tm = plan.timings(); plan.close()
-            assert tm['launches']['filter_lin'] >= 2                      # sweeps 2 and 3 ran the fixed-site kernel (one launch per sweep, or per chunk behind the previous sweep's smoother)
-        finally:
-            os.environ.pop('NAGP_LIN_MFMA', None)
-    for q in range(2):
-        a, v = res['mfma'][q], res['valu'][q]
-        for f, tol in (('Eft', 1e-9), ('Varft', 1e-9), ('MS', 1e-9), ('MF', 1e-9), ('lZ', 1e-9), ('ttau', 1e-7), ('tnu', 1e-7)):
-            assert rel(getattr(a, f), getattr(v, f)) < tol, (q, f)
-        assert relz(a.nlZ, v.nlZ) < 1e-10 and np.array_equal(a.counters, v.counters)
 
 
 def test_plan_that_cannot_fit_returns_enomem_and_the_device_stays_usable():

@@ -231,6 +231,38 @@ except nagp.NagpError as e:
     assert 'device 0: ' in outs['1'] and 'developer switch NAGP_TEST_FAKE_DEVICES=4 is active' in outs['1'], outs['1']
 
 
+def test_developer_switches_set_by_tests_and_tools_exist_and_are_read_in_one_place():
+    """(a) Every NAGP_* variable that a test or a tool sets (quoted, or assigned as NAME=) is read somewhere: as a string literal of
+    csrc/ or by the Python side (nagp/*.py, bench.py) -- a removed switch left behind in a test runs the default path twice.
+    (b) getenv occurs in csrc/ only inside read_dev_switches (nagp_api.hip): the switches are one snapshot per plan / call."""
+    pkg = os.path.join(ROOT, 'nonstationary-audio-gp_amd')
+    csrc = os.path.join(pkg, 'csrc')
+    def text(path):
+        with open(path, errors='replace') as f:
+            return f.read()
+    users = [os.path.join(ROOT, 'tests', f) for f in os.listdir(os.path.join(ROOT, 'tests')) if f.endswith('.py')]
+    users += [os.path.join(ROOT, 'tools', f) for f in os.listdir(os.path.join(ROOT, 'tools')) if os.path.isfile(os.path.join(ROOT, 'tools', f))]
+    abi = re.compile(r'NAGP_(FLAG|KIND|MODE|LIK)_\w+$|NAGP_(OK|E[A-Z]+)$')      # constants of include/nagp.h, not switches
+    set_by = {}
+    for path in users:
+        for name in re.findall(r"""['"](NAGP_[A-Z0-9_]+)['"]|\b(NAGP_[A-Z0-9_]+)=""", text(path)):
+            name = name[0] or name[1]
+            if not abi.match(name):
+                set_by.setdefault(name, os.path.relpath(path, ROOT))
+    assert 'NAGP_DEVELOPER' in set_by and 'NAGP_NO_SPARSE' in set_by      # the scan sees what it should
+    c_src = ''.join(text(os.path.join(csrc, f)) for f in sorted(os.listdir(csrc)))
+    py_src = ''.join(text(os.path.join(pkg, 'nagp', f)) for f in sorted(os.listdir(os.path.join(pkg, 'nagp'))) if f.endswith('.py'))
+    py_src += text(os.path.join(ROOT, 'bench.py'))
+    stale = {n: f for n, f in set_by.items() if '"%s"' % n not in c_src and n not in py_src}
+    assert not stale, 'set by tests / tools but read nowhere: %s' % stale
+    api = text(os.path.join(csrc, 'nagp_api.hip'))
+    head = 'static DevSwitches read_dev_switches() {'
+    assert api.count(head) == 1
+    body = api[api.index(head):]
+    body = body[:body.index('\n}\n')]
+    assert body.count('getenv(') >= 1 and c_src.count('getenv(') == body.count('getenv('), 'getenv outside read_dev_switches'
+
+
 def test_measmodel_handle_raises_the_documented_error():
     H = np.zeros((5, 7)); H[np.arange(5), [0, 1, 2, 3, 5]] = 1.0
     mm = nagp.MeasModel(H, np.ones((3, 2)), 3, 2)

@@ -26,8 +26,8 @@ for it in range(1, itts + 1):
     print('itts', it, 'oracle self-sensitivity Eft %.2e ttau %.2e' % (rel(o2[0], o[0]), rel(o2[5]['ttau'], o[5]['ttau'])),
           'NaN in oracle ttau/tnu/Eft', int(np.isnan(o[5]['ttau']).sum()), int(np.isnan(o[5]['tnu']).sum()), int(np.isnan(o[0]).sum()),
           'max |ttau| %.2e' % np.nanmax(np.abs(o[5]['ttau'])))
-    for env in ({}, {'NAGP_IH_PACK': '0'}, {'NAGP_IH_ROLES': '0'}, {'NAGP_NO_SPARSE': '1'}):
-        for k_ in ('NAGP_IH_PACK', 'NAGP_IH_ROLES', 'NAGP_NO_SPARSE'):
+    for env in ({}, {'NAGP_IH_ROLES': '0'}, {'NAGP_NO_SPARSE': '1'}):
+        for k_ in ('NAGP_IH_ROLES', 'NAGP_NO_SPARSE'):
             os.environ.pop(k_, None)
         os.environ.update(env)
         r = nagp.ihgp_ep_modulator_nmf(pr['w'], t, pr['y'], SSHandle(), mom, t, k1, k2, 1, D, N, alpha, d, it, nargout=6)
@@ -35,7 +35,7 @@ for it in range(1, itts + 1):
               'NaN gpu ttau/tnu/Eft', int(np.isnan(r[5]['ttau']).sum()), int(np.isnan(r[5]['tnu']).sum()), int(np.isnan(r[0]).sum()))
 
 if len(sys.argv) > 3:      # detail: first step where the default device path and the oracle part (one sweep)
-    for k_ in ('NAGP_IH_PACK', 'NAGP_IH_ROLES', 'NAGP_NO_SPARSE'):
+    for k_ in ('NAGP_IH_ROLES', 'NAGP_NO_SPARSE'):
         os.environ.pop(k_, None)
     np.set_printoptions(linewidth=200, precision=5)
     d = damp[:1]

@@ -31,5 +31,5 @@ else
   for wl in cfg5_fill cfg2_batch; do cp profiles/${tag}_pmc_traffic_$wl.txt profiles/${tag}_kernel_stats_$wl.csv profiles/${tag}_pmc_mfma_$wl.txt gpurun_out/ 2>/dev/null; done; cp profiles/pmc_traffic.json gpurun_out/pmc_traffic.json
   { for a in "19 4096 0 1" "19 4096 0 0" "38 4096 1 1" "38 4096 1 0"; do tools/ubench/gain_check $a; done; tools/ubench/chol16; } > gpurun_out/${tag}_gain_check.txt 2>&1
   res=${d%/*}      # the output folder of the traces above
-  ( time python bench.py --full > $res/${tag}_bench_default.json 2> $res/${tag}_bench_default.err ) 2> $res/${tag}_bench_default.time && tail -3 $res/${tag}_bench_default.time ; echo FINAL_PART2_DONE
+  ( unset NAGP_DEVELOPER; time python bench.py --full > $res/${tag}_bench_default.json 2> $res/${tag}_bench_default.err ) 2> $res/${tag}_bench_default.time && tail -3 $res/${tag}_bench_default.time ; echo FINAL_PART2_DONE
 fi
