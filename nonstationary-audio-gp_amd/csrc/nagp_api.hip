@@ -56,6 +56,7 @@ struct DevSwitches {
   bool force_rccl = false;       // NAGP_FORCE_RCCL
   bool stamps = false;           // NAGP_STAMPS
   bool ih_roles = true;          // NAGP_IH_ROLES: off when the value starts with '0'
+  bool ih_tables = false;        // NAGP_IH_TABLES: on when the value starts with '1' (table form of stage 1b in ihgp_adf8_kernel)
   int gain_form = 0;             // NAGP_GAIN_FORM: 0 = the plan's rule, 1 = solve, 2 = inv
   // numeric switches (0: not set, unless said otherwise)
   int chunks = 12;               // NAGP_CHUNKS (>= 1): smoother chunks per sweep
@@ -93,6 +94,7 @@ static DevSwitches read_dev_switches() {
   s.force_rccl = env("NAGP_FORCE_RCCL"); s.stamps = env("NAGP_STAMPS");
   const char* v;
   if ((v = env("NAGP_IH_ROLES"))) s.ih_roles = v[0] != '0';
+  if ((v = env("NAGP_IH_TABLES"))) s.ih_tables = v[0] == '1';
   if ((v = env("NAGP_GAIN_FORM"))) s.gain_form = !strcmp(v, "solve") ? 1 : (!strcmp(v, "inv") ? 2 : 0);
   if ((v = env("NAGP_CHUNKS"))) s.chunks = std::max(1, atoi(v));
   if ((v = env("NAGP_PIPELINE_SLOTS"))) s.pipeline_slots = std::max(1, atoi(v));

@@ -742,7 +742,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
         const size_t need8 = ihgp_adf8_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16;
         if (p->sp.bdesc && need8 <= 156 * 1024 && dev.ih_roles) {
           p->sp_ih8 = 1; p->lds_sp8 = need8;
-#define SL8(V) PLAN_TRY(set_lds(ihgp_adf8_kernel<V>, need8))
+#define SL8(V) do { if (dev.ih_tables) PLAN_TRY(set_lds((ihgp_adf8_kernel<V, true>), need8)); else PLAN_TRY(set_lds((ihgp_adf8_kernel<V, false>), need8)); } while (0)
           switch (o->cub_dim) { case 1: SL8(1); break; case 2: SL8(2); break; case 3: SL8(3); break; case 4: SL8(4); break; case 5: SL8(5); break; case 6: SL8(6); break; default: SL8(7); break; }
 #undef SL8
         }

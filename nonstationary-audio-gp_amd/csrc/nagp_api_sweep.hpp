@@ -781,7 +781,8 @@ static int exec_ihgp(nagp_plan* p) {
       } else if (p->sp_ih) {
         IhgpPar ia = ip; ia.hph_lds = p->hph_sp; ia.kb = p->kb_sp;
 #define LA(V) hipLaunchKernelGGL((ihgp_adf_kernel<V>), dim3(B), dim3(MSP_NT), p->lds_sp, p->stream, sh, p->b, mcf, p->sp, p->tb, ia)
-#define LA8(V) hipLaunchKernelGGL((ihgp_adf8_kernel<V>), dim3(B), dim3(MSR_NT), p->lds_sp8, p->stream, sh, p->b, mcf, p->sp, p->tb, ia)
+#define LA8(V) do { if (p->dev.ih_tables) hipLaunchKernelGGL((ihgp_adf8_kernel<V, true>), dim3(B), dim3(MSR_NT), p->lds_sp8, p->stream, sh, p->b, mcf, p->sp, p->tb, ia); \
+                    else hipLaunchKernelGGL((ihgp_adf8_kernel<V, false>), dim3(B), dim3(MSR_NT), p->lds_sp8, p->stream, sh, p->b, mcf, p->sp, p->tb, ia); } while (0)
         if (p->sp_ih8) switch (mcf.cdim) { case 1: LA8(1); break; case 2: LA8(2); break; case 3: LA8(3); break; case 4: LA8(4); break; case 5: LA8(5); break; case 6: LA8(6); break; default: LA8(7); break; }
         else switch (mcf.cdim) { case 1: LA(1); break; case 2: LA(2); break; case 3: LA(3); break; case 4: LA(4); break; case 5: LA(5); break; case 6: LA(6); break; default: LA(7); break; }
 #undef LA
@@ -881,7 +882,7 @@ extern "C" int nagp_plan_execute(nagp_plan* p) {
     if (hipMemcpy(st, p->d_stamps, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
       if (p->opts.kind == NAGP_KIND_IHGP)
         for (int w = 0; w < 2; ++w)
-          fprintf(stderr, "[nagp stamps] %s: wait at B1 %llu | Q/v %llu | B2..B3 %llu | weights %llu | wait at B4 %llu | marginal sums %llu | MFMA steps %llu | wait at B5 %llu\n",
+          fprintf(stderr, "[nagp stamps] %s: wait at B1 %llu | Q/v %llu | B2..B3 (direct stage 1b: wait at B2) %llu | weights %llu | wait at B4 %llu | bin sums %llu | - %llu | wait at B5 %llu\n",
                   w ? "last worker wave " : "first worker wave", st[8 + 8 * w], st[9 + 8 * w], st[10 + 8 * w], st[11 + 8 * w], st[12 + 8 * w], st[13 + 8 * w], st[14 + 8 * w], st[15 + 8 * w]);
     }
     if (p->opts.kind == NAGP_KIND_GF_EP && hipMemcpy(st, p->d_stamps, 64, hipMemcpyDeviceToHost) == hipSuccess)

@@ -545,8 +545,12 @@ __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomC
 
 // The same sweep with role-specialised waves (nagp_momsp.hpp, role layout): 512 threads, waves 0 / 1 as above, waves 2..7 run the
 // parallel stages of the cubature in their own loop.  A wave holds the registers of its role only, which is what lets two
-// waves share a SIMD (the sigma points take one round, the MFMA steps of two waves alternate on the matrix core).
-template <int CD>
+// waves share a SIMD.
+// Barriers of a step, TAB = false (the product): B1 | Q / 2Q / v (workers), link tables (wave 1) | B2 | Gaussian weights straight from
+// Q, v and the link tables (msr_stage1b_direct); e table (wave 1) | B4 | bin sums | B5 | serial tail.  TAB = true (developer switch
+// NAGP_IH_TABLES=1, the form of the four-wave kernel): behind B2 the tables e / t1 / ve on wave 1 and q0 / s0 on workers 3 and 4, one more
+// barrier (B3), then the weights from those tables (msp_stage1b).
+template <int CD, bool TAB>
 __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
@@ -596,10 +600,6 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   double* g_fm = b.fm + (size_t)pb * T * M;
   msr_init(CD, D, ws);
   __syncthreads();
-  // developer A/B, ip.dbg_wave & 64 (NAGP_STAMP_WORKER): tables / q0 / s0 of a step on every worker wave for itself (msr_fold) instead
-  // of on wave 1 / workers 3, 4 between two barriers.  Measured slower (profiles/r03_stamps_cycles.txt): a lone wave issues a dependent
-  // VALU instruction every 8 - 10 cycles, so the ~80 instructions of the stage on EVERY worker cost more than barrier B3 saves.
-  const bool fold = (CD * CD <= 48) && (ip.dbg_wave & 64) != 0;
   if (wave >= MSR_W0) {
     // ================= worker role: the parallel stages of the cubature; the same barriers as the serial role below
     const MspLay lay = msp_layout(CD, D, 1);
@@ -624,16 +624,14 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       msp_qv<CD>(xw, mc);            // workers 0..2
       WK_STAMP(1);
       lds_barrier();                 // B2
-      if (fold) {                    // tables, q0, s0 on every worker wave for itself: no barrier B3
-        double q0, s0;
-        if constexpr (CD * CD <= 48) msr_fold<CD>(xw, mc, q0, s0); else { q0 = 0.0; s0 = 0.0; }
-        WK_STAMP(2);
-        msp_stage1b_qs<CD>(xw, mc, sp, sn2a, ry[kk], q0, s0);
-      } else {
+      if constexpr (TAB) {
         if (wave == MSR_W0 + 3 || wave == MSR_W0 + 4) msr_q0_or_s0(xw, wave == MSR_W0 + 3, ws + lay.q0, ws + lay.s0);
         lds_barrier();                 // B3
-        WK_STAMP(2);                   // (B2 .. B3: tables on wave 1, q0 / s0 on worker 3)
+        WK_STAMP(2);                   // (B2 .. B3: tables on wave 1, q0 / s0 on workers 3, 4)
         msp_stage1b<CD>(xw, mc, sp, sn2a, ry[kk], ws);
+      } else {
+        WK_STAMP(2);                   // (wait at B2: wave 1's link tables)
+        msr_stage1b_direct<CD>(xw, sn2a, ry[kk]);
       }
       WK_STAMP(3);
       lds_barrier();                 // B4
@@ -737,7 +735,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   };
   if (wave <= 1) head(ip.k_start);
   // link tables of a step (the exp / log chain of the modulators' sigma-point coordinates, ~1 000 cycles on wave 1): evaluated BEHIND
-  // barrier B1, beside the worker waves' Q / 2Q / v stage -- nothing reads them before wave 1's own msp_tables behind B2.  (Evaluated
+  // barrier B1, beside the worker waves' Q / 2Q / v stage -- nothing reads them before the stages behind B2.  (Evaluated
   // ahead of B1 they were the tail of the serial chain: wave 0 waited ~800 cycles at B1 for them.)  ip.dbg_wave & 16: the old placement.
   const bool link_early = (ip.dbg_wave & 16) != 0;
   if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }      // link tables of the first step
@@ -757,11 +755,13 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       if (wave == 1 && !link_early) msp_link<CD>(x, mc);
       lds_barrier();                 // B2
       IH_STAMP(0);
-      if (!fold) {
+      if constexpr (TAB) {
         if (wave == 1) msp_tables<CD>(x, mc);
         lds_barrier();                 // B3
+      } else {
+        if (wave == 1) msr_etable<CD>(x, mc);      // read behind B4 only (level 2 of msr_sums): beside the workers' weights
       }
-      // (tables, q0, s0, Gaussian weights: worker waves)
+      // (Gaussian weights: worker waves)
       lds_barrier();                 // B4
       IH_STAMP(1);
       // (bin sums: worker waves)

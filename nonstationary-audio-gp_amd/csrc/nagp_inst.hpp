@@ -156,11 +156,13 @@
   P void nagp::ihgp_adf_kernel<5> NAGP_SIG_IHA; P void nagp::ihgp_adf_kernel<6> NAGP_SIG_IHA;                            \
   P void nagp::ihgp_adf_kernel<7> NAGP_SIG_IHA;
 
-#define NAGP_LIST_IHA8(P)                                                                                                  \
-  P void nagp::ihgp_adf8_kernel<1> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2> NAGP_SIG_IHA;                          \
-  P void nagp::ihgp_adf8_kernel<3> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4> NAGP_SIG_IHA;                          \
-  P void nagp::ihgp_adf8_kernel<5> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6> NAGP_SIG_IHA;                          \
-  P void nagp::ihgp_adf8_kernel<7> NAGP_SIG_IHA;
+// (TAB = false: the direct stage 1b, the product; TAB = true: the table form, developer switch NAGP_IH_TABLES=1)
+#define NAGP_LIST_IHA8T(P, TAB)                                                                                            \
+  P void nagp::ihgp_adf8_kernel<1, TAB> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, TAB> NAGP_SIG_IHA;                \
+  P void nagp::ihgp_adf8_kernel<3, TAB> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, TAB> NAGP_SIG_IHA;                \
+  P void nagp::ihgp_adf8_kernel<5, TAB> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, TAB> NAGP_SIG_IHA;                \
+  P void nagp::ihgp_adf8_kernel<7, TAB> NAGP_SIG_IHA;
+#define NAGP_LIST_IHA8(P) NAGP_LIST_IHA8T(P, false) NAGP_LIST_IHA8T(P, true)
 
 // the role-specialised sweep for likModulatorPreCalcwn (nagp_momsq.hpp)
 #define NAGP_LIST_IHA8Q(P)                                                                                                 \

@@ -335,6 +335,16 @@ __device__ __forceinline__ void msp_tables(const X& x, const MomCfg& c) {
     x.a_out[5 * MSP_TS] = vv * e;
   }
 }
+// the e table alone (direct form of the role layout, msr_stage1b_direct: t1, ve, q0, s0 have no reader there); e = lk - l0 is read by
+// level 2 of msr_sums, behind the barrier that follows the weights
+template <int CD, class X>
+__device__ __forceinline__ void msr_etable(const X& x, const MomCfg& c) {
+  const int TN = CD * c.nd;
+  if (((int)threadIdx.x & 63) < TN) {
+    const double lk = ((msp_rp)x.a_out)[0], l0o = *x.a_l0own;
+    x.a_out[3 * MSP_TS] = lk - l0o;
+  }
+}
 // stage B, q0 = l0' Q l0 and s0 = v' l0 (one wave)
 template <class X>
 __device__ __forceinline__ void msp_q0s0(const X& x, double* q0, double* s0) {
@@ -358,22 +368,6 @@ __device__ __forceinline__ void msp_stageB(const MspCtx<CD>& x, const MomCfg& c,
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   if (wave == __builtin_amdgcn_readfirstlane(x.lw)) msp_tables<CD>(x, c);
   else if (wave == __builtin_amdgcn_readfirstlane(x.qw)) msp_q0s0(x, ws + l.q0, ws + l.s0);
-}
-
-__device__ __forceinline__ void msp_wave_fence();
-// Folded stage B of the role layout (CD*CD <= 48): this wave's own copy of the tables -- every worker wave writes the same values to the
-// same LDS words and reads them back behind its own writes (DS operations of a wave complete in issue order) -- and q0 = l0' Q l0,
-// s0 = v' l0 from one 16-lane group sum: rows 0..2 of the wave hold the q0 terms, row 3 the s0 terms, at the lane positions (inside a row)
-// and in the association order of the two-wave form (msr_q0_or_s0), so both sums keep their bits.
-template <int CD, class X>
-__device__ __forceinline__ void msr_fold(const X& x, const MomCfg& c, double& q0, double& s0) {
-  static_assert(CD * CD <= 48, "q0 terms beyond three rows of the wave");
-  const double t = (*x.f_p0) * (*x.f_p1) * (*x.f_p2);      // unused lanes: zero * ...
-  msp_tables<CD>(x, c);
-  const double v = group_sum(t, 16);
-  q0 = (readlane_d(v, 0) + readlane_d(v, 16)) + (readlane_d(v, 32) + 0.0);
-  s0 = (readlane_d(v, 48) + 0.0) + (0.0 + 0.0);
-  msp_wave_fence();
 }
 
 // stage 1b.  After a barrier behind stage B; ends without a barrier.
@@ -434,6 +428,60 @@ __device__ __forceinline__ void msp_stage1b_qs(const X& x, const MomCfg& c, cons
       x.p_c[u][X::CS] = w0 * q;
       x.p_c[u][2 * X::CS] = w0 * (q * q - inv);
     }
+  }
+}
+
+// stage 1b of the role layout in the DIRECT form (likModulatorNMFPower.m:44-47 as written): with Q = W' diag(s2) W and v = W' mu
+// behind the barrier that follows msp_qv,
+//   sum_d a_d mu_d = v . lk_p,      sum_d a_d^2 s2_d = lk_p' Q lk_p = sum_j lk_j (Q_jj lk_j + sum_{j2 > j} 2 Q_jj2 lk_j2)
+// with lk_pj = link table[j][c_pj]: CD reads at static per-lane addresses, Q (diagonal) / 2Q (above it) / v at wave-uniform addresses
+// (broadcast reads), all issued before the first FMA; CD independent chains, no cross-lane operation.  Needs nothing of stage B: no
+// e / t1 / ve tables, no q0 / s0, no barrier between msp_qv's and this stage's.  Every term is positive for W >= 0, lk > 0 (no
+// cancellation, where the centre + deviation form of msp_stage1b_qs adds terms of both signs).  Lanes without a point read the zero word.
+template <int CD, class X>
+__device__ __forceinline__ void msr_stage1b_direct(const X& x, double sn2a, double y) {
+  if (__builtin_amdgcn_readfirstlane(x.p_any[0]) == 0) return;   // wave-uniform skip
+  constexpr int NO = CD * (CD - 1) / 2;
+  double lk[CD], qd[CD], vv[CD], qo[NO + 1];
+#pragma unroll
+  for (int j = 0; j < CD; ++j) { lk[j] = *x.d_lk[j]; qd[j] = x.d_qv[j * CD + j]; vv[j] = x.d_qv[2 * CD * CD + j]; }
+  {
+    int q = 0;
+#pragma unroll
+    for (int j = 0; j < CD; ++j)
+#pragma unroll
+      for (int j2 = j + 1; j2 < CD; ++j2) { qo[q] = x.d_qv[CD * CD + j * CD + j2]; ++q; }
+  }
+#pragma unroll
+  for (int j = 0; j < CD; ++j) asm volatile("" : "+v"(lk[j]), "+v"(qd[j]), "+v"(vv[j]));
+#pragma unroll
+  for (int q = 0; q < NO; ++q) asm volatile("" : "+v"(qo[q]));
+  double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+  for (int j = 0; j < CD; ++j) { if (j & 1) a1 = fma(vv[j], lk[j], a1); else a0 = fma(vv[j], lk[j], a0); }
+  const double sam = a0 + a1;
+  // the rows' chains are independent (row j: CD - j operations); the two sums take the short rows first
+  double t[CD];
+  {
+    int q = 0;
+#pragma unroll
+    for (int j = 0; j < CD; ++j) {
+      t[j] = qd[j] * lk[j];
+#pragma unroll
+      for (int j2 = j + 1; j2 < CD; ++j2) { t[j] = fma(qo[q], lk[j2], t[j]); ++q; }
+    }
+  }
+  double b0 = 0.0, b1 = 0.0;
+#pragma unroll
+  for (int j = CD - 1; j >= 0; --j) { if (j & 1) b1 = fma(lk[j], t[j], b1); else b0 = fma(lk[j], t[j], b0); }
+  const double sa2 = b0 + b1;
+  double pdf, q, inv;
+  gauss_terms(y, sam, sn2a + sa2, pdf, q, inv);
+  const double w0 = x.p_wn[0] * pdf;
+  if (x.p_ok[0]) {
+    x.p_c[0][0] = w0;
+    x.p_c[0][X::CS] = w0 * q;
+    x.p_c[0][2 * X::CS] = w0 * (q * q - inv);
   }
 }
 
@@ -528,8 +576,8 @@ __device__ __forceinline__ void msp_outputs(msp_rp acc, bool sub, int jmod, cons
 
 // =====================================================================================================================
 // Role layout (LAY = 1): 512 threads.  Waves 0 and 1 carry the serial stages of the caller (wave 1 also evaluates the link
-// tables and e / t1 / ve); waves 2 .. 7 carry the parallel ones: Q / 2Q / v on waves 2..4, q0 / s0 on wave 5, one sigma
-// point per lane of the six (<= 384 points), the cubature sums round the six.  The two roles run in separate loops of the
+// tables and e -- with t1 / ve in the table form of stage 1b); waves 2 .. 7 carry the parallel ones: Q / 2Q / v on waves 2..4,
+// (table form: q0 / s0 on waves 5 / 6), one sigma point per lane of the six (<= 384 points), the cubature sums round the six.  The two roles run in separate loops of the
 // kernel, so a wave holds the registers of its own role only: two waves per SIMD within 256 registers each.
 //
 // The cubature sums (likModulatorNMFPower.m:59-80) from BIN SUMS over static member lists, on the VALU.  Every sigma point
@@ -568,10 +616,8 @@ struct MsrW {
   static constexpr int NPS = 1, CS = MSR_CS;
   int q_kind; msp_rp q_ww, q_src; msp_wp q_out0, q_out1, q_out2, q_out3;
   int b_kind; msp_rp b_p0, b_p1, b_p2;
-  // folded form (msr_fold): EVERY worker wave forms the tables e / t1 / ve (lanes < CD*nd) and q0, s0 for itself between B2 and the
-  // weights -- no barrier B3, no wait for the serial wave
-  msp_rp a_l0[CD], a_l0own, a_qrow, a_qjj, a_v; msp_wp a_out; msp_rp f_p0, f_p1, f_p2;
-  msp_rp p_e[1][MSP_NZ], p_q[1][6]; msp_wp p_c[1]; double p_wn[1]; bool p_ok[1]; int p_any[1];
+  msp_rp p_e[1][MSP_NZ], p_q[1][6]; msp_wp p_c[1]; double p_wn[1]; bool p_ok[1]; int p_any[1];   // (p_e, p_q: table form of stage 1b)
+  msp_rp d_lk[CD], d_qv;                                              // direct form of stage 1b: this point's link entries; Q | 2Q | v (uniform)
   msp_rp s_mem[MSR_NMEM]; msp_wp s_out; int s_grp;                    // level 1: members, result slot, group flags (1: lane ^ 1, 2: lane ^ 2)
   msp_rp t_bin[MSR_KT], t_fa[MSR_KT], t_fb[MSR_KT]; msp_wp t_out; int t_grp;   // level 2
 };
@@ -622,7 +668,7 @@ __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave - MSR_W0;     // wr = 0 .. 5
   const int nd = c.nd, D = c.D, npt = c.n_pts;
   const MspLay l = msp_layout(CD, D, 1);
-  // ---- q0 on worker 3, s0 on worker 4 (one wave sum each, side by side between barriers B2 and B3)
+  // ---- table form of stage 1b: q0 on worker 3, s0 on worker 4 (one wave sum each, side by side between barriers B2 and B3)
   {
     const int L = tid - 64 * (MSR_W0 + 3), L2 = tid - 64 * (MSR_W0 + 4);
     x.b_kind = 0; x.b_p0 = x.b_p1 = x.b_p2 = (msp_rp)(ws + l.zero);
@@ -632,29 +678,6 @@ __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const 
     } else if (L2 >= 0 && L2 < CD) {
       const int j = L2;
       x.b_kind = 2; x.b_p0 = (msp_rp)(ws + l.v + j); x.b_p1 = (msp_rp)(ws + l.lk + j * nd + sp.c0); x.b_p2 = (msp_rp)(ws + l.one);
-    }
-  }
-  // ---- folded form: table lane t = lane (as on the serial wave's lanes, msr_setup_S); q0 terms on lanes 0 .. CD*CD-1 and the s0 terms
-  // on lanes 48 .. 48+CD-1 of ONE 16-lane group sum (CD*CD <= 48), or the layout of the two-wave form twice (msr_fold)
-  {
-    const int TN = CD * nd;
-    const int t = (lane < TN) ? lane : 0;
-    const int j = t / nd;
-    const int oz = opaque_zero();
-#pragma unroll
-    for (int j2 = 0; j2 < CD; ++j2) x.a_l0[j2] = (msp_rp)(ws + l.lk + j2 * nd + sp.c0) + oz;
-    x.a_l0own = (msp_rp)(ws + l.lk + j * nd + sp.c0);
-    x.a_qrow = (msp_rp)(ws + l.Q + j * CD);
-    x.a_qjj = (msp_rp)(ws + l.Q + j * CD + j);
-    x.a_v = (msp_rp)(ws + l.v + j);
-    x.a_out = (msp_wp)(ws + t);
-    x.f_p0 = x.f_p1 = x.f_p2 = (msp_rp)(ws + l.zero);
-    if (lane < CD * CD && CD * CD <= 48) {
-      const int jq = lane / CD, j2 = lane - jq * CD;
-      x.f_p0 = (msp_rp)(ws + l.Q + lane); x.f_p1 = (msp_rp)(ws + l.lk + jq * nd + sp.c0); x.f_p2 = (msp_rp)(ws + l.lk + j2 * nd + sp.c0);
-    } else if (lane >= 48 && lane < 48 + CD && CD * CD <= 48) {
-      const int js = lane - 48;
-      x.f_p0 = (msp_rp)(ws + l.v + js); x.f_p1 = (msp_rp)(ws + l.lk + js * nd + sp.c0); x.f_p2 = (msp_rp)(ws + l.one);
     }
   }
   // ---- Q / 2Q / v on workers 0..2: 4-lane group -> one entry
@@ -714,6 +737,10 @@ __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const 
       }
     x.p_c[0] = (msp_wp)(ws + l.c0 + p);
     x.p_wn[0] = ok ? c.wn[p] : 0.0;
+    // direct form: the link entry of every dimension at this point's coordinate code (the centre's code where pdesc names none)
+#pragma unroll
+    for (int j = 0; j < CD; ++j) x.d_lk[j] = ok ? (msp_rp)(ws + l.lk + j * nd + c.code[(size_t)p * CD + j]) : zero;
+    x.d_qv = (msp_rp)(ws + l.Q) + opaque_zero();
   }
   // ---- cubature sums: this lane's members and terms (host lists; offsets in doubles from ws, unused entries address the zero word)
   {
