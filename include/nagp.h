@@ -251,6 +251,39 @@ int nagp_plan_download(nagp_plan* plan, nagp_out* outs);          /* n_problems 
 int nagp_plan_upload_sites(nagp_plan* plan, const double* const* ttau0, const double* const* tnu0); /* warm start: n_problems pointers to
                                                                      M x T doubles each, or NULL/NULL to return to cold starts */
 int64_t nagp_plan_device_bytes(const nagp_plan* plan);
+
+/* Opt-in time-parallel schedule of the fixed-site Kalman filter (NAGP_KIND_GF_EP, sweeps >= 2, predict and nlml mode).  In those sweeps the
+ * sites are fixed for the steps k < T-1 and the filter is one workgroup per problem, sequential in k.  With the option set, [0, T-1) is cut
+ * into n_windows windows that run at the same time, one workgroup per (problem, window): window j >= 1 starts `overlap` steps early from the
+ * prior (m = 0, P = Pinf), runs those warm-up steps without storing anything and stores from its first own step on -- a Kalman filter with
+ * fixed sites forgets its start (profiles/r07_window_contraction.txt: how fast, per model).  Nothing is taken on trust: the state a window
+ * started its own steps from is compared with what the window in front of it stored for that step,
+ *     mismatch_m = max|dm| / max(max|m|, sqrt(max|P|)),   mismatch_P = max|dP| / max|P|,
+ * boundary by boundary in increasing order, and a window whose boundary is above `tol` in either figure runs again from the stored state
+ * (the sequential continuation), after which the next boundary is checked against the re-run.  Worst case: the sequential time plus the
+ * warm-ups; tol = 0 re-runs every window and gives the sequential result bit for bit.  What a window within tol leaves in the outputs is
+ * its boundary mismatch propagated (and contracted further) through its own steps.
+ * n_windows <= 1 turns the option off: every launch, buffer and output is then what a plan that never called this is.  The option holds for
+ * every later nagp_plan_execute.  On a windowed sweep the smoother starts behind the filter (no chunk pipeline beside it) and the cross-sweep
+ * schedule is not used: windows pay where compute units are idle -- one long sequence, or fewer segments than compute units.
+ * NAGP_EUNSUPPORTED for n_windows > 1 on NAGP_KIND_IHGP / NAGP_KIND_GIEKF plans, NAGP_EINVAL for overlap < 0 or tol < 0 (host checks, before any device call). */
+int nagp_plan_set_windows(nagp_plan* plan, int32_t n_windows, int32_t overlap, double tol);
+/* What the windows of the last nagp_plan_execute did, summed over its sweeps.  A window counts once however many problems the plan holds
+ * (its workgroups run, pass or re-run together: a boundary passes when every problem is within tol). */
+typedef struct nagp_window_stats {
+  int64_t windows_run;        /* windows launched in the time-parallel launches */
+  int64_t boundaries_checked; /* boundary comparisons read by the host */
+  int64_t reruns;             /* windows run again from the stored state */
+  int64_t warmup_steps;       /* warm-up steps of those windows (per problem) */
+  double worst_m;             /* largest mismatch_m seen at a checked boundary (Inf: a NaN state) */
+  double worst_P;             /* largest mismatch_P */
+} nagp_window_stats;
+int nagp_plan_window_stats(const nagp_plan* plan, nagp_window_stats* stats);
+/* The geometry nagp_plan_set_windows uses (pure host code): the fixed-site pass covers the steps [0, T-1); they are cut into
+ * P = min(n_windows, T-1) windows (at least one) of equal length to within a step.  Returns P (or a negative status);
+ * t_start[0 .. P] (P+1 entries, t_start[P] = T-1; room for n_windows + 1): window j stores the steps [t_start[j], t_start[j+1]);
+ * t_warm[0 .. P-1] (room for n_windows): its warm-up starts at t_warm[j] = max(0, t_start[j] - overlap), t_warm[0] = 0. */
+int nagp_window_partition(int64_t T, int32_t n_windows, int32_t overlap, int64_t* t_start, int64_t* t_warm);
 void nagp_plan_destroy(nagp_plan* plan);
 
 /* Multi-GPU form of the batched call (one process, the GPUs of one node) -- what a MEX caller uses to spread audio segments

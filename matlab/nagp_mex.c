@@ -12,7 +12,7 @@
  *                D, N, lik_param                                         -> nagp_model
  * y      double vector (NaN = missing)
  * opts   struct: kind, mode, lik_kind, link_kind, link_shift, wn, xn_unscaled, ep_fraction, ep_damping, l_iter,
- *                predict_at_k1, flags, device [, chunk, ttau0, tnu0, ep_itts]  -> nagp_opts
+ *                predict_at_k1, flags, device [, chunk, ttau0, tnu0, ep_itts, windows, window_overlap, window_tol]  -> nagp_opts (windows: nagp_plan_set_windows)
  *                (ep_itts defaults to numel(ep_damping); the EKF kind passes it explicitly as g_iter)
  * tables struct: r (n_grid x 1), PP, PG (double vectors), pp_off, pg_off (int64, M)          -> nagp_ihgp_tables
  *
@@ -308,7 +308,22 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     st = nagp_ihgp_run(&m, &tb, mxGetPr(prhs[1]), (int64_t)T, &o, &out);
   } else if (o.kind == NAGP_KIND_GIEKF) {
     st = nagp_giekf_run(&m, mxGetPr(prhs[1]), (int64_t)T, &o, &out);
-  } else {
+  } else if (scalar_or(prhs[2], "windows", 0.0) > 1.0) {
+    /* optional field `windows` of the options (nagp_opts.m): the fixed-site filter of the sweeps >= 2 in that many windows at the same time
+     * (nagp_plan_set_windows; fields window_overlap / window_tol, defaults 8000 steps / 1e-10) -- the steps of nagp_ep_run on a plan of one problem */
+    nagp_plan* pl = NULL;
+    const double* ys[1]; const double* t0[1]; const double* n0[1];
+    ys[0] = mxGetPr(prhs[1]); t0[0] = o.ttau0; n0[0] = o.tnu0;
+    if (out.PS) o.flags |= NAGP_FLAG_WANT_PS;
+    st = nagp_plan_create(&pl, 1, &m, NULL, (int64_t)T, &o);
+    if (st == NAGP_OK) st = nagp_plan_set_windows(pl, (int32_t)scalar_or(prhs[2], "windows", 0.0), (int32_t)scalar_or(prhs[2], "window_overlap", 8000.0),
+                                                  scalar_or(prhs[2], "window_tol", 1e-10));
+    if (st == NAGP_OK) st = nagp_plan_upload_y(pl, ys);
+    if (st == NAGP_OK && (o.ttau0 || o.tnu0)) st = nagp_plan_upload_sites(pl, t0, n0);
+    if (st == NAGP_OK) st = nagp_plan_execute(pl);
+    if (st == NAGP_OK) st = nagp_plan_download(pl, &out);
+    nagp_plan_destroy(pl);
+  } else {      /* (no `windows` field, or <= 1: today's path) */
     st = nagp_ep_run(&m, mxGetPr(prhs[1]), (int64_t)T, &o, &out);
   }
   fail_if(st);

@@ -211,6 +211,12 @@ struct nagp_plan {
   nagp_timings tim{};
   std::vector<double> h_hval;          // [B][M]
   size_t lds_filter = 0, lds_gain = 0, lds_scan = 0, lds_ep = 0, lds_ih = 0;
+  // time-parallel fixed-site filter of sweeps >= 2 (nagp_plan_set_windows; off while win.size() < 2): the windows of the plan, their
+  // device copy, the per-(problem, window) state at the end of the warm-up, the per-(problem, boundary) mismatches (m, P)
+  std::vector<FilterWin> win;
+  double* d_win = nullptr; double* d_win_state = nullptr; double* d_win_cmp = nullptr;
+  double win_tol = 0.0;
+  nagp_window_stats wstats{};
 };
 
 extern "C" int nagp_version(void) { return NAGP_VERSION; }

@@ -3,10 +3,11 @@
 // The sweep scheduler: filter launches, the chunk-pipelined smoother (gain, compose, boundary, apply), site refresh, the three execute loops, download.
 
 // ---------------------------------------------------------------------------------------------
-static int launch_filter(nagp_plan* p, const FilterPar& fp_in) {
+// n_win > 0: the time-parallel form of a fixed-site launch -- one workgroup per (problem, window of fp.win), nothing published
+static int launch_filter(nagp_plan* p, const FilterPar& fp_in, int n_win = 0) {
   FilterPar fp = fp_in;
   fp.kb = p->kb_f;
-  if (p->pipeline && fp.store_PF) { fp.progress = p->h_progress; fp.progress_every = 256; }
+  if (p->pipeline && fp.store_PF && !n_win) { fp.progress = p->h_progress; fp.progress_every = 256; }
   fp.dbg = p->dev.filter_dbg;   // developer switch: see FilterPar::dbg
   const bool ekf = p->opts.kind == NAGP_KIND_GIEKF;
   MomCfg mc = p->mc; mc.DG = p->DG_f; mc.cache_tabs = p->cache_f; mc.store_a = p->sta_f; mc.chunk_cap = p->chunk_cap_f;
@@ -18,6 +19,12 @@ static int launch_filter(nagp_plan* p, const FilterPar& fp_in) {
   if (ekf && p->NT_f + 64 <= 512 && p->sh.N <= 64) { nt_ekf = p->NT_f + 64; fp.spl_wave = 1; }   // one extra wave for the link
   Timed t(p, adf ? NAGP_K_FILTER : NAGP_K_FILTER_LIN);
   dim3 g(p->B), bl(p->NT_f);
+  const dim3 gw(p->B, n_win > 0 ? n_win : 1);
+  // fixed-site launches (no step calls mom): the sequential kernel, or its windowed instantiation
+#define LFIX(TP, LBV, CP, NTH) do { \
+    if (n_win > 0) hipLaunchKernelGGL((gf_filter_kernel<TP, 0, -1, LBV, 0, CP, true>), gw, dim3(NTH), p->lds_filter, p->stream, p->sh, p->b, mc, fp); \
+    else hipLaunchKernelGGL((gf_filter_kernel<TP, 0, -1, LBV, 0, CP>), g, dim3(NTH), p->lds_filter, p->stream, p->sh, p->b, mc, fp); } while (0)
+  if (n_win > 0 && adf) FAIL(NAGP_EINVAL, "windowed launch of a pass that calls mom");
   if (p->sh.Ms < p->sh.M) {      // split blocks: one geometry (the fixed-site one) for every launch, the general mom code
     fp.cpl_doubles = (int)filter_cpl_doubles(p->sh); fp.cpl_chunk = filter_cpl_chunk(p->sh);
     mc.sp = MomSp{};
@@ -27,9 +34,9 @@ static int launch_filter(nagp_plan* p, const FilterPar& fp_in) {
 #define LFC4(V) LFC(4, 0, V)
     if (ekf) switch (p->TPT_f) { case 1: LFC(1, 1, 0); break; case 2: LFC(2, 1, 0); break; default: LFC(4, 1, 0); break; }
     else if (adf) switch (p->TPT_f) { case 1: NAGP_MV_SWITCH(mom_variant(mc), LFC1) break; case 2: NAGP_MV_SWITCH(mom_variant(mc), LFC2) break; default: NAGP_MV_SWITCH(mom_variant(mc), LFC4) break; }
-    else if (p->wide_l && p->NT_l <= 768) hipLaunchKernelGGL((gf_filter_kernel<1, 0, -1, 768, 0, true>), g, dim3(p->NT_l), p->lds_filter, p->stream, p->sh, p->b, mc, fp);
-    else if (p->wide_l) hipLaunchKernelGGL((gf_filter_kernel<1, 0, -1, 1024, 0, true>), g, dim3(p->NT_l), p->lds_filter, p->stream, p->sh, p->b, mc, fp);
-    else switch (p->TPT_f) { case 1: LFC1(-1); break; case 2: LFC2(-1); break; default: LFC4(-1); break; }
+    else if (p->wide_l && p->NT_l <= 768) LFIX(1, 768, true, p->NT_l);
+    else if (p->wide_l) LFIX(1, 1024, true, p->NT_l);
+    else switch (p->TPT_f) { case 1: LFIX(1, 512, true, p->NT_f); break; case 2: LFIX(2, 512, true, p->NT_f); break; default: LFIX(4, 512, true, p->NT_f); break; }
 #undef LFC
 #undef LFC1
 #undef LFC2
@@ -82,16 +89,17 @@ static int launch_filter(nagp_plan* p, const FilterPar& fp_in) {
 #undef LF4
 #undef LF5
     } else if (p->wide_l) {
-      if (p->NT_l <= 768) hipLaunchKernelGGL((gf_filter_kernel<1, 0, -1, 768>), g, dim3(p->NT_l), p->lds_filter, p->stream, p->sh, p->b, mc, fp);
-      else hipLaunchKernelGGL((gf_filter_kernel<1, 0, -1, 1024>), g, dim3(p->NT_l), p->lds_filter, p->stream, p->sh, p->b, mc, fp);
+      if (p->NT_l <= 768) LFIX(1, 768, false, p->NT_l);
+      else LFIX(1, 1024, false, p->NT_l);
     } else {   // no step of this launch calls mom
       switch (p->TPT_f) {
-        case 1: hipLaunchKernelGGL((gf_filter_kernel<1, 0, -1>), g, dim3(p->NT_fl), p->lds_filter, p->stream, p->sh, p->b, mc, fp); break;
-        case 2: hipLaunchKernelGGL((gf_filter_kernel<2, 0, -1>), g, bl, p->lds_filter, p->stream, p->sh, p->b, mc, fp); break;
-        default: hipLaunchKernelGGL((gf_filter_kernel<4, 0, -1>), g, bl, p->lds_filter, p->stream, p->sh, p->b, mc, fp); break;
+        case 1: LFIX(1, 512, false, p->NT_fl); break;
+        case 2: LFIX(2, 512, false, p->NT_f); break;
+        default: LFIX(4, 512, false, p->NT_f); break;
       }
     }
   }
+#undef LFIX
   HIP_TRY(hipGetLastError());
   return NAGP_OK;
 }
@@ -574,6 +582,102 @@ static int zero_async(nagp_plan* p, void* ptr, size_t bytes) {
   return NAGP_OK;
 }
 
+// ---- time-parallel fixed-site filter (nagp_plan_set_windows)
+// The geometry: the fixed-site pass covers steps [0, T-1); P = min(n_windows, T-1) windows (at least one) of equal length to within a step,
+// window j = [t_start[j], t_start[j+1]), warm-up from t_warm[j] = max(0, t_start[j] - overlap) (t_warm[0] = 0).  Returns P.
+static int window_partition(int64_t T, int n_windows, int64_t overlap, std::vector<int64_t>& t_start, std::vector<int64_t>& t_warm) {
+  const int64_t n = std::max<int64_t>(T - 1, 0);
+  const int P = (int)std::max<int64_t>(1, std::min<int64_t>(std::max(n_windows, 1), n));
+  t_start.assign((size_t)P + 1, 0); t_warm.assign((size_t)P, 0);
+  for (int j = 0; j <= P; ++j) t_start[j] = n * j / P;      // (n < 2^40, P < 2^16)
+  for (int j = 1; j < P; ++j) t_warm[j] = std::max<int64_t>(0, t_start[j] - overlap);
+  return P;
+}
+
+// Boundary check of the windowed filter: workgroup (i, q) compares the state window j = j_first + i of problem q started its stored steps
+// from (win_state) with what window j - 1 stored for step k_begin_j - 1:
+//   out[q][j][0] = max|dm| / max(max|m|, sqrt(max|P|)),  out[q][j][1] = max|dP| / max|P|      (a NaN anywhere gives +Inf)
+static __global__ void __launch_bounds__(256) win_boundary_kernel(Shape sh, Bufs b, const FilterWin* win, const double* win_state, int n_win, int j_first, double* out) {
+  __shared__ double red[4][256];
+  const int j = j_first + blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+  const int64_t k = win[j].k_begin - 1;
+  const int nlow = sh.M * (sh.M + 1) / 2;
+  const size_t pfd = pf_step_doubles(sh);
+  const double* wst = win_state + ((size_t)q * n_win + j) * filter_win_doubles(sh);
+  const double* Pr = b.PF + ((size_t)q * sh.T + k) * pfd;
+  const double* mr = b.MF + ((size_t)q * sh.T + k) * sh.S;
+  auto up = [](double a, double v) { return (v == v) ? fmax(a, v) : (double)INFINITY; };
+  double dm = 0.0, nm = 0.0, dP = 0.0, nP = 0.0;
+  for (int i = tid; i < sh.S; i += 256) { dm = up(dm, fabs(wst[pfd + i] - mr[i])); nm = up(nm, fabs(mr[i])); }
+  for (int i = tid; i < nlow * 16; i += 256) {
+    const size_t o = pf_off(i >> 4, i & 15);
+    dP = up(dP, fabs(wst[o] - Pr[o])); nP = up(nP, fabs(Pr[o]));
+  }
+  red[0][tid] = dm; red[1][tid] = nm; red[2][tid] = dP; red[3][tid] = nP;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (tid < s)
+      for (int c = 0; c < 4; ++c) red[c][tid] = fmax(red[c][tid], red[c][tid + s]);      // (+Inf stands for NaN here: fmax keeps it)
+    __syncthreads();
+  }
+  if (tid == 0) {
+    double* o = out + ((size_t)q * n_win + j) * 2;
+    o[0] = red[0][0] / fmax(red[1][0], sqrt(red[3][0]));
+    o[1] = red[2][0] / red[3][0];
+  }
+}
+
+// a window runs again: what its discarded run added to the NaN-observation counter comes off first
+static __global__ void win_uncount_kernel(Shape sh, Bufs b, const double* win_state, int n_win, int j, int B) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < B) b.counters[(size_t)q * 4 + 2] -= (unsigned long long)win_state[((size_t)q * n_win + j) * filter_win_doubles(sh) + filter_win_nan(sh)];
+}
+
+// One fixed-site pass over [0, T-1) in windows: all windows of all problems at once, then the boundaries in increasing order on the host --
+// a window whose start state is further than tol from what the window in front of it stored runs again from that stored state (the
+// sequential continuation, k_begin = t_j), and the next boundary is checked against the re-run.  tol = 0 re-runs every window.
+static int filter_windows(nagp_plan* p, const FilterPar& fp) {
+  const Shape& sh = p->sh; const int P = (int)p->win.size(), B = p->B;
+  FilterPar fw = fp;
+  fw.k_begin = 0; fw.k_end = sh.T - 1; fw.win = reinterpret_cast<const FilterWin*>(p->d_win); fw.win_state = p->d_win_state;
+  RUN(launch_filter(p, fw, P));
+  p->wstats.windows_run += P;
+  for (int j = 0; j < P; ++j) p->wstats.warmup_steps += p->win[j].k_begin - p->win[j].k_warm;
+  std::vector<double> cmp((size_t)B * P * 2);
+  auto check = [&](int j0, int nj) -> int {
+    {
+      Timed t(p, NAGP_K_OTHER);
+      hipLaunchKernelGGL(win_boundary_kernel, dim3(nj, B), dim3(256), 0, p->stream, sh, p->b, reinterpret_cast<const FilterWin*>(p->d_win), p->d_win_state, P, j0, p->d_win_cmp);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemcpyAsync(cmp.data(), p->d_win_cmp, cmp.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    return NAGP_OK;
+  };
+  if (P > 1) RUN(check(1, P - 1));
+  bool stale = false;      // the reference of this boundary was rewritten by a re-run
+  for (int j = 1; j < P; ++j) {
+    if (stale) RUN(check(j, 1));
+    double wm = 0.0, wP = 0.0;
+    for (int q = 0; q < B; ++q) {
+      const double a = cmp[((size_t)q * P + j) * 2], c = cmp[((size_t)q * P + j) * 2 + 1];
+      wm = (a == a) ? std::max(wm, a) : INFINITY; wP = (c == c) ? std::max(wP, c) : INFINITY;
+    }
+    p->wstats.boundaries_checked += 1;
+    p->wstats.worst_m = std::max(p->wstats.worst_m, wm); p->wstats.worst_P = std::max(p->wstats.worst_P, wP);
+    stale = !(p->win_tol > 0.0 && wm <= p->win_tol && wP <= p->win_tol);
+    if (stale) {
+      hipLaunchKernelGGL(win_uncount_kernel, dim3((B + 255) / 256), dim3(256), 0, p->stream, sh, p->b, p->d_win_state, P, j, B);
+      HIP_TRY(hipGetLastError());
+      FilterPar fr = fp;
+      fr.k_begin = p->win[j].k_begin; fr.k_end = p->win[j].k_end;
+      RUN(launch_filter(p, fr));
+      p->wstats.reruns += 1;
+    }
+  }
+  return NAGP_OK;
+}
+
 static int exec_gf(nagp_plan* p) {
   const Shape& sh = p->sh; const nagp_opts& o = p->opts; const int I = o.ep_itts, B = p->B;
   const bool nlml = (o.mode == NAGP_MODE_NLML);
@@ -582,6 +686,10 @@ static int exec_gf(nagp_plan* p) {
   const size_t RR = (size_t)B * 8;
   RUN(zero_async(p, p->red_all, (size_t)(I + 2) * RR * sizeof(double)));
   struct RestoreRed { nagp_plan* p; ~RestoreRed() { p->b.red = p->red0; } } restore{p};
+  // windowed plans (nagp_plan_set_windows): the fixed-site pass of the sweeps >= 2 runs in windows; the smoother then starts behind the filter
+  // (the progress counter means "leading steps done", which windows break) and the cross-sweep form, whose next filter follows the
+  // smoother chunk by chunk, is not used
+  const bool windowed = p->win.size() > 1;
   bool xs_pending = false;             // the previous sweep ended in the cross-sweep form: ev_chunk[c] per chunk, ev_red behind everything
   std::vector<ChunkGeom> xs_ch;
   for (int itt = 1; itt <= I; ++itt) {
@@ -610,6 +718,8 @@ static int exec_gf(nagp_plan* p) {
           }
           HIP_TRY(hipStreamWaitEvent(p->stream, p->ev_red, 0));      // (the lZ sum reads lZ[T-1], which the ADF step rewrites; the fixed-site launches in front of it, k_end < T, do not write lZ at all)
           xs_pending = false;
+        } else if (windowed) {
+          RUN(filter_windows(p, fp));
         } else {
           fp.k_end = sh.T - 1;
           RUN(launch_filter(p, fp));
@@ -628,7 +738,7 @@ static int exec_gf(nagp_plan* p) {
       const int ep_clamp = (nlml || mixture_rule(p)) ? 0 : 1, ep_wR = nlml ? 0 : 1;
       double* ep_lZ = mixture_rule(p) ? nullptr : p->b.lZ;   // the mixture variant leaves the clamp to the next filter pass (gf_ep_mods_nmf_mixture.m:195, 280-284)
       const EpRange ep_range = [&](int64_t lo, int64_t hi, hipStream_t st) { return launch_ep(p, o.ep_fraction, ep_damp, ep_clamp, ep_wR, ep_lZ, lo, hi, st); };
-      if (smooth) RUN(sweep_finish(p, sc, itt < I ? &ep_range : nullptr));
+      if (smooth) RUN(sweep_finish(p, sc, (itt < I && !windowed) ? &ep_range : nullptr));
       if (itt < I) {
         if (sc.xs) {
           hipStream_t st = p->s_apply[0];
@@ -843,6 +953,7 @@ extern "C" int nagp_plan_execute(nagp_plan* p) {
   RUN(zero_async(p, p->b.state, (size_t)p->B * ((size_t)sh.ntiles * 16 + sh.S) * 8));
   if (p->d_stamps) RUN(zero_async(p, p->d_stamps, 24 * 8));
   if (p->d_gstamps) RUN(zero_async(p, p->d_gstamps, 32 * 8));
+  p->wstats = nagp_window_stats{};
   std::fill(p->nlZ.begin(), p->nlZ.end(), 0.0);
   std::fill(p->mdM.begin(), p->mdM.end(), 0.0);
   std::fill(p->mdP.begin(), p->mdP.end(), 0.0);
@@ -917,6 +1028,66 @@ extern "C" int nagp_plan_execute(nagp_plan* p) {
 extern "C" int nagp_plan_timings(const nagp_plan* p, nagp_timings* t) {
   if (!p || !t) FAIL(NAGP_EINVAL, "null argument");
   *t = p->tim;
+  return NAGP_OK;
+}
+
+// ---- time-parallel fixed-site filter: the option, its statistics, its geometry (see include/nagp.h)
+extern "C" int nagp_window_partition(int64_t T, int32_t n_windows, int32_t overlap, int64_t* t_start, int64_t* t_warm) {
+  if (T < 1 || overlap < 0 || !t_start || !t_warm) FAIL(NAGP_EINVAL, "bad window partition arguments (T=%lld overlap=%d)", (long long)T, overlap);
+  std::vector<int64_t> ts, tw;
+  const int P = window_partition(T, n_windows, overlap, ts, tw);
+  for (int j = 0; j <= P; ++j) t_start[j] = ts[j];
+  for (int j = 0; j < P; ++j) t_warm[j] = tw[j];
+  return P;
+}
+
+extern "C" int nagp_plan_set_windows(nagp_plan* p, int32_t n_windows, int32_t overlap, double tol) {
+  if (!p) FAIL(NAGP_EINVAL, "null plan");
+  if (n_windows > 1 && p->opts.kind != NAGP_KIND_GF_EP)
+    FAIL(NAGP_EUNSUPPORTED, "windows exist for the fixed-site filter of NAGP_KIND_GF_EP only (the IHGP path is parallel in time already, the EKF pass does not forget its start)");
+  if (overlap < 0 || !(tol >= 0.0)) FAIL(NAGP_EINVAL, "overlap = %d, tol = %g: both must be >= 0", overlap, tol);
+  if (n_windows > 65535) FAIL(NAGP_EINVAL, "n_windows = %d (at most 65535)", n_windows);
+  // (everything above is host checking; from here on the device)
+  HIP_TRY(hipSetDevice(p->opts.device));
+  dfree(p, p->d_win); dfree(p, p->d_win_state); dfree(p, p->d_win_cmp);
+  p->d_win = p->d_win_state = p->d_win_cmp = nullptr;
+  p->win.clear(); p->win_tol = tol;
+  if (n_windows <= 1 || !p->need_PF || p->sh.T <= 2) return NAGP_OK;      // off (or nothing to cut)
+  std::vector<int64_t> ts, tw;
+  const int P = window_partition(p->sh.T, n_windows, overlap, ts, tw);
+  if (P <= 1) return NAGP_OK;
+  std::vector<FilterWin> w((size_t)P);
+  for (int j = 0; j < P; ++j) w[j] = FilterWin{tw[j], ts[j], ts[j + 1], 0, 0};
+  static_assert(sizeof(FilterWin) == 4 * sizeof(double), "FilterWin is stored in a buffer of doubles");
+  int st = dalloc(p, &p->d_win, (size_t)P * 4, false);
+  if (st == NAGP_OK) st = dalloc(p, &p->d_win_state, (size_t)p->B * P * filter_win_doubles(p->sh));
+  if (st == NAGP_OK) st = dalloc(p, &p->d_win_cmp, (size_t)p->B * P * 2);
+  if (st == NAGP_OK) {
+    // the windowed instantiation launch_filter will pick: the same LDS need as its sequential twin
+    const bool split = p->sh.Ms < p->sh.M;
+#define SLW(TP, LBV) (split ? set_lds((gf_filter_kernel<TP, 0, -1, LBV, 0, true, true>), p->lds_filter) : set_lds((gf_filter_kernel<TP, 0, -1, LBV, 0, false, true>), p->lds_filter))
+    if (p->wide_l) st = (p->NT_l <= 768) ? SLW(1, 768) : SLW(1, 1024);
+    else st = (p->TPT_f == 1) ? SLW(1, 512) : (p->TPT_f == 2 ? SLW(2, 512) : SLW(4, 512));
+#undef SLW
+  }
+  if (st == NAGP_OK) {
+    const hipError_t e = hipMemcpy(p->d_win, w.data(), w.size() * sizeof(FilterWin), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { g_last_error = std::string("nagp_plan_set_windows: hipMemcpy -> ") + hipGetErrorString(e); (void)hipGetLastError(); st = NAGP_EHIP; }
+  }
+  if (st != NAGP_OK) {      // leave the option off
+    const std::string keep = g_last_error;
+    dfree(p, p->d_win); dfree(p, p->d_win_state); dfree(p, p->d_win_cmp);
+    p->d_win = p->d_win_state = p->d_win_cmp = nullptr;
+    g_last_error = keep;
+    return st;
+  }
+  p->win = w;
+  return NAGP_OK;
+}
+
+extern "C" int nagp_plan_window_stats(const nagp_plan* p, nagp_window_stats* s) {
+  if (!p || !s) FAIL(NAGP_EINVAL, "null argument");
+  *s = p->wstats;
   return NAGP_OK;
 }
 

@@ -56,6 +56,14 @@
 #define NAGP_LIST_GF_SQ12(P) NAGP_LIST_GF_SQ(P, 1) NAGP_LIST_GF_SQ(P, 2)
 #define NAGP_LIST_GF_SQ34(P) NAGP_LIST_GF_SQ(P, 3) NAGP_LIST_GF_SQ(P, 4)
 
+// time-parallel form of the fixed-site launches (nagp_plan_set_windows): a window index in the grid, warm-up steps that store nothing
+#define NAGP_LIST_GF_WIN_C(P, CPL)                                                                                          \
+  P void nagp::gf_filter_kernel<1, 0, -1, 512, 0, CPL, true> NAGP_SIG_GF; P void nagp::gf_filter_kernel<2, 0, -1, 512, 0, CPL, true> NAGP_SIG_GF;   \
+  P void nagp::gf_filter_kernel<4, 0, -1, 512, 0, CPL, true> NAGP_SIG_GF; P void nagp::gf_filter_kernel<1, 0, -1, 768, 0, CPL, true> NAGP_SIG_GF;   \
+  P void nagp::gf_filter_kernel<1, 0, -1, 1024, 0, CPL, true> NAGP_SIG_GF;
+#define NAGP_LIST_GF_WIN(P) NAGP_LIST_GF_WIN_C(P, false)
+#define NAGP_LIST_GF_WINC(P) NAGP_LIST_GF_WIN_C(P, true)
+
 // EKF and fixed-site filters, smoother kernels
 #define NAGP_LIST_GF_REST(P)                                                                                               \
   P void nagp::gf_filter_kernel<1, 1, 0> NAGP_SIG_GF; P void nagp::gf_filter_kernel<2, 1, 0> NAGP_SIG_GF;                \
@@ -182,4 +190,4 @@
 
 #define NAGP_LIST_ALL(P)                                                                                                   \
   NAGP_LIST_GF_ADF1(P) NAGP_LIST_GF_ADF2(P) NAGP_LIST_GF_ADF3(P) NAGP_LIST_GF_ADF4(P) NAGP_LIST_GF_ADF5(P)               \
-  NAGP_LIST_GF_SP12(P) NAGP_LIST_GF_SP34(P) NAGP_LIST_GF_SQ12(P) NAGP_LIST_GF_SQ34(P) NAGP_LIST_GF_REST(P) NAGP_LIST_SMOOTH(P) NAGP_LIST_SMOOTH8(P) NAGP_LIST_BIG(P) NAGP_LIST_GAINM(P) NAGP_LIST_GAINI(P) NAGP_LIST_EP(P) NAGP_LIST_EPS(P) NAGP_LIST_EPQ(P) NAGP_LIST_IH0(P) NAGP_LIST_IH8(P) NAGP_LIST_IH1(P) NAGP_LIST_IHA(P) NAGP_LIST_IHA8(P) NAGP_LIST_IHA8Q(P) NAGP_LIST_GF_A81(P) NAGP_LIST_GF_A82(P) NAGP_LIST_GF_A83(P) NAGP_LIST_GF_CPL1(P) NAGP_LIST_GF_CPL2(P) NAGP_LIST_GF_CPL4(P) NAGP_LIST_GF_CPLW(P) NAGP_LIST_GAIN_CPL(P)
+  NAGP_LIST_GF_SP12(P) NAGP_LIST_GF_SP34(P) NAGP_LIST_GF_SQ12(P) NAGP_LIST_GF_SQ34(P) NAGP_LIST_GF_REST(P) NAGP_LIST_SMOOTH(P) NAGP_LIST_SMOOTH8(P) NAGP_LIST_BIG(P) NAGP_LIST_GAINM(P) NAGP_LIST_GAINI(P) NAGP_LIST_EP(P) NAGP_LIST_EPS(P) NAGP_LIST_EPQ(P) NAGP_LIST_IH0(P) NAGP_LIST_IH8(P) NAGP_LIST_IH1(P) NAGP_LIST_IHA(P) NAGP_LIST_IHA8(P) NAGP_LIST_IHA8Q(P) NAGP_LIST_GF_A81(P) NAGP_LIST_GF_A82(P) NAGP_LIST_GF_A83(P) NAGP_LIST_GF_CPL1(P) NAGP_LIST_GF_CPL2(P) NAGP_LIST_GF_CPL4(P) NAGP_LIST_GF_CPLW(P) NAGP_LIST_GAIN_CPL(P) NAGP_LIST_GF_WIN(P) NAGP_LIST_GF_WINC(P)

@@ -68,6 +68,14 @@ struct Bufs {
   unsigned long long* counters;  // [B][4]
 };
 
+// One window of a time-parallel fixed-site launch: steps [k_warm, k_begin) are the warm-up -- computed, nothing stored --, steps
+// [k_begin, k_end) store as usual.  seed = 0: start at k_warm from the prior (m = 0, P = Pinf; k_warm = 0 is the true start),
+// seed = 1: continue from the stored (MF, PF) of step k_warm - 1.
+struct FilterWin {
+  int64_t k_warm, k_begin, k_end;
+  int seed, pad;
+};
+
 struct FilterPar {
   int itt;            // 1-based sweep
   double ep_damp;
@@ -98,7 +106,12 @@ struct FilterPar {
                            // 1: rank-M covariance update, 2: PF stores, 4: prediction congruence, 8: W panel writes, 16: mean update
   int cpl_doubles;         // split blocks (Shape::part): doubles of the extra LDS region in FRONT of everything else (filter_cpl_doubles)
   int cpl_chunk;           // ... and the tiles per phase of the exchange (filter_cpl_chunk)
+  // time-parallel fixed-site launches (template parameter WIN; nagp_plan_set_windows): workgroup (pb, blockIdx.y) runs window
+  // win[blockIdx.y] and leaves its state at the end of the warm-up in win_state[pb][blockIdx.y] (filter_win_doubles each)
+  const FilterWin* win;
+  double* win_state;
 };
+
 
 // The filtered covariance is symmetric: PF holds only the lower-triangular tiles, tile (I,J), I >= J, at tile index I(I+1)/2 + J.
 // Layout of ONE step (pf_step_doubles): groups of 64 consecutive tile indices, and inside a group the eight 16-byte pieces of the
@@ -108,6 +121,10 @@ struct FilterPar {
 // step at S = 146 -- profiles/r03_filter_phase_costs.txt).  pf_load returns tile (I,J) of the full matrix (transposing for I < J).
 __host__ __device__ inline int pf_ntiles(const Shape& s) { return s.M * (s.M + 1) / 2; }
 __host__ __device__ inline size_t pf_step_doubles(const Shape& s) { return (size_t)((pf_ntiles(s) + 63) / 64) * 64 * 16; }
+// record of one (problem, window): its state at the end of the warm-up -- the lower tiles of P in the layout of one PF step, then m -- and
+// behind them (filter_win_nan) the NaN observations its stored steps counted (taken back from the counter when the window runs again)
+__host__ __device__ inline size_t filter_win_nan(const Shape& s) { return pf_step_doubles(s) + (((size_t)s.S + 1) & ~(size_t)1); }
+__host__ __device__ inline size_t filter_win_doubles(const Shape& s) { return filter_win_nan(s) + 2; }
 __host__ __device__ inline size_t pf_off(int t, int x) { return ((((size_t)(t >> 6) * 8 + (x >> 1)) * 64) + (t & 63)) * 2 + (x & 1); }
 // (32-bit index arithmetic on purpose: a step holds < 2^16 tiles, and the sequential filters have no scalar registers to spare)
 __device__ __forceinline__ void pf_tile_load(double* t, const double* PFk, int tile) {
@@ -192,8 +209,14 @@ __host__ __device__ inline size_t filter_lds_doubles(const Shape& s, const MomCf
 // CPL: plans with split blocks (Shape::part): the prediction couples the two tile rows of a block -- every thread leaves its tiles in an LDS
 // exchange buffer and forms  P(I,J) <- sum_{a in {I, part I}} sum_{b in {J, part J}} A(I,a) P(a,b) A(J,b)'  from up to four of them --
 // and the tail rows behind the Ms real sites take no part in the site arithmetic (h = 0, sites fixed at zero)
-template <int TPT, int MEAS, int MV, int LB = 512, int SP = 0, bool CPL = false>
+// WIN: time-parallel form of the fixed-site launches (MV = -1): the grid carries a window index in y, the steps come from fp.win[blockIdx.y]
+// (FilterWin).  The warm-up predicate is uniform per workgroup and per ring block and gates stores only (PF tiles, the ring flush, the
+// NaN counter): the arithmetic of a stored step is that of the sequential launch.  A warm-up READS sites (and, with clamp_always, ttau)
+// of steps the window in front of it rewrites at the same time -- with the values they already hold (tnu, R) or with max(ttau, 0), which
+// this kernel applies to what it reads anyway: either value gives the same step.
+template <int TPT, int MEAS, int MV, int LB = 512, int SP = 0, bool CPL = false, bool WIN = false>
 __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg mc, FilterPar fp) {
+  static_assert(!WIN || (MEAS == 0 && MV < 0), "windows exist for the fixed-site launches only");
   extern __shared__ __attribute__((aligned(16))) double lds_raw[];
   double* lds = lds_raw + (CPL ? fp.cpl_doubles : 0);
   const int tid = threadIdx.x, NT = blockDim.x;
@@ -206,6 +229,13 @@ __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg 
   const int64_t T = sh.T;
   const int pb = blockIdx.x;
   const double* mdl = b.model + (size_t)pb * mdl_size(sh);
+  // steps of this workgroup: [kw_first, kw_store) warm-up (WIN only), [kw_store, kw_end) stored
+  int64_t kw_first = fp.k_begin, kw_store = fp.k_begin, kw_end = fp.k_end;
+  bool from_store = fp.k_begin > 0;
+  if constexpr (WIN) {
+    const FilterWin w = fp.win[blockIdx.y];
+    kw_first = w.k_warm; kw_store = w.k_begin; kw_end = w.k_end; from_store = w.seed != 0;
+  }
 
   int* ioff = reinterpret_cast<int*>(lds);          // [MAXM+1]
   int* ibsz = ioff + (MAXM + 1);                     // [MAXM]
@@ -317,8 +347,8 @@ __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg 
   for (int q = 0; q < TPT; ++q) {
     tile_zero(P[q]);
     if (own.ok[q]) {
-      if (fp.k_begin > 0)
-        pf_tile_load(P[q], b.PF + ((size_t)pb * T + (fp.k_begin - 1)) * (size_t)(((nlow + 63) & ~63) * 16), tid + q * NT);
+      if (from_store)
+        pf_tile_load(P[q], b.PF + ((size_t)pb * T + (kw_first - 1)) * (size_t)(((nlow + 63) & ~63) * 16), tid + q * NT);
       else if (fp.init_from_state && !fp.reset_P)
         tile_load(P[q], st + (size_t)(own.I[q] * M + own.J[q]) * 16);
       else if (own.I[q] == own.J[q])
@@ -328,7 +358,7 @@ __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg 
     }
   }
   for (int i = tid; i < S; i += NT)
-    m[i] = (fp.k_begin > 0) ? b.MF[((size_t)pb * T + (fp.k_begin - 1)) * S + i]
+    m[i] = from_store ? b.MF[((size_t)pb * T + (kw_first - 1)) * S + i]
                             : (fp.init_from_state ? st[(size_t)sh.ntiles * 16 + i] : 0.0);
   __syncthreads();
   // State lanes.  The vector work of a step (mean prediction, mean update, the filtered mean's way to the ring) belongs to thread
@@ -394,8 +424,22 @@ __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg 
 #define EKF_STAMP(slot) do { if ((MEAS == 1 || MV == -1) && mc.stamps && tid == 0) { st_b = __builtin_readcyclecounter(); stp[slot] += st_b - st_a; st_a = st_b; } } while (0)
   if (mc.stamps && tid == 0) st_a = __builtin_readcyclecounter();
 
-  for (int64_t k0 = fp.k_begin; k0 < fp.k_end; k0 += KB) {
-    const int nb = (fp.k_end - k0 < KB) ? (int)(fp.k_end - k0) : KB;
+  // the state this window starts its stored steps from (its estimate of (m, P) after step kw_store - 1), for the boundary check
+  auto win_state_store = [&]() {
+    if constexpr (WIN) {
+      double* wst = fp.win_state + ((size_t)pb * gridDim.y + blockIdx.y) * filter_win_doubles(sh);
+#pragma unroll
+      for (int q = 0; q < TPT; ++q)
+        if (own.ok[q]) pf_tile_store(wst, tid + q * NT, P[q]);
+      for (int i = tid; i < S; i += NT) wst[(size_t)pf_tiles * 16 + i] = m[i];
+    }
+  };
+  if constexpr (WIN) { if (kw_first == kw_store) win_state_store(); }      // (no warm-up: the seed itself)
+
+  for (int64_t k0 = kw_first; k0 < kw_end;) {
+    const bool warm = WIN && k0 < kw_store;      // uniform over the workgroup and over the ring block
+    const int64_t k_lim = warm ? kw_store : kw_end;
+    const int nb = (k_lim - k0 < KB) ? (int)(k_lim - k0) : KB;
     // ---- fill the ring
     for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
     if (MEAS == 0)
@@ -857,7 +901,7 @@ __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg 
           }
         }
       } else {
-        ++n_nan;
+        if (!warm) ++n_nan;
       }
       EKF_STAMP(6);   // (P -= K S K')
       // ---- per-step outputs -> ring ; covariance tiles -> HBM
@@ -869,7 +913,7 @@ __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg 
       for (int q = 0; q < TPT; ++q)
         if (own.ok[q] && own.I[q] == own.J[q])
           rfv[kk * M + own.I[q]] = shv[own.I[q]] * shv[own.I[q]] * P[q][0];
-      if (g_PF && !(fp.dbg & 2)) {
+      if (g_PF && !(fp.dbg & 2) && !warm) {
 #pragma unroll
         for (int q = 0; q < TPT; ++q)
           if (own.ok[q]) pf_tile_store(g_PF + (size_t)k * pf_tiles * 16, tid + q * NT, P[q]);   // lower tile index == ownership index
@@ -877,6 +921,12 @@ __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg 
       lds_barrier();  // B5
       EKF_STAMP(7);   // (outputs, PF stores, B5)
       if (mc.stamps && tid == 0 && do_mom) { st_b = __builtin_readcyclecounter(); stp[5] += st_b - st_a; st_a = st_b; }
+    }
+    if (warm) {      // a warm-up block stores nothing; the last one leaves (m, P) for the boundary check
+      if (k0 + nb == kw_store) win_state_store();
+      __syncthreads();
+      k0 += nb;
+      continue;
     }
     // ---- flush the ring
     if constexpr (MEAS == 0 && MV >= 0) {
@@ -894,14 +944,18 @@ __global__ void __launch_bounds__(LB) gf_filter_kernel(Shape sh, Bufs b, MomCfg 
       g_fm[(size_t)k0 * M + i] = rfm[i]; g_fv[(size_t)k0 * M + i] = rfv[i];
     }
     for (int i = tid; i < nb * S; i += NT) g_MF[(size_t)k0 * S + i] = rMF[i];
-    const bool publish = fp.progress && ((k0 + nb) / fp.progress_every != k0 / fp.progress_every || k0 + nb == fp.k_end);
+    const bool publish = fp.progress && ((k0 + nb) / fp.progress_every != k0 / fp.progress_every || k0 + nb == kw_end);
     if (publish) __threadfence_system();      // this thread's stores (its PF tiles, its share of the flush) before the flag
     __syncthreads();
     if (publish && tid == 0)
       __hip_atomic_store(&fp.progress[pb], (unsigned long long)(k0 + nb), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    k0 += WIN ? nb : KB;
   }
   if (tid < M && n_clamped) atomicAdd(&b.counters[(size_t)pb * 4 + 1], n_clamped);
   if (tid == 0 && n_nan) atomicAdd(&b.counters[(size_t)pb * 4 + 2], n_nan);
+  if constexpr (WIN) {
+    if (tid == 0) fp.win_state[((size_t)pb * gridDim.y + blockIdx.y) * filter_win_doubles(sh) + filter_win_nan(sh)] = (double)n_nan;
+  }
   if (mc.stamps && tid == 0)
     for (int i = 0; i < 8; ++i) mc.stamps[i] += stp[i];
 }

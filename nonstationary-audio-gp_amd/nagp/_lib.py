@@ -59,11 +59,16 @@ class Timings(C.Structure):
     _fields_ = [('ms', C.c_double * N_KERNELS), ('launches', C.c_int64 * N_KERNELS), ('total_ms', C.c_double)]
 
 
+class WindowStats(C.Structure):
+    _fields_ = [('windows_run', C.c_int64), ('boundaries_checked', C.c_int64), ('reruns', C.c_int64), ('warmup_steps', C.c_int64),
+                ('worst_m', C.c_double), ('worst_P', C.c_double)]
+
+
 EXPORTS = ['nagp_version', 'nagp_device_count', 'nagp_strerror', 'nagp_last_error', 'nagp_ep_run',
            'nagp_ihgp_run', 'nagp_giekf_run', 'nagp_plan_create', 'nagp_plan_upload_y', 'nagp_plan_execute',
            'nagp_plan_timings', 'nagp_plan_download', 'nagp_plan_device_bytes', 'nagp_plan_destroy', 'nagp_plan_upload_sites',
            'nagp_batch_partition', 'nagp_batch_run', 'nagp_shutdown', 'nagp_reconstruct', 'nagp_mom_eval', 'nagp_iekf_update1', 'nagp_fastfb_run',
-           'nagp_giekf_nlml_grad']
+           'nagp_giekf_nlml_grad', 'nagp_plan_set_windows', 'nagp_plan_window_stats', 'nagp_window_partition']
 
 
 class NagpError(RuntimeError):
@@ -211,6 +216,9 @@ def lib():
     L.nagp_plan_download.argtypes = [C.c_void_p, C.POINTER(Out)]
     L.nagp_plan_device_bytes.argtypes = [C.c_void_p]; L.nagp_plan_device_bytes.restype = C.c_int64
     L.nagp_plan_destroy.argtypes = [C.c_void_p]; L.nagp_plan_destroy.restype = None
+    L.nagp_plan_set_windows.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_double]; L.nagp_plan_set_windows.restype = C.c_int
+    L.nagp_plan_window_stats.argtypes = [C.c_void_p, C.POINTER(WindowStats)]; L.nagp_plan_window_stats.restype = C.c_int
+    L.nagp_window_partition.argtypes = [C.c_int64, C.c_int32, C.c_int32, c_lp, c_lp]; L.nagp_window_partition.restype = C.c_int
     for f in ('nagp_plan_upload_sites', 'nagp_batch_partition', 'nagp_batch_run', 'nagp_ep_run', 'nagp_ihgp_run', 'nagp_giekf_run', 'nagp_mom_eval', 'nagp_iekf_update1', 'nagp_fastfb_run', 'nagp_plan_create', 'nagp_plan_upload_y',
               'nagp_plan_execute', 'nagp_plan_timings', 'nagp_plan_download'):
         getattr(L, f).restype = C.c_int

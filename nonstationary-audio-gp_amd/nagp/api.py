@@ -261,8 +261,28 @@ def _unpack_constraints(w, w_fixed, tune_hypers, constraints, num_lik_params, D,
     return lik_param, np.concatenate(groups[:3]), np.concatenate(groups[3:]), Wnmf
 
 
+# Defaults of the time-parallel fixed-site filter (nagp_plan_set_windows).  The tolerance is on the state a window starts from; the EP sweeps
+# behind it can amplify that (1.7e3 measured on the 32-channel segment over two sweeps: profiles/r07_windows.txt), and 1e-10 keeps the outputs
+# within the 1e-7 the suite asks of the marginals.  The overlap is the warm-up after which the restarted filter is at least a decade below
+# that on the four-state models of profiles/r07_window_contraction.txt (six-state sub-bands need 12 000); sequences shorter than
+# windows * overlap gain nothing from the option.
+WINDOW_OVERLAP = 8000
+WINDOW_TOL = 1e-10
+
+
+def check_windows(kind, windows, window_overlap, window_tol):
+    """The host checks of nagp_plan_set_windows, made before anything touches a device."""
+    if windows is None or int(windows) <= 1:
+        return
+    if kind != L.KIND_GF_EP:
+        raise L.NagpError('libnagp: unsupported shape (%d): windows exist for the fixed-site filter of KIND_GF_EP only' % -2)
+    if int(window_overlap) < 0 or not float(window_tol) >= 0.0:
+        raise L.NagpError('libnagp: invalid argument (%d): window_overlap and window_tol must be >= 0' % -1)
+
+
 def _run_gf(blk, Wnmf, lik_param, yall, return_ind, mom, ep_fraction, ep_damping, ep_itts, predict, nargout,
-            predict_at_k1=0, device=0, flags=0):
+            predict_at_k1=0, device=0, flags=0, windows=None):
+    check_windows(L.KIND_GF_EP, windows, WINDOW_OVERLAP, WINDOW_TOL)
     prob = _Problem(blk, Wnmf, lik_param)
     dim = blk.D if mom.kind == L.LIK_POWER else blk.N
     damp = _damping(ep_damping, ep_itts)
@@ -270,40 +290,56 @@ def _run_gf(blk, Wnmf, lik_param, yall, return_ind, mom, ep_fraction, ep_damping
     opts, keep = make_opts(L.KIND_GF_EP, L.MODE_PREDICT if predict else L.MODE_NLML, mom, dim, ep_fraction, damp,
                            ep_itts, predict_at_k1=predict_at_k1, flags=flags | (L.FLAG_WANT_PS if want_PS else 0), device=device)
     out = _Outputs(blk.M, blk.S, yall.size, ep_itts, want_PS=want_PS)
-    L.check(L.lib().nagp_ep_run(C.byref(prob.model), L.dptr(yall), yall.size, C.byref(opts), C.byref(out.c)))
+    if windows is None:
+        L.check(L.lib().nagp_ep_run(C.byref(prob.model), L.dptr(yall), yall.size, C.byref(opts), C.byref(out.c)))
+        return out
+    # windows asked for: the same steps as nagp_ep_run through a plan of one problem, with the option set (default overlap and tolerance)
+    lib = L.lib(); h = C.c_void_p()
+    L.check(lib.nagp_plan_create(C.byref(h), 1, C.byref(prob.model), None, yall.size, C.byref(opts)))
+    try:
+        L.check(lib.nagp_plan_set_windows(h, int(windows), WINDOW_OVERLAP, WINDOW_TOL))
+        L.check(lib.nagp_plan_upload_y(h, (L.c_dp * 1)(L.dptr(yall))))
+        L.check(lib.nagp_plan_execute(h))
+        L.check(lib.nagp_plan_download(h, C.byref(out.c)))
+        ws = L.WindowStats(); L.check(lib.nagp_plan_window_stats(h, C.byref(ws)))
+        out.window_stats = dict(windows_run=int(ws.windows_run), boundaries_checked=int(ws.boundaries_checked), reruns=int(ws.reruns),
+                                warmup_steps=int(ws.warmup_steps), worst_m=float(ws.worst_m), worst_P=float(ws.worst_P))
+    finally:
+        lib.nagp_plan_destroy(h)
     return out
 
 
 def gf_ep_modulator_nmf(w, x, y, ss, mom, xt=None, kernel1='matern32', kernel2='matern52', num_lik_params=1, D=None, N=None,
-                        ep_fraction=0.5, ep_damping=None, ep_itts=30, nargout=2, device=0):
-    """[Eft,Varft,Covft,lb,ub,out] (xt given) or [e,eg] (xt empty) -- matlab/gf_ep_modulator_nmf.m:1."""
+                        ep_fraction=0.5, ep_damping=None, ep_itts=30, nargout=2, device=0, windows=None):
+    """[Eft,Varft,Covft,lb,ub,out] (xt given) or [e,eg] (xt empty) -- matlab/gf_ep_modulator_nmf.m:1.
+    windows > 1: the fixed-site filter of the sweeps >= 2 in that many windows at the same time (Plan, nagp_plan_set_windows)."""
     yall, return_ind = _merge_inputs(x, y, xt)
     lik_param, p1, p2, Wnmf = _unpack_log(w, num_lik_params, D, N)
     blk = _blocks_from_dense(*ss(x, p1, p2, kernel1, kernel2), D, N)           # balance OFF (:80 `if false`)
     predict = xt is not None and np.size(xt) > 0
-    out = _run_gf(blk, Wnmf, lik_param, yall, return_ind, mom, ep_fraction, ep_damping, ep_itts, predict, nargout, device=device)
+    out = _run_gf(blk, Wnmf, lik_param, yall, return_ind, mom, ep_fraction, ep_damping, ep_itts, predict, nargout, device=device, windows=windows)
     if predict:
         return _returns(out, return_ind, nargout)
     return float(out.nlZ[0]), np.zeros(np.size(w))                             # eg is all zeros (:363, :531)
 
 
 def gf_ep_modulator_nmf_constraints(w, x, y, ss, mom, xt, kernel1, kernel2, num_lik_params, D, N, ep_fraction, ep_damping,
-                                    ep_itts, constraints, w_fixed, tune_hypers, nargout=2, device=0):
-    """matlab/gf_ep_modulator_nmf_constraints.m:1-2 (sigmoid-constrained parameters, balance ON :115)."""
+                                    ep_itts, constraints, w_fixed, tune_hypers, nargout=2, device=0, windows=None):
+    """matlab/gf_ep_modulator_nmf_constraints.m:1-2 (sigmoid-constrained parameters, balance ON :115).  windows: see gf_ep_modulator_nmf."""
     yall, return_ind = _merge_inputs(x, y, xt)
     lik_param, p1, p2, Wnmf = _unpack_constraints(w, w_fixed, tune_hypers, constraints, num_lik_params, D, N)
     blk = ssm.balance_blocks(_blocks_from_dense(*ss(x, p1, p2, kernel1, kernel2), D, N))
     predict = xt is not None and np.size(xt) > 0
-    out = _run_gf(blk, Wnmf, lik_param, yall, return_ind, mom, ep_fraction, ep_damping, ep_itts, predict, nargout, device=device)
+    out = _run_gf(blk, Wnmf, lik_param, yall, return_ind, mom, ep_fraction, ep_damping, ep_itts, predict, nargout, device=device, windows=windows)
     if predict:
         return _returns(out, return_ind, nargout)
     return float(out.nlZ[0]), np.zeros(np.size(w))
 
 
 def gf_ep_modulator(w, x, y, ss, mom, xt=None, kernel1='matern32', kernel2='matern52', num_lik_params=1,
-                    ep_fraction=0.5, ep_damping=None, ep_itts=30, nargout=2, device=0):
+                    ep_fraction=0.5, ep_damping=None, ep_itts=30, nargout=2, device=0, windows=None):
     """matlab/gf_ep_modulator.m:1 (one modulator per sub-band; balance ON :75; predicts at k=1 in
-    predict mode :131-133)."""
+    predict mode :131-133).  windows: see gf_ep_modulator_nmf."""
     yall, return_ind = _merge_inputs(x, y, xt)
     w = np.asarray(w, float).ravel()
     lik_param = w[:num_lik_params]; param = np.exp(w[num_lik_params:])
@@ -311,7 +347,7 @@ def gf_ep_modulator(w, x, y, ss, mom, xt=None, kernel1='matern32', kernel2='mate
     blk = ssm.balance_blocks(_blocks_from_dense(*ss(x, param, kernel1, kernel2), D, D))
     predict = xt is not None and np.size(xt) > 0
     out = _run_gf(blk, None, lik_param, yall, return_ind, mom, ep_fraction, ep_damping, ep_itts, predict, nargout,
-                  predict_at_k1=1, device=device)
+                  predict_at_k1=1, device=device, windows=windows)
     if predict:
         return _returns(out, return_ind, nargout)
     return float(out.nlZ[0]), np.zeros(np.size(w))
@@ -385,7 +421,7 @@ def _mixture_mom(mom):
 
 
 def gf_ep_mods_nmf_mixture(w, x, y, ss, mom, xt, kernel1, kernel2, J, ep_fraction=0.5, ep_damping=0.1, ep_itts=30,
-                           nargout=2, device=0):
+                           nargout=2, device=0, windows=None):
     """matlab/experiments/gf_ep_mods_nmf_mixture.m:1 -- source separation: J stacked GT-NMF models, the older
     Power-EP rule (mom at power ep_fraction in the filter too, d/ep_fraction scaling, clamp in the filter pass,
     NAGP_FLAG_MIXTURE_RULE).  `mom` is the usual Mom object; its ep_frac argument is bound to ep_fraction as the
@@ -395,7 +431,7 @@ def gf_ep_mods_nmf_mixture(w, x, y, ss, mom, xt, kernel1, kernel2, J, ep_fractio
     yall, return_ind = _merge_inputs(x, y, xt)
     blk, Wnmf, lik_param = _stack_sources(ss, x, w, kernel1, kernel2, J)
     out = _run_gf(blk, Wnmf, lik_param, yall, return_ind, _mixture_mom(mom), ep_fraction, float(np.ravel(ep_damping)[0]), ep_itts,
-                  True, nargout, device=device, flags=L.FLAG_MIXTURE_RULE)
+                  True, nargout, device=device, flags=L.FLAG_MIXTURE_RULE, windows=windows)
     return _returns(out, return_ind, nargout)
 
 

@@ -5,15 +5,29 @@ import ctypes as C
 import numpy as np
 
 from . import _lib as L
-from .api import _Outputs, _Problem, make_opts, _damping
+from .api import _Outputs, _Problem, make_opts, _damping, check_windows, WINDOW_OVERLAP, WINDOW_TOL
 from . import ihgp_tables
+
+
+def window_partition(T, windows, overlap):
+    """nagp_window_partition: (t_start[P + 1], t_warm[P]) of the P = min(windows, T - 1) windows of the fixed-site pass over [0, T - 1)."""
+    n = max(int(windows), 1)
+    ts = np.zeros(n + 1, dtype=np.int64); tw = np.zeros(n, dtype=np.int64)
+    P = L.lib().nagp_window_partition(int(T), int(windows), int(overlap), ts.ctypes.data_as(L.c_lp), tw.ctypes.data_as(L.c_lp))
+    if P < 0:
+        L.check(P)
+    return ts[:P + 1].copy(), tw[:P].copy()
 
 
 class Plan:
     def __init__(self, kind, problems, T, mom=None, ep_fraction=0.5, ep_damping=None, ep_itts=3, mode=L.MODE_PREDICT,
-                 l_iter=1, predict_at_k1=0, flags=0, device=0, chunk=0):
+                 l_iter=1, predict_at_k1=0, flags=0, device=0, chunk=0, windows=None, window_overlap=WINDOW_OVERLAP, window_tol=WINDOW_TOL):
         """problems: list of (BlockSS, Wnmf, lik_param[, overrides]) -- already balanced if the variant balances; `overrides` is an
-        optional dict of dense S x S arrays 'A', 'Q', 'Pinf' replacing the discretised blocks (block diagonal with the same blocks)."""
+        optional dict of dense S x S arrays 'A', 'Q', 'Pinf' replacing the discretised blocks (block diagonal with the same blocks).
+        windows > 1: the fixed-site filter of the sweeps >= 2 runs in that many windows at the same time (KIND_GF_EP; see
+        nagp_plan_set_windows in include/nagp.h: warm-up of window_overlap steps, boundaries checked against window_tol, re-run where
+        they miss it).  None: the call is never made."""
+        check_windows(kind, windows, window_overlap, window_tol)
         self.kind, self.T, self.I = kind, int(T), int(ep_itts)
         sym = kind == L.KIND_IHGP
         statq = kind == L.KIND_GIEKF and mode == L.MODE_NLML        # Q = Pinf - A Pinf A' (gf_giekf_modulator_nmf_constraints.m:378)
@@ -41,6 +55,22 @@ class Plan:
             tabs_arr = (L.IhgpTables * self.B)(*tl)
         self._h = C.c_void_p()
         L.check(L.lib().nagp_plan_create(C.byref(self._h), self.B, models, tabs_arr, self.T, C.byref(self.opts)))
+        if windows is not None:
+            self.set_windows(windows, window_overlap, window_tol)
+
+    def set_windows(self, windows, overlap=WINDOW_OVERLAP, tol=WINDOW_TOL):
+        """nagp_plan_set_windows; windows <= 1 turns the option off again."""
+        st = L.lib().nagp_plan_set_windows(self._h, int(windows), int(overlap), float(tol))
+        if st != L.NAGP_OK:
+            self.close()
+            L.check(st)
+
+    def window_stats(self):
+        """What the windows of the last execute did (nagp_plan_window_stats), as a dict."""
+        s = L.WindowStats()
+        L.check(L.lib().nagp_plan_window_stats(self._h, C.byref(s)))
+        return dict(windows_run=int(s.windows_run), boundaries_checked=int(s.boundaries_checked), reruns=int(s.reruns),
+                    warmup_steps=int(s.warmup_steps), worst_m=float(s.worst_m), worst_P=float(s.worst_P))
 
     def upload(self, ys):
         ys = [L.f64(y, 'C') for y in ys]
