@@ -240,6 +240,45 @@ int nagp_reconstruct(int32_t D, int32_t N, int64_t T, const double* Eft, const d
                      int32_t link_kind, double link_shift, int32_t n_gh, const double* gh_x, const double* gh_w,
                      int32_t n_samples, uint64_t seed, double* Esig, double* Vsig, double* Eft_mod, double* Varft_mod, int32_t device);
 
+/* The same post-processing as the experiment scripts write it (experiments/noise_reduction_speech.m:142, missing_data_music.m:173,
+ * test_missing_data.m:159, synthetic_data_experiment.m:221, source_sep_piano.m:165-244): an amplitude kind -- a_d = W_d.lk (the demos,
+ * nagp_reconstruct) or a_d = sqrt(W_d.lk) (the model of NAGP_LIK_POWER_NMF_SQRT), lk = link(g) --, a partition of the sub-bands into
+ * J sources and the envelopes.  Under the independent marginals of every step (as above)
+ *     sig = sum_d a_d z_d,   sig_j = sum_{d in source j} a_d z_d,   env_d = a_d
+ * and the outputs are Esig / Vsig (T), Esrc / Vsrc (J x T: Esig1..3 / Vsig1..3 of source_sep_piano.m:229-234), Eenv (D x T: `envs`, :218,
+ * :225) and Eft_mod / Varft_mod (N x T) as in nagp_reconstruct.  sig is summed on its own, not as sum_j sig_j.
+ * n_samples >= 2: the scripts' estimator (mean, var with s-1, Eenv = mean over the draws) on the draws of nagp_reconstruct (same generator,
+ *   same counters: with NAGP_AMP_LINEAR and one source Esig, Vsig, Eft_mod, Varft_mod are those of nagp_reconstruct).
+ * n_samples = 0: the population values.  Eft_mod / Varft_mod from the 1-D rule gh_x, gh_w (exp link: closed form).  NAGP_AMP_LINEAR: the
+ *   closed forms of nagp_reconstruct restricted to each source, Eenv = W E lk.  NAGP_AMP_SQRT: E a_d^2 = W_d.E lk is exact from the 1-D
+ *   rule; E a_d and the moments of u_j(g) = sum_{d in j} a_d(g) Eft_d come from the caller's N-dimensional rule (wn, xn_unscaled: unit
+ *   points for the standard normal weight, as in nagp_opts; g_n = Eft_n + sqrt(Varft_n) x_n):
+ *     Esig_j = E u_j,   Vsig_j = sum_{d in j} (W_d.E lk) Varft_d + E u_j^2 - (E u_j)^2,
+ *   the last difference accumulated about u_j at the centre g = Eft (exact for weights of any sum).
+ * A negative W_d.lk under NAGP_AMP_SQRT gives NaN in that sub-band's envelope, its source and the total (MATLAB goes complex there).
+ * N <= 9, D + N <= 64, J <= 8.  NAGP_EINVAL (host checks, before any device call): NULL inputs, bad sizes, unknown amp / link kind,
+ * n_samples < 0 or == 1, source_offsets not 0 = off[0] < ... < off[J] = D (NULL only with J = 1), population form without the rule
+ * it needs (softplus: the 1-D rule; NAGP_AMP_SQRT: the N-dimensional rule), every pointer of `out` NULL. */
+typedef enum nagp_amp { NAGP_AMP_LINEAR = 0, NAGP_AMP_SQRT = 1 } nagp_amp;
+typedef struct nagp_recon_opts {
+  int32_t amp_kind;                 /* nagp_amp */
+  int32_t link_kind; double link_shift;
+  int32_t n_sources;                /* J >= 1 */
+  const int32_t* source_offsets;    /* J+1 ascending, [0] = 0, [J] = D: source j owns sub-bands [off[j], off[j+1]); NULL only with J = 1 */
+  int32_t n_samples; uint64_t seed; /* >= 2: sampling form; 0: population form */
+  int32_t n_gh; const double* gh_x; const double* gh_w;                 /* 1-D rule, population form */
+  int32_t n_pts; const double* wn; const double* xn_unscaled;           /* N x n_pts rule (as nagp_opts), population form with NAGP_AMP_SQRT */
+  int32_t device;
+} nagp_recon_opts;
+typedef struct nagp_recon_out {     /* caller-allocated, any pointer may be NULL */
+  double *Esig, *Vsig;              /* T */
+  double *Esrc, *Vsrc;              /* J x T column-major */
+  double *Eenv;                     /* D x T: mean amplitude a_d (source_sep_piano.m:218,225) */
+  double *Eft_mod, *Varft_mod;      /* N x T */
+} nagp_recon_out;
+int nagp_reconstruct_sources(int32_t D, int32_t N, int64_t T, const double* Eft, const double* Varft, const double* Wnmf,
+                             const nagp_recon_opts* opts, nagp_recon_out* out);
+
 /* Batched / device-resident form: n_problems independent problems of identical shape
  * (S, M, block structure, T) -- audio segments or hyper-parameter replicas -- run concurrently. */
 int nagp_plan_create(nagp_plan** plan, int32_t n_problems, const nagp_model* models,

@@ -21,6 +21,9 @@
  *   [MS, sum_v2] = nagp_mex('fastfb', A, AKHA, HA, K, G ([] = filter only), y [,device])                       nagp_fastfb_run
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
+ *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
+ *                                    ropts struct: amp_kind, link_kind, link_shift, source_offsets (int32, 0-based, J+1 entries; [] = one source),
+ *                                    n_samples, seed, gh_x, gh_w, wn, xn_unscaled, device                      -> nagp_recon_opts
  *   [nlZ_total, Eft, Varft, nlZ] = nagp_mex('batch', models {cell of model structs}, ys {cell}, opts, n_gpus [, tables {cell}])
  *                                    Eft, Varft, nlZ: cells, one entry per problem                             nagp_batch_run
  *   [e, g] = nagp_mex('giekf_grad', model, y, dA, dQ, dPinf, dR, hess, w_index, w_direct [,device])            nagp_giekf_nlml_grad
@@ -214,6 +217,41 @@ static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* 
   for (i = 1; i < 4; ++i) if (nlhs > i) plhs[i] = o[i];
 }
 
+static void cmd_reconstruct_sources(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('reconstruct_sources', Eft, Varft, Wnmf, ropts) -> [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod]  (source_sep_piano.m:165-244, noise_reduction_speech.m:142);
+     only the outputs asked for are computed (the others stay NULL in nagp_recon_out) */
+  size_t n, nv, ng, nw, nx, D, N, M, T, J = 1; const double *E, *V, *W; const mxArray* f; nagp_recon_opts o; nagp_recon_out r; double* p[7]; int i;
+  if (nrhs != 5 || nlhs > 7) mexErrMsgIdAndTxt("nagp:arg", "usage: [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources',Eft,Varft,Wnmf,ropts)");
+  E = dvec(prhs[1], "Eft", &n); V = dvec(prhs[2], "Varft", &nv); W = dvec(prhs[3], "Wnmf", NULL);
+  M = mxGetM(prhs[1]); D = mxGetM(prhs[3]); N = D ? mxGetNumberOfElements(prhs[3]) / D : 0;
+  if (!E || !V || !W || n != nv || M != D + N) mexErrMsgIdAndTxt("nagp:arg", "Eft, Varft must be (D+N) x T for Wnmf of D x N");
+  T = n / M;
+  memset(&o, 0, sizeof o); memset(&r, 0, sizeof r);
+  o.amp_kind = (int32_t)scalar_or(prhs[4], "amp_kind", NAGP_AMP_SQRT);
+  o.link_kind = (int32_t)scalar_or(prhs[4], "link_kind", NAGP_LINK_SOFTPLUS);
+  o.link_shift = scalar_or(prhs[4], "link_shift", 0.0);
+  f = field(prhs[4], "source_offsets", 0);
+  if (f && !mxIsEmpty(f)) {
+    if (!mxIsInt32(f) || mxGetNumberOfElements(f) < 2) mexErrMsgIdAndTxt("nagp:arg", "source_offsets must be int32 with J+1 entries");
+    J = mxGetNumberOfElements(f) - 1; o.source_offsets = (const int32_t*)mxGetData(f);
+  }
+  o.n_sources = (int32_t)J;
+  o.n_samples = (int32_t)scalar_or(prhs[4], "n_samples", 0); o.seed = (uint64_t)scalar_or(prhs[4], "seed", 0);
+  o.gh_x = doubles(prhs[4], "gh_x", 0, &ng); o.gh_w = doubles(prhs[4], "gh_w", 0, &nw);
+  if (ng != nw) mexErrMsgIdAndTxt("nagp:arg", "gh_x and gh_w must have the same length");
+  o.n_gh = (int32_t)ng;
+  o.wn = doubles(prhs[4], "wn", 0, &nw); o.xn_unscaled = doubles(prhs[4], "xn_unscaled", 0, &nx);
+  if (nx != nw * N) mexErrMsgIdAndTxt("nagp:arg", "xn_unscaled must be N x numel(wn)");
+  o.n_pts = (int32_t)nw;
+  o.device = (int32_t)scalar_or(prhs[4], "device", 0);
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) {
+    plhs[i] = mxCreateDoubleMatrix(i < 2 ? 1 : (i < 4 ? J : (i == 4 ? D : N)), T, mxREAL); p[i] = mxGetPr(plhs[i]);
+  }
+  for (; i < 7; ++i) p[i] = NULL;
+  r.Esig = p[0]; r.Vsig = p[1]; r.Esrc = p[2]; r.Vsrc = p[3]; r.Eenv = p[4]; r.Eft_mod = p[5]; r.Varft_mod = p[6];
+  fail_if(nagp_reconstruct_sources((int32_t)D, (int32_t)N, (int64_t)T, E, V, W, &o, &r));
+}
+
 static void cmd_batch(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('batch', models {cell}, ys {cell}, opts, n_gpus [, tables {cell}]) -> [nlZ_total, Eft {cell}, Varft {cell}, nlZ {cell}]
      segments / objective replicas spread over the GPUs of the node, nlZ all-reduced with RCCL (nagp_batch_run) */
@@ -267,6 +305,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!strcmp(cmd, "iekf_update1")) cmd_iekf_update1(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fastfb")) cmd_fastfb(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "giekf_grad")) cmd_giekf_grad(nlhs, plhs, nrhs, prhs);
     else mexErrMsgIdAndTxt("nagp:arg", "unknown command '%s'", cmd);

@@ -431,3 +431,78 @@ extern "C" int nagp_reconstruct(int32_t D, int32_t N, int64_t T, const double* E
   return st;
 }
 
+// the experiment scripts' form of the same post-processing: amplitude kind, sources, envelopes (see include/nagp.h, nagp_recon.hpp)
+extern "C" int nagp_reconstruct_sources(int32_t D, int32_t N, int64_t T, const double* Eft, const double* Varft, const double* Wnmf,
+                                        const nagp_recon_opts* o, nagp_recon_out* out) {
+  if (!Eft || !Varft || !Wnmf || !o || !out) FAIL(NAGP_EINVAL, "null argument");
+  if (D < 1 || N < 1 || N > MOM_MAXCD || D + N > MAXM || T < 1) FAIL(NAGP_EINVAL, "bad sizes (D=%d N=%d T=%lld)", D, N, (long long)T);
+  if (o->amp_kind != NAGP_AMP_LINEAR && o->amp_kind != NAGP_AMP_SQRT) FAIL(NAGP_EINVAL, "unknown amplitude kind");
+  if (o->link_kind != NAGP_LINK_SOFTPLUS && o->link_kind != NAGP_LINK_EXP) FAIL(NAGP_EINVAL, "unknown link");
+  const int J = o->n_sources;
+  if (J < 1 || J > RECON_MAXSRC || J > D) FAIL(NAGP_EINVAL, "bad number of sources (%d)", J);
+  if (!o->source_offsets && J > 1) FAIL(NAGP_EINVAL, "source_offsets missing");
+  int off[RECON_MAXSRC + 1] = {0};
+  off[J] = D;
+  if (o->source_offsets) {
+    for (int j = 0; j <= J; ++j) off[j] = o->source_offsets[j];
+    if (off[0] != 0 || off[J] != D) FAIL(NAGP_EINVAL, "source_offsets must start at 0 and end at D");
+    for (int j = 0; j < J; ++j) if (off[j + 1] <= off[j]) FAIL(NAGP_EINVAL, "source_offsets must be strictly ascending");
+  }
+  if (o->n_samples < 0 || o->n_samples == 1) FAIL(NAGP_EINVAL, "sampling needs at least two draws");
+  const bool sampling = o->n_samples > 0, sq = o->amp_kind == NAGP_AMP_SQRT;
+  if (!sampling && o->link_kind == NAGP_LINK_SOFTPLUS && (o->n_gh < 1 || o->n_gh > 256 || !o->gh_x || !o->gh_w)) FAIL(NAGP_EINVAL, "Gauss-Hermite rule missing");
+  if (!sampling && sq && (o->n_pts < 1 || o->n_pts > (1 << 20) || !o->wn || !o->xn_unscaled)) FAIL(NAGP_EINVAL, "N-dimensional rule missing");
+  if (!out->Esig && !out->Vsig && !out->Esrc && !out->Vsrc && !out->Eenv && !out->Eft_mod && !out->Varft_mod) FAIL(NAGP_EINVAL, "no output wanted");
+  if (hipSetDevice(o->device) != hipSuccess) FAIL(NAGP_EHIP, "hipSetDevice(%d)", o->device);
+  const int M = D + N;
+  const size_t nW = (size_t)D * N, nMT = (size_t)M * T, ngh = (!sampling && o->link_kind == NAGP_LINK_SOFTPLUS) ? (size_t)o->n_gh : 0,
+               npt = (!sampling && sq) ? (size_t)o->n_pts : 0;
+  // outputs that are not wanted get no buffer: the kernels skip a NULL pointer
+  const size_t n_es = out->Esig ? T : 0, n_vs = out->Vsig ? T : 0, n_ej = out->Esrc ? (size_t)J * T : 0, n_vj = out->Vsrc ? (size_t)J * T : 0,
+               n_en = out->Eenv ? (size_t)D * T : 0, n_em = out->Eft_mod ? (size_t)N * T : 0, n_vm = out->Varft_mod ? (size_t)N * T : 0;
+  const size_t o_W = 0, o_E = o_W + nW, o_V = o_E + nMT, o_gx = o_V + nMT, o_gw = o_gx + ngh, o_wn = o_gw + ngh, o_xn = o_wn + npt,
+               o_es = o_xn + npt * N, o_vs = o_es + n_es, o_ej = o_vs + n_vs, o_vj = o_ej + n_ej, o_en = o_vj + n_vj, o_em = o_en + n_en,
+               o_vm = o_em + n_em, o_off = o_vm + n_vm, total = o_off + (RECON_MAXSRC + 2) / 2;
+  double* dev = nullptr;
+  if (hipMalloc(&dev, total * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", total * sizeof(double)); }
+  std::vector<double> Wr(nW);
+  for (int d = 0; d < D; ++d)
+    for (int j = 0; j < N; ++j) Wr[(size_t)d * N + j] = Wnmf[d + (size_t)D * j];
+  int st = NAGP_OK;
+#define RC_HIP(x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string("nagp_reconstruct_sources: " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
+  RC_HIP(hipMemcpy(dev + o_W, Wr.data(), nW * 8, hipMemcpyHostToDevice));
+  RC_HIP(hipMemcpy(dev + o_E, Eft, nMT * 8, hipMemcpyHostToDevice));      // M x T column-major = [T][M]
+  RC_HIP(hipMemcpy(dev + o_V, Varft, nMT * 8, hipMemcpyHostToDevice));
+  RC_HIP(hipMemcpy(dev + o_off, off, sizeof off, hipMemcpyHostToDevice));
+  if (ngh) { RC_HIP(hipMemcpy(dev + o_gx, o->gh_x, ngh * 8, hipMemcpyHostToDevice)); RC_HIP(hipMemcpy(dev + o_gw, o->gh_w, ngh * 8, hipMemcpyHostToDevice)); }
+  if (npt) { RC_HIP(hipMemcpy(dev + o_wn, o->wn, npt * 8, hipMemcpyHostToDevice)); RC_HIP(hipMemcpy(dev + o_xn, o->xn_unscaled, npt * N * 8, hipMemcpyHostToDevice)); }
+  auto buf = [&](size_t n, size_t at) -> double* { return n ? dev + at : nullptr; };
+  ReconSrcPar rp{D, N, M, J, T, sq ? 1 : 0, o->link_kind, o->link_shift, dev + o_W, dev + o_E, dev + o_V, reinterpret_cast<const int*>(dev + o_off),
+                 (int)ngh, dev + o_gx, dev + o_gw, (int)npt, dev + o_wn, dev + o_xn, o->n_samples, o->seed,
+                 buf(n_es, o_es), buf(n_vs, o_vs), buf(n_ej, o_ej), buf(n_vj, o_vj), buf(n_en, o_en), buf(n_em, o_em), buf(n_vm, o_vm)};
+  if (st == NAGP_OK) {
+    const size_t ldsW = (size_t)D * MOM_MAXCD;
+    if (sampling) {
+      const unsigned grid = (unsigned)std::min<int64_t>(T, 65536);
+      hipLaunchKernelGGL(recon_src_sample_kernel, dim3(grid), dim3(64), (ldsW + D + MOM_MAXCD + RECON_MAXSRC) * sizeof(double), 0, rp);
+    } else if (sq) {
+      const unsigned grid = (unsigned)std::min<int64_t>(T, 65536);
+      hipLaunchKernelGGL(recon_src_pop_sqrt_kernel, dim3(grid), dim3(64), (ldsW + 2 * ngh + (size_t)D * 65) * sizeof(double), 0, rp);
+    } else {
+      hipLaunchKernelGGL(recon_src_moments_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), (ldsW + 2 * ngh) * sizeof(double), 0, rp);
+    }
+  }
+  RC_HIP(hipGetLastError());
+  RC_HIP(hipDeviceSynchronize());
+  if (n_es) RC_HIP(hipMemcpy(out->Esig, dev + o_es, n_es * 8, hipMemcpyDeviceToHost));
+  if (n_vs) RC_HIP(hipMemcpy(out->Vsig, dev + o_vs, n_vs * 8, hipMemcpyDeviceToHost));
+  if (n_ej) RC_HIP(hipMemcpy(out->Esrc, dev + o_ej, n_ej * 8, hipMemcpyDeviceToHost));      // [T][J] = J x T column-major
+  if (n_vj) RC_HIP(hipMemcpy(out->Vsrc, dev + o_vj, n_vj * 8, hipMemcpyDeviceToHost));
+  if (n_en) RC_HIP(hipMemcpy(out->Eenv, dev + o_en, n_en * 8, hipMemcpyDeviceToHost));
+  if (n_em) RC_HIP(hipMemcpy(out->Eft_mod, dev + o_em, n_em * 8, hipMemcpyDeviceToHost));
+  if (n_vm) RC_HIP(hipMemcpy(out->Varft_mod, dev + o_vm, n_vm * 8, hipMemcpyDeviceToHost));
+#undef RC_HIP
+  (void)hipFree(dev);
+  return st;
+}
+

@@ -21,6 +21,7 @@ KIND_GF_EP, KIND_IHGP, KIND_GIEKF = 0, 1, 2
 MODE_PREDICT, MODE_NLML = 0, 1
 LIK_POWER, LIK_POWER_NMF, LIK_POWER_NMF_SQRT = 0, 1, 2
 LINK_SOFTPLUS, LINK_EXP = 0, 1
+AMP_LINEAR, AMP_SQRT = 0, 1
 FLAG_IHGP_CONSTRAINTS, FLAG_EKF_RESET_P, FLAG_WANT_PS, FLAG_MIXTURE_RULE = 0x1, 0x2, 0x4, 0x8
 N_KERNELS = 8
 KERNEL_NAMES = ['filter', 'gain', 'scan', 'epsite', 'reduce', 'filter_lin', 'output', 'other']
@@ -64,11 +65,21 @@ class WindowStats(C.Structure):
                 ('worst_m', C.c_double), ('worst_P', C.c_double)]
 
 
+class ReconOpts(C.Structure):
+    _fields_ = [('amp_kind', C.c_int32), ('link_kind', C.c_int32), ('link_shift', C.c_double), ('n_sources', C.c_int32),
+                ('source_offsets', c_ip), ('n_samples', C.c_int32), ('seed', C.c_uint64), ('n_gh', C.c_int32), ('gh_x', c_dp), ('gh_w', c_dp),
+                ('n_pts', C.c_int32), ('wn', c_dp), ('xn_unscaled', c_dp), ('device', C.c_int32)]
+
+
+class ReconOut(C.Structure):
+    _fields_ = [('Esig', c_dp), ('Vsig', c_dp), ('Esrc', c_dp), ('Vsrc', c_dp), ('Eenv', c_dp), ('Eft_mod', c_dp), ('Varft_mod', c_dp)]
+
+
 EXPORTS = ['nagp_version', 'nagp_device_count', 'nagp_strerror', 'nagp_last_error', 'nagp_ep_run',
            'nagp_ihgp_run', 'nagp_giekf_run', 'nagp_plan_create', 'nagp_plan_upload_y', 'nagp_plan_execute',
            'nagp_plan_timings', 'nagp_plan_download', 'nagp_plan_device_bytes', 'nagp_plan_destroy', 'nagp_plan_upload_sites',
            'nagp_batch_partition', 'nagp_batch_run', 'nagp_shutdown', 'nagp_reconstruct', 'nagp_mom_eval', 'nagp_iekf_update1', 'nagp_fastfb_run',
-           'nagp_giekf_nlml_grad', 'nagp_plan_set_windows', 'nagp_plan_window_stats', 'nagp_window_partition']
+           'nagp_giekf_nlml_grad', 'nagp_plan_set_windows', 'nagp_plan_window_stats', 'nagp_window_partition', 'nagp_reconstruct_sources']
 
 
 class NagpError(RuntimeError):
@@ -211,6 +222,8 @@ def lib():
     L.nagp_reconstruct.argtypes = [C.c_int32, C.c_int32, C.c_int64, c_dp, c_dp, c_dp, C.c_int32, C.c_double, C.c_int32, c_dp, c_dp,
                                    C.c_int32, C.c_uint64, c_dp, c_dp, c_dp, c_dp, C.c_int32]
     L.nagp_reconstruct.restype = C.c_int
+    L.nagp_reconstruct_sources.argtypes = [C.c_int32, C.c_int32, C.c_int64, c_dp, c_dp, c_dp, C.POINTER(ReconOpts), C.POINTER(ReconOut)]
+    L.nagp_reconstruct_sources.restype = C.c_int
     L.nagp_plan_execute.argtypes = [C.c_void_p]
     L.nagp_plan_timings.argtypes = [C.c_void_p, C.POINTER(Timings)]
     L.nagp_plan_download.argtypes = [C.c_void_p, C.POINTER(Out)]
