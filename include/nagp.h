@@ -227,6 +227,31 @@ int nagp_giekf_nlml_grad(int32_t n_problems, const nagp_model* models, const dou
 int nagp_fastfb_run(int32_t S, const double* A, const double* AKHA, const double* HA, const double* K, const double* G,
                     const double* y, int64_t T, double* MS, double* sum_v2, int32_t device);
 
+/* Joint posterior draws of the stationary filterbank by the simulation smoother (Durbin & Koopman 2002): whole trajectories,
+ * correlated in time -- what fills a gap with texture and gives error bars on functionals that couple time steps (the
+ * missing-data experiment of demo_stationary_filterbank.m:168-200 fills its gap with the smoother MEAN, which decays to zero
+ * inside a long gap).  Inputs are those of nagp_fastfb_run plus the observation row H (S entries), the observation variance R
+ * and lower factors Lp, Lq (S x S column-major) with Lp Lp' = Pinf, Lq Lq' = Q.  Write S_y(.) for the smoothed means
+ * nagp_fastfb_run returns for an observation sequence (filter from m = 0, smoother with G, NaN = missing).  Draw i of n_draws:
+ *     z[t][j] = normals(T, j, n_draws, seed)[t, i]  (j = 0..S-1),   e[t] = normals(T, S, n_draws, seed)[t, i]
+ *     x*_0 = Lp z[0];  x*_t = A x*_{t-1} + Lq z[t]  (t >= 1)
+ *     y*_t = H x*_t + sqrt(R) e[t] where y_t is observed, NaN where y_t is NaN
+ *     X_i = x* + S_y(y - y*)   (S x T),      Ydraw_i[t] = H X_i[:, t]
+ * `normals` is the counter-based generator of nagp_reconstruct (Philox4x32-10 keyed by seed, counter = (t low, t high,
+ * sample block i / 4, site), Box-Muller), restated on the host in oracle/recon.py:normals: draw i does not depend on
+ * n_draws or on how the draws are batched on the device.  The mean over draws is S_y(y) in expectation; the covariance is the
+ * error covariance of the steady-state smoother under the model: Psm away from the ends and from gaps, larger inside gaps.
+ * Outputs (each may be NULL, not all three): Ydraw n_draws x T draw-major; Xdraw n_draws blocks of S x T column-major;
+ * MS = S_y(y), S x T, the bits of nagp_fastfb_run.  NAGP_EINVAL: a NULL input (G included: there is no filter-only form),
+ * S, T or n_draws < 1, R not positive and finite, no output; NAGP_EUNSUPPORTED: S > 256; NAGP_ENOMEM: one draw (2 T S
+ * doubles and change) does not fit the device-memory budget of a call -- all decided on the host before any device call. */
+int nagp_fastfb_sample(int32_t S, const double* A, const double* AKHA, const double* HA, const double* K, const double* G,
+                       const double* H, double R, const double* Lp, const double* Lq,
+                       const double* y, int64_t T, int32_t n_draws, uint64_t seed,
+                       double* Ydraw /* n_draws x T, draw-major; may be NULL */,
+                       double* Xdraw /* n_draws x (S x T column-major); may be NULL */,
+                       double* MS    /* S x T: S_y(y); may be NULL */, int32_t device);
+
 /* What the drivers do next with Eft / Varft (demo_toy_modulators_nmf.m:119-158, the same block in the other
  * demos): the reconstructed signal sig = sum_d (W link(g))_d z_d and the modulator amplitudes link(g_n) under the independent
  * posterior marginals z_d ~ N(Eft_d, Varft_d), g_n ~ N(Eft_{D+n}, Varft_{D+n}) of every time step:

@@ -19,6 +19,8 @@
  * Further entry points of include/nagp.h, selected by a command string in the first argument:
  *   [M,P,K,MU,S] = nagp_mex('iekf_update1', M, P, y, h_col(int32, 0-based), h_val, Wnmf, R, iters [,device])   nagp_iekf_update1
  *   [MS, sum_v2] = nagp_mex('fastfb', A, AKHA, HA, K, G ([] = filter only), y [,device])                       nagp_fastfb_run
+ *   [Ydraw, Xdraw, MS] = nagp_mex('fastfb_sample', A, AKHA, HA, K, G, H, R, Lp, Lq, y, n_draws, seed [,device])   nagp_fastfb_sample
+ *                                    Ydraw T x n_draws, Xdraw S x T x n_draws (computed only when asked for), MS S x T
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
  *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
@@ -198,6 +200,31 @@ static void cmd_fastfb(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
   if (nlhs > 1) { plhs[1] = mxCreateDoubleMatrix(1, 1, mxREAL); mxGetPr(plhs[1])[0] = sv2; }
 }
 
+static void cmd_fastfb_sample(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('fastfb_sample', A, AKHA, HA, K, G, H, R, Lp, Lq, y, n_draws, seed [,device]) -> [Ydraw, Xdraw, MS]: joint posterior draws of the
+     stationary filterbank by the simulation smoother; states and the smoother mean only when asked for */
+  size_t n, S, T; const double *A, *AK, *HA, *K, *G, *H, *Lp, *Lq, *y; int32_t dev, nd; mwSize dims3[3];
+  if (nrhs < 13 || nrhs > 14 || nlhs > 3) mexErrMsgIdAndTxt("nagp:arg", "usage: [Ydraw,Xdraw,MS] = nagp_mex('fastfb_sample',A,AKHA,HA,K,G,H,R,Lp,Lq,y,n_draws,seed[,device])");
+  A = dvec(prhs[1], "A", &n); S = mxGetM(prhs[1]);
+  if (!A || n != S * S) mexErrMsgIdAndTxt("nagp:arg", "A must be S x S");
+  AK = dvec(prhs[2], "AKHA", &n); if (n != S * S) mexErrMsgIdAndTxt("nagp:arg", "AKHA must be S x S");
+  HA = dvec(prhs[3], "HA", &n); if (n != S) mexErrMsgIdAndTxt("nagp:arg", "HA must have S entries");
+  K = dvec(prhs[4], "K", &n); if (n != S) mexErrMsgIdAndTxt("nagp:arg", "K must have S entries");
+  G = dvec(prhs[5], "G", &n); if (n != S * S) mexErrMsgIdAndTxt("nagp:arg", "G must be S x S");
+  H = dvec(prhs[6], "H", &n); if (n != S) mexErrMsgIdAndTxt("nagp:arg", "H must have S entries");
+  Lp = dvec(prhs[8], "Lp", &n); if (n != S * S) mexErrMsgIdAndTxt("nagp:arg", "Lp must be S x S");
+  Lq = dvec(prhs[9], "Lq", &n); if (n != S * S) mexErrMsgIdAndTxt("nagp:arg", "Lq must be S x S");
+  y = dvec(prhs[10], "y", &T);
+  nd = (int32_t)mxGetScalar(prhs[11]);
+  if (!y || nd < 1) mexErrMsgIdAndTxt("nagp:arg", "y must not be empty and n_draws must be at least 1");
+  dev = nrhs > 13 ? (int32_t)mxGetScalar(prhs[13]) : 0;
+  plhs[0] = mxCreateDoubleMatrix(T, (mwSize)nd, mxREAL);
+  if (nlhs > 1) { dims3[0] = S; dims3[1] = T; dims3[2] = (mwSize)nd; plhs[1] = mxCreateNumericArray(3, dims3, mxDOUBLE_CLASS, mxREAL); }
+  if (nlhs > 2) plhs[2] = mxCreateDoubleMatrix(S, T, mxREAL);
+  fail_if(nagp_fastfb_sample((int32_t)S, A, AK, HA, K, G, H, mxGetScalar(prhs[7]), Lp, Lq, y, (int64_t)T, nd, (uint64_t)mxGetScalar(prhs[12]),
+                             mxGetPr(plhs[0]), nlhs > 1 ? mxGetPr(plhs[1]) : NULL, nlhs > 2 ? mxGetPr(plhs[2]) : NULL, dev));
+}
+
 static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])  (demo_toy_modulators_nmf.m:119-158) */
   size_t n, nv, ngx, ngw, D, N, M, T; const double *E, *V, *W, *gx, *gw; int32_t dev; mxArray* o[4]; int i;
@@ -304,6 +331,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (mxGetString(prhs[0], cmd, sizeof cmd)) mexErrMsgIdAndTxt("nagp:arg", "command string too long");
     if (!strcmp(cmd, "iekf_update1")) cmd_iekf_update1(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fastfb")) cmd_fastfb(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "fastfb_sample")) cmd_fastfb_sample(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);

@@ -222,6 +222,136 @@ extern "C" int nagp_fastfb_run(int32_t S, const double* A, const double* AKHA, c
 }
 
 // ---------------------------------------------------------------------------------------------
+// stationary filterbank: joint posterior draws by the simulation smoother (see include/nagp.h, nagp_fbsample.hpp)
+constexpr size_t FBS_BUDGET_BYTES = (size_t)8 << 30;      // device memory of one call: the draws run in device batches under it
+constexpr int FBS_ONE_SPAN_DRAWS = 256;                   // from this many draws on, one span per draw fills the chip
+
+// M^n of a column-major S x S matrix in the layout of the boundary pass: out[i * (S+4) + l] = (M^n)(i,l)
+static void fbs_matrix_power(const double* M, int S, int64_t n, double* out) {
+  const size_t SS = (size_t)S * S;
+  std::vector<double> r(SS, 0.0), b(SS), t(SS);
+  for (int i = 0; i < S; ++i) { r[(size_t)i * S + i] = 1.0; for (int l = 0; l < S; ++l) b[(size_t)i * S + l] = M[i + (size_t)l * S]; }
+  auto mul = [&](const std::vector<double>& x, const std::vector<double>& z) {
+    std::fill(t.begin(), t.end(), 0.0);
+    for (int i = 0; i < S; ++i)
+      for (int q = 0; q < S; ++q) { const double xv = x[(size_t)i * S + q]; for (int l = 0; l < S; ++l) t[(size_t)i * S + l] += xv * z[(size_t)q * S + l]; }
+  };
+  for (; n > 0; n >>= 1) {
+    if (n & 1) { mul(r, b); r.swap(t); }
+    if (n > 1) { mul(b, b); b.swap(t); }
+  }
+  for (int i = 0; i < S; ++i) for (int l = 0; l < S + 4; ++l) out[(size_t)i * (S + 4) + l] = l < S ? r[(size_t)i * S + l] : 0.0;
+}
+
+extern "C" int nagp_fastfb_sample(int32_t S, const double* A, const double* AKHA, const double* HA, const double* K, const double* G,
+                                  const double* H, double R, const double* Lp, const double* Lq, const double* y, int64_t T,
+                                  int32_t n_draws, uint64_t seed, double* Ydraw, double* Xdraw, double* MS, int32_t device) {
+  if (!A || !AKHA || !HA || !K || !G || !H || !Lp || !Lq || !y) FAIL(NAGP_EINVAL, "null argument (there is no filter-only form: G is required)");
+  if (S < 1 || T < 1 || n_draws < 1) FAIL(NAGP_EINVAL, "bad sizes (S=%d T=%lld n_draws=%d)", S, (long long)T, n_draws);
+  if (!(R > 0.0) || !std::isfinite(R)) FAIL(NAGP_EINVAL, "the observation variance R must be positive and finite");
+  if (!Ydraw && !Xdraw && !MS) FAIL(NAGP_EINVAL, "no output requested");
+  if (S > 256) FAIL(NAGP_EUNSUPPORTED, "S=%d: the stationary filterbank runs a thread per state (S <= 256)", S);
+  const DevSwitches dev_sw = read_dev_switches();
+  const int mat_global = (fb_lds_doubles(S) * sizeof(double) > 160 * 1024) ? 1 : 0;
+  const size_t lds = fb_lds_doubles(S, mat_global) * sizeof(double);
+  const size_t lds_c = fb_compose_lds_doubles(S) * sizeof(double);
+  // spans as in nagp_fastfb_run (the filter's span matrices come from its compose pass); one span per draw for short series and large batches
+  int ns = 1;
+  if (lds_c <= 160 * 1024 && T >= 2048 && n_draws < FBS_ONE_SPAN_DRAWS && !dev_sw.fb_sequential) ns = (int)std::min<int64_t>(512, T / 128);
+  const int64_t L = (T + ns - 1) / ns;
+  ns = (int)((T + L - 1) / L);
+  const int nss = T > 1 ? (int)((T - 1 + L - 1) / L) : 0;      // spans of the T-1 smoothing steps
+  const size_t SS = (size_t)S * S, SP = (size_t)S + 4, TS = (size_t)T * S;
+  const size_t budget = dev_sw.fbs_budget_mb ? (size_t)dev_sw.fbs_budget_mb << 20 : FBS_BUDGET_BYTES;
+  const size_t fixed = (5 * SS + 3 * (size_t)S + (size_t)T + ((size_t)ns + 3) * S * SP + 8) * sizeof(double);
+  const size_t per_draw = (2 * TS + 2 * (size_t)T + 2 * (size_t)ns * S) * sizeof(double);
+  if (fixed + per_draw > budget) FAIL(NAGP_ENOMEM, "one draw takes %zu B of device memory (budget %zu B)", fixed + per_draw, budget);
+  const int nb = (int)std::min<size_t>({(size_t)n_draws, (budget - fixed) / per_draw, (size_t)32768});
+  if (MS) {                                                     // S_y(y): the smoother itself, same launches and bits
+    const int st0 = nagp_fastfb_run(S, A, AKHA, HA, K, G, y, T, MS, nullptr, device);
+    if (st0 != NAGP_OK) return st0;
+  }
+  if (!Ydraw && !Xdraw) return NAGP_OK;
+  if (hipSetDevice(device) != hipSuccess) FAIL(NAGP_EHIP, "hipSetDevice(%d)", device);
+  const size_t o_A = 0, o_B = o_A + SS, o_G = o_B + SS, o_lq = o_G + SS, o_lp = o_lq + SS, o_k = o_lp + SS, o_h = o_k + S, o_ha = o_h + S,
+               o_y = o_ha + S, o_phf = o_y + T, o_pha = o_phf + (size_t)ns * S * SP, o_phg = o_pha + S * SP, o_phl = o_phg + S * SP,
+               o_xs = o_phl + S * SP + 8, o_ms = o_xs + (size_t)nb * TS, o_d = o_ms + (size_t)nb * TS, o_yd = o_d + (size_t)nb * T,
+               o_c = o_yd + (size_t)nb * T, o_st = o_c + (size_t)nb * ns * S, total = o_st + (size_t)nb * ns * S;
+  double* dev = nullptr;
+  if (hipMalloc(&dev, total * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", total * sizeof(double)); }
+  int st = NAGP_OK;
+#define FS_HIP(x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string("nagp_fastfb_sample: " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
+  FS_HIP(hipMemcpy(dev + o_A, A, SS * 8, hipMemcpyHostToDevice));
+  FS_HIP(hipMemcpy(dev + o_B, AKHA, SS * 8, hipMemcpyHostToDevice));
+  FS_HIP(hipMemcpy(dev + o_G, G, SS * 8, hipMemcpyHostToDevice));
+  FS_HIP(hipMemcpy(dev + o_lq, Lq, SS * 8, hipMemcpyHostToDevice));
+  FS_HIP(hipMemcpy(dev + o_lp, Lp, SS * 8, hipMemcpyHostToDevice));
+  FS_HIP(hipMemcpy(dev + o_k, K, (size_t)S * 8, hipMemcpyHostToDevice));
+  FS_HIP(hipMemcpy(dev + o_h, H, (size_t)S * 8, hipMemcpyHostToDevice));
+  FS_HIP(hipMemcpy(dev + o_ha, HA, (size_t)S * 8, hipMemcpyHostToDevice));
+  FS_HIP(hipMemcpy(dev + o_y, y, (size_t)T * 8, hipMemcpyHostToDevice));
+  if (ns > 1) {                                                 // the span matrices that do not depend on y: A^L, G^L, G^(last span)
+    std::vector<double> ph(3 * S * SP);
+    fbs_matrix_power(A, S, L, ph.data());
+    fbs_matrix_power(G, S, L, ph.data() + S * SP);
+    fbs_matrix_power(G, S, (T - 1) - (int64_t)(nss - 1) * L, ph.data() + 2 * S * SP);
+    FS_HIP(hipMemcpy(dev + o_pha, ph.data(), ph.size() * 8, hipMemcpyHostToDevice));
+  }
+  const int NT = std::max(64, roundup64(S));
+  if (st == NAGP_OK) st = set_lds(fbs_prior_kernel<false>, lds);
+  if (st == NAGP_OK) st = set_lds(fbs_filter_kernel<false>, lds);
+  if (st == NAGP_OK) st = set_lds(fbs_smoother_kernel<false>, lds);
+  if (st == NAGP_OK && ns > 1) st = set_lds(fbs_prior_kernel<true>, lds);
+  if (st == NAGP_OK && ns > 1) st = set_lds(fbs_filter_kernel<true>, lds);
+  if (st == NAGP_OK && ns > 1) st = set_lds(fbs_smoother_kernel<true>, lds);
+  if (st == NAGP_OK && ns > 1) st = set_lds(fastfb_compose_kernel<false>, lds_c);
+  if (st == NAGP_OK && ns > 1) {                                // the filter's span matrices: a function of the NaN pattern of y alone
+    FbPar cp{S, T, dev + o_A, dev + o_B, dev + o_ha, dev + o_k, dev + o_y, nullptr, nullptr, L, ns, dev + o_phf, nullptr, 0};
+    hipLaunchKernelGGL(fastfb_compose_kernel<false>, dim3(ns), dim3(256), lds_c, 0, cp);
+  }
+  for (int i0 = 0; i0 < n_draws && st == NAGP_OK; i0 += nb) {
+    const int nbk = std::min(nb, n_draws - i0);
+    FbsPar fq{};
+    fq.S = S; fq.T = T; fq.L = L; fq.ns = ns; fq.draw0 = i0; fq.seed = seed; fq.sqrtR = std::sqrt(R);
+    fq.A = dev + o_A; fq.Lp = dev + o_lp; fq.H = dev + o_h; fq.K = dev + o_k; fq.y = dev + o_y;
+    fq.xs = dev + o_xs; fq.d = dev + o_d; fq.ms = dev + o_ms; fq.yd = dev + o_yd; fq.want_x = Xdraw ? 1 : 0;
+    fq.c = dev + o_c; fq.starts = ns > 1 ? dev + o_st : nullptr; fq.mat_global = mat_global;
+    // prior draw x*, d = y - y*
+    fq.B = dev + o_lq; fq.Phi = dev + o_pha; fq.phi_stride = 0; fq.PhiLast = dev + o_pha;
+    if (ns > 1) {
+      hipLaunchKernelGGL(fbs_prior_kernel<true>, dim3(ns, nbk), dim3(NT), lds, 0, fq);
+      hipLaunchKernelGGL(fbs_boundary_kernel<false>, dim3(nbk), dim3(256), 0, 0, fq);
+    }
+    hipLaunchKernelGGL(fbs_prior_kernel<false>, dim3(ns, nbk), dim3(NT), lds, 0, fq);
+    // filter of d
+    fq.B = dev + o_B; fq.Phi = dev + o_phf; fq.phi_stride = (size_t)S * SP; fq.PhiLast = dev + o_phf + (size_t)(ns - 1) * S * SP;
+    if (ns > 1) {
+      hipLaunchKernelGGL(fbs_filter_kernel<true>, dim3(ns, nbk), dim3(NT), lds, 0, fq);
+      hipLaunchKernelGGL(fbs_boundary_kernel<false>, dim3(nbk), dim3(256), 0, 0, fq);
+    }
+    hipLaunchKernelGGL(fbs_filter_kernel<false>, dim3(ns, nbk), dim3(NT), lds, 0, fq);
+    // step T-1, then the T-1 smoothing steps with + x* and the product with H in the replay
+    if (Xdraw) hipLaunchKernelGGL(fbs_last_kernel<true>, dim3(nbk), dim3(256), 0, 0, fq);
+    else hipLaunchKernelGGL(fbs_last_kernel<false>, dim3(nbk), dim3(256), 0, 0, fq);
+    if (T > 1) {
+      fq.B = dev + o_G; fq.ns = nss; fq.Phi = dev + o_phg; fq.phi_stride = 0; fq.PhiLast = dev + o_phl;
+      if (ns > 1) {
+        hipLaunchKernelGGL(fbs_smoother_kernel<true>, dim3(nss, nbk), dim3(NT), lds, 0, fq);
+        hipLaunchKernelGGL(fbs_boundary_kernel<true>, dim3(nbk), dim3(256), 0, 0, fq);
+      }
+      hipLaunchKernelGGL(fbs_smoother_kernel<false>, dim3(nss, nbk), dim3(NT), lds, 0, fq);
+    }
+    FS_HIP(hipGetLastError());
+    FS_HIP(hipDeviceSynchronize());
+    if (Ydraw) FS_HIP(hipMemcpy(Ydraw + (size_t)i0 * T, dev + o_yd, (size_t)nbk * T * 8, hipMemcpyDeviceToHost));
+    if (Xdraw) FS_HIP(hipMemcpy(Xdraw + (size_t)i0 * TS, dev + o_xs, (size_t)nbk * TS * 8, hipMemcpyDeviceToHost));
+  }
+#undef FS_HIP
+  (void)hipFree(dev);
+  return st;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Multi-GPU batched call (see include/nagp.h): problems round robin over the devices, one host thread + plan per device,
 // RCCL all-reduce of the per-sweep nlZ sums.
 extern "C" int nagp_batch_partition(int32_t n_problems, int32_t n_gpus, int32_t* dev_of) {

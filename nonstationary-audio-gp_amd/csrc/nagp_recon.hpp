@@ -28,28 +28,7 @@ struct ReconPar {
   double* Emod; double* Vmod;                          // [T][N]
 };
 
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned* out) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-// four standard normals from one counter (Box-Muller on 32-bit uniforms, (x + 0.5) / 2^32)
-__device__ __forceinline__ void normal4(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, double* z) {
-  unsigned u[4];
-  philox4x32_10(c0, c1, c2, c3, k0, k1, u);
-  const double s = 2.3283064365386963e-10;   // 2^-32
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const double u1 = ((double)u[2 * h] + 0.5) * s, u2 = ((double)u[2 * h + 1] + 0.5) * s;
-    const double r = sqrt(-2.0 * log(u1)), a = 6.283185307179586 * u2;
-    z[2 * h] = r * cos(a); z[2 * h + 1] = r * sin(a);
-  }
-}
+// (the generator -- philox4x32_10, normal4 -- is in nagp_dev.hpp: the joint draws of nagp_fbsample.hpp use the same one)
 
 // moments form: one thread per time step
 __global__ void __launch_bounds__(256) recon_moments_kernel(ReconPar rp) {

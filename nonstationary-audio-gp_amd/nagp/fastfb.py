@@ -6,6 +6,7 @@
 The set-up (`dare`, stationary gain, smoother gain) stays on the host exactly where the .m has it -- SciPy's
 solve_discrete_are / solve_discrete_lyapunov stand for the Control-System-Toolbox `dare` -- and the two O(T) loops run on
 the GPU (nagp_fastfb_run).  There is no CPU fallback.
+`kernel_ss_sampleFastFB` draws whole posterior trajectories on the same model (nagp_fastfb_sample).
 """
 import ctypes as C
 
@@ -35,13 +36,11 @@ def get_disc_model(lamx, varx, omega, D, kernel, se_approx_order=6):
     return sla.block_diag(*Ab), sla.block_diag(*Qb), np.hstack(Hb), sla.block_diag(*Pb), D * tau1, tau1
 
 
-def kernel_ss_kalmanFastFB(A, Q, C_, P0, K, vary, y, verbose=0, KF=0, steady=False, device=0):
-    """[lik,Xfin,Pfin] = kernel_ss_kalmanFastFB(A,Q,C,P0,K,vary,y,verbose,KF) (kernel_ss_kalmanFastFB.m:1).
-    Xfin is 1 x S x T, Pfin S x S x T (every slice the steady-state covariance, the last one the filter's -- as the .m
-    stores them); steady=True returns Pfin = (P_smoother or None, P_filter) instead of the T-fold copy."""
-    A = L.f64(A); S = A.shape[0]
+def _steady_state(A, Q, C_, vary, KF=0):
+    """The set-up lines of kernel_ss_kalmanFastFB.m (:46-77, :127-132): DARE, stationary gain, smoother gain and covariance.
+    Returns A (Fortran order), H (1 x S), R, Sinn, Kg, HA, AKHA, PF2, G and Psm (both None when KF == 1)."""
+    A = L.f64(A)
     H = np.asarray(C_, float).reshape(1, -1); R = float(np.ravel(vary)[0])
-    y = L.f64(np.asarray(y, float).ravel(), 'C'); T = y.size
     try:
         PP = sla.solve_discrete_are(A.T, H.T, np.asarray(Q, float), np.array([[R]]))      # :46
     except Exception as e:                                                                 # :51-53
@@ -57,6 +56,16 @@ def kernel_ss_kalmanFastFB(A, Q, C_, P0, K, vary, y, verbose=0, KF=0, steady=Fal
         QQ = PF2 - G @ PP @ G.T; QQ = (QQ + QQ.T) / 2                                      # :130-131
         Psm = sla.solve_discrete_lyapunov(G, QQ)                                           # :132  dare(G',0,QQ)
         G = L.f64(G)
+    return A, H, R, Sinn, Kg, HA, AKHA, PF2, G, Psm
+
+
+def kernel_ss_kalmanFastFB(A, Q, C_, P0, K, vary, y, verbose=0, KF=0, steady=False, device=0):
+    """[lik,Xfin,Pfin] = kernel_ss_kalmanFastFB(A,Q,C,P0,K,vary,y,verbose,KF) (kernel_ss_kalmanFastFB.m:1).
+    Xfin is 1 x S x T, Pfin S x S x T (every slice the steady-state covariance, the last one the filter's -- as the .m
+    stores them); steady=True returns Pfin = (P_smoother or None, P_filter) instead of the T-fold copy."""
+    A, H, R, Sinn, Kg, HA, AKHA, PF2, G, Psm = _steady_state(A, Q, C_, vary, KF)
+    S = A.shape[0]
+    y = L.f64(np.asarray(y, float).ravel(), 'C'); T = y.size
     MS = np.zeros((S, T), order='F'); sv2 = C.c_double(0.0)
     L.check(L.lib().nagp_fastfb_run(S, L.dptr(A), L.dptr(AKHA), L.dptr(L.f64(HA, 'C')), L.dptr(L.f64(Kg, 'C')), L.dptr(G),
                                     L.dptr(y), T, L.dptr(MS), C.byref(sv2), int(device)))
@@ -72,3 +81,37 @@ def kernel_ss_kalmanFastFB(A, Q, C_, P0, K, vary, y, verbose=0, KF=0, steady=Fal
     Pfin[:] = (PF2 if Psm is None else Psm)[:, :, None]
     Pfin[:, :, T - 1] = PF2
     return lik, Xfin, Pfin
+
+
+def _lower_factor(P):
+    """F with F F' = P: the Cholesky factor, or -- when P is not numerically positive definite -- the symmetric eigen-factor with
+    negative eigenvalues clipped to 0."""
+    P = np.asarray(P, float); P = (P + P.T) / 2
+    try:
+        return np.linalg.cholesky(P)
+    except np.linalg.LinAlgError:
+        w, V = np.linalg.eigh(P)
+        return V * np.sqrt(np.clip(w, 0.0, None))
+
+
+def kernel_ss_sampleFastFB(A, Q, C_, P0, K, vary, y, n_draws, seed=0, return_states=False, Lq=None, Lp=None, device=0):
+    """Joint posterior draws of the stationary filterbank (nagp_fastfb_sample, include/nagp.h): the simulation smoother on the
+    steady-state filter / smoother of kernel_ss_kalmanFastFB, same arguments (P0 = Pinf; NaN in y = missing).
+    Draw i:  x* ~ prior (x*_0 = Lp z_0, x*_t = A x*_{t-1} + Lq z_t),  y* = H x* + sqrt(vary) e where y is observed,
+    X_i = x* + S_y(y - y*),  Ydraw_i = H X_i, with S_y(.) the smoothed means of kernel_ss_kalmanFastFB and z, e from the
+    counter-based generator keyed by `seed` (draw i does not depend on n_draws).  The covariance over draws is the error covariance of
+    the steady-state smoother under the model: Psm away from the ends and from gaps, larger inside gaps.
+    Lq, Lp: factors with Lq Lq' = Q, Lp Lp' = P0 (default: Cholesky; eigen-factor with clipped eigenvalues when that fails).
+    Returns Ydraw (n_draws, T), Xdraw (n_draws, S, T) or None, Xmean (S, T) = S_y(y)."""
+    A, H, R, Sinn, Kg, HA, AKHA, PF2, G, Psm = _steady_state(A, Q, C_, vary, 0)
+    S = A.shape[0]; n_draws = int(n_draws)
+    y = L.f64(np.asarray(y, float).ravel(), 'C'); T = y.size
+    Lq = L.f64(_lower_factor(Q) if Lq is None else Lq); Lp = L.f64(_lower_factor(P0) if Lp is None else Lp)
+    if Lq.shape != (S, S) or Lp.shape != (S, S):
+        raise ValueError('Lq and Lp must be S x S')
+    Yd = np.zeros((max(n_draws, 0), T)); MS = np.zeros((S, T), order='F')
+    Xd = np.zeros((max(n_draws, 0), T, S)) if return_states else None                      # draw-major blocks of S x T column-major
+    L.check(L.lib().nagp_fastfb_sample(S, L.dptr(A), L.dptr(AKHA), L.dptr(L.f64(HA, 'C')), L.dptr(L.f64(Kg, 'C')), L.dptr(G),
+                                       L.dptr(L.f64(H.ravel(), 'C')), R, L.dptr(Lp), L.dptr(Lq), L.dptr(y), T, n_draws, int(seed) & (2 ** 64 - 1),
+                                       L.dptr(Yd), L.dptr(Xd), L.dptr(MS), int(device)))
+    return Yd, (Xd.transpose(0, 2, 1) if return_states else None), MS
