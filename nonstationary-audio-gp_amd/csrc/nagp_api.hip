@@ -133,6 +133,9 @@ static DevSwitches read_dev_switches() {
     return (code);                               \
   } while (0)
 
+// kernel signatures, the plan's table of resolved kernels, the pickers, set_lds / set_kernel
+#include "nagp_api_kernels.hpp"
+
 struct EvRec { int kid; hipEvent_t a, b; };
 
 struct nagp_plan {
@@ -146,7 +149,7 @@ struct nagp_plan {
   int TPT = 1, TPT_f = 1, NT = 256, NT_f = 256, NT_ih = 256;
   int TPT_a = 1, NT_a = 256, LB_a = 256;   // ADF (mom) launches of the gf filter
   int NT_fl = 256;                         // threads of the (not wide) fixed-site launches
-  int wide_l = 0, NT_l = 256;              // fixed-site launches of models with 512 < tiles <= 1024: one tile per thread, 1024-thread bound
+  int wide_l = 0, NT_l = 256, LB_l = 512;  // fixed-site launches of models with 512 < tiles <= 1024: one tile per thread, 768- / 1024-thread bound (LB_l)
   int chunk = 2048, LP1 = 1, LP2 = 1, ns_max = 1;
   SpanPar spar{};
   int mfma_sp = 0;      // > 0: FP64-MFMA smoother passes on dense Sp x Sp matrices
@@ -215,6 +218,7 @@ struct nagp_plan {
   nagp_timings tim{};
   std::vector<double> h_hval;          // [B][M]
   size_t lds_filter = 0, lds_gain = 0, lds_scan = 0, lds_ep = 0, lds_ih = 0;
+  PlanKernels k{};      // the kernels the plan launches, resolved at plan creation (nagp_api_kernels.hpp)
   // time-parallel fixed-site filter of sweeps >= 2 (nagp_plan_set_windows; off while win.size() < 2): the windows of the plan, their
   // device copy, the per-(problem, window) state at the end of the warm-up, the per-(problem, boundary) mismatches (m, P)
   std::vector<FilterWin> win;
@@ -276,24 +280,6 @@ static void dfree(nagp_plan* p, double* ptr) {
   (void)hipStreamSynchronize(p->stream);          // (a memset of the buffer may still be queued)
   (void)hipFree(ptr);
 }
-
-// run CALL(MV) for the mom variant mv (0 = POWER, 1..9 = NMF cubature dimension; 9 = three sources x three components of the
-// source-separation mixtures, experiments/source_sep_piano.m:78-90)
-#define NAGP_MV_SWITCH(mv, CALL)                                                                         \
-  switch (mv) {                                                                                          \
-    case 0: CALL(0); break; case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break;      \
-    case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break;      \
-    case 8: CALL(8); break; default: CALL(9); break;                                                     \
-  }
-
-// the kernels without covariance tiles (IHGP filter, site refresh, mom) also exist for N = 9 (three sources x three
-// components of the source-separation mixtures, experiments/source_sep_piano.m:78-90)
-#define NAGP_MV_SWITCH9(mv, CALL)                                                                        \
-  switch (mv) {                                                                                          \
-    case 0: CALL(0); break; case 1: CALL(1); break; case 2: CALL(2); break; case 3: CALL(3); break;      \
-    case 4: CALL(4); break; case 5: CALL(5); break; case 6: CALL(6); break; case 7: CALL(7); break;      \
-    case 8: CALL(8); break; default: CALL(9); break;                                                     \
-  }
 
 // Block structure of Wnmf (source-separation mixtures): the finest partition into contiguous (sub-band range,
 // component range) blocks that holds the non-zeros of every problem of the plan; the tables of MomSrc (nagp_dev.hpp).
@@ -427,16 +413,6 @@ struct Timed {
     if (a && b) p->evs.push_back({kid, a, b});
   }
 };
-
-// The dynamic-LDS limit of a kernel is a per-process attribute: it is raised to the full 160 KiB once and never lowered, so that
-// plans with different LDS needs can be alive at the same time (a later, smaller plan must not shrink it under a live one).
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-  if (bytes > 160 * 1024) FAIL(NAGP_EUNSUPPORTED, "kernel needs %zu B of LDS (> 160 KiB)", bytes);
-  if (bytes > 48 * 1024)
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-  return NAGP_OK;
-}
 
 // ---- the rest of this translation unit, in three parts (one object file: the parts share the plan struct and the static helpers above)
 #include "nagp_api_plan.hpp"

@@ -2,6 +2,9 @@
 // nagp_api_entry.hpp; the plan struct, the error helpers and the developer switches live in nagp_api.hip itself).
 // The one-shot entry points (ep / ihgp / giekf run), mom on its own, iekf_update1, the stationary filterbank, nagp_batch_run (RCCL), reconstruction.
 
+// device calls of the per-call entry points: the first failure is kept (st, the text names the entry point), the calls after it are skipped
+#define ENTRY_HIP(fn, x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string(#fn ": " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
+
 // ---------------------------------------------------------------------------------------------
 static int run_one(const nagp_model* model, const nagp_ihgp_tables* tables, const double* y, int64_t T,
                    const nagp_opts* opts, nagp_out* out) {
@@ -73,14 +76,13 @@ extern "C" int nagp_mom_eval(const nagp_opts* o, int32_t D, int32_t N, const dou
   for (int dd = 0; dd < (power ? 0 : D); ++dd)
     for (int j = 0; j < N; ++j) Wr[(size_t)dd * N + j] = Wnmf[dd + (size_t)D * j];
   int st = NAGP_OK;
-#define ME_HIP(x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string("nagp_mom_eval: " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
-  ME_HIP(hipMemcpy(dev + o_wn, o->wn, (size_t)o->n_pts * 8, hipMemcpyHostToDevice));
-  ME_HIP(hipMemcpy(dev + o_xd, xd.data(), xd.size() * 8, hipMemcpyHostToDevice));
-  ME_HIP(hipMemcpy(dev + o_code, code.data(), code.size(), hipMemcpyHostToDevice));
-  if (nW) ME_HIP(hipMemcpy(dev + o_W, Wr.data(), nW * 8, hipMemcpyHostToDevice));
-  ME_HIP(hipMemcpy(dev + o_y, y, (size_t)n * 8, hipMemcpyHostToDevice));
-  ME_HIP(hipMemcpy(dev + o_mu, mu, (size_t)n * M * 8, hipMemcpyHostToDevice));
-  ME_HIP(hipMemcpy(dev + o_s2, s2, (size_t)n * M * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(dev + o_wn, o->wn, (size_t)o->n_pts * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(dev + o_xd, xd.data(), xd.size() * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(dev + o_code, code.data(), code.size(), hipMemcpyHostToDevice));
+  if (nW) ENTRY_HIP(nagp_mom_eval, hipMemcpy(dev + o_W, Wr.data(), nW * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(dev + o_y, y, (size_t)n * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(dev + o_mu, mu, (size_t)n * M * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(dev + o_s2, s2, (size_t)n * M * 8, hipMemcpyHostToDevice));
   MomCfg mc{};
   mc.lik_kind = o->lik_kind; mc.link_kind = o->link_kind; mc.link_shift = o->link_shift;
   mc.n_pts = o->n_pts; mc.cdim = o->cub_dim; mc.D = D; mc.nd = (int)xd.size();
@@ -95,15 +97,15 @@ extern "C" int nagp_mom_eval(const nagp_opts* o, int32_t D, int32_t N, const dou
   MomPar mp{D, power ? 0 : N, M, std::exp(lik_param), o->ep_fraction, nW ? dev + o_W : nullptr, dev + o_y, dev + o_mu, dev + o_s2,
             dev + o_lZ, dev + o_dl, dev + o_d2, n};
   const int grid = (int)std::min<int64_t>(n, 1024);
-#define LM(V) do { if (st == NAGP_OK) st = set_lds(mom_kernel<V>, lds); if (st == NAGP_OK) hipLaunchKernelGGL(mom_kernel<V>, dim3(grid), dim3(256), lds, 0, mc, mp); } while (0)
-  NAGP_MV_SWITCH9(mom_variant(mc), LM)
+  const MomFn mom = pick_mom(mom_variant(mc));
+  if (st == NAGP_OK) st = set_lds(mom, lds);
+  if (st == NAGP_OK) hipLaunchKernelGGL(mom, dim3(grid), dim3(256), lds, 0, mc, mp);
 #undef LM
-  ME_HIP(hipGetLastError());
-  ME_HIP(hipDeviceSynchronize());
-  ME_HIP(hipMemcpy(lZ, dev + o_lZ, (size_t)n * 8, hipMemcpyDeviceToHost));
-  ME_HIP(hipMemcpy(dlZ, dev + o_dl, (size_t)n * M * 8, hipMemcpyDeviceToHost));
-  ME_HIP(hipMemcpy(d2lZ, dev + o_d2, (size_t)n * M * 8, hipMemcpyDeviceToHost));
-#undef ME_HIP
+  ENTRY_HIP(nagp_mom_eval, hipGetLastError());
+  ENTRY_HIP(nagp_mom_eval, hipDeviceSynchronize());
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(lZ, dev + o_lZ, (size_t)n * 8, hipMemcpyDeviceToHost));
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(dlZ, dev + o_dl, (size_t)n * M * 8, hipMemcpyDeviceToHost));
+  ENTRY_HIP(nagp_mom_eval, hipMemcpy(d2lZ, dev + o_d2, (size_t)n * M * 8, hipMemcpyDeviceToHost));
   (void)hipFree(dev);
   return st;
 }
@@ -128,23 +130,21 @@ extern "C" int nagp_iekf_update1(int32_t S, int32_t D, int32_t N, const int32_t*
   for (int dd = 0; dd < D; ++dd)
     for (int j = 0; j < N; ++j) Wr[(size_t)dd * N + j] = Wnmf[dd + (size_t)D * j];
   int st = NAGP_OK;
-#define EK_HIP(x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string("nagp_iekf_update1: " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
-  EK_HIP(hipMemcpy(dev + o_m, m, (size_t)S * 8, hipMemcpyHostToDevice));
-  EK_HIP(hipMemcpy(dev + o_P, P, (size_t)S * S * 8, hipMemcpyHostToDevice));
-  EK_HIP(hipMemcpy(dev + o_hv, h_val, (size_t)M * 8, hipMemcpyHostToDevice));
-  EK_HIP(hipMemcpy(dev + o_W, Wr.data(), Wr.size() * 8, hipMemcpyHostToDevice));
-  EK_HIP(hipMemcpy(dev + o_hc, h_col, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_iekf_update1, hipMemcpy(dev + o_m, m, (size_t)S * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_iekf_update1, hipMemcpy(dev + o_P, P, (size_t)S * S * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_iekf_update1, hipMemcpy(dev + o_hv, h_val, (size_t)M * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_iekf_update1, hipMemcpy(dev + o_W, Wr.data(), Wr.size() * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_iekf_update1, hipMemcpy(dev + o_hc, h_col, (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice));
   EkfPar ep{S, D, N, iters, R, y, reinterpret_cast<const int*>(dev + o_hc), dev + o_hv, dev + o_W, dev + o_m, dev + o_P, dev + o_K, dev + o_ms};
   const size_t lds = (2 * (size_t)S + 2 * M + 2) * sizeof(double);
   if (st == NAGP_OK) hipLaunchKernelGGL(iekf_update1_kernel, dim3(1), dim3(256), lds, 0, ep);
-  EK_HIP(hipGetLastError());
-  EK_HIP(hipDeviceSynchronize());
+  ENTRY_HIP(nagp_iekf_update1, hipGetLastError());
+  ENTRY_HIP(nagp_iekf_update1, hipDeviceSynchronize());
   double ms[2] = {0, 0};
-  EK_HIP(hipMemcpy(m, dev + o_m, (size_t)S * 8, hipMemcpyDeviceToHost));
-  EK_HIP(hipMemcpy(P, dev + o_P, (size_t)S * S * 8, hipMemcpyDeviceToHost));
-  if (K) EK_HIP(hipMemcpy(K, dev + o_K, (size_t)S * 8, hipMemcpyDeviceToHost));
-  EK_HIP(hipMemcpy(ms, dev + o_ms, 16, hipMemcpyDeviceToHost));
-#undef EK_HIP
+  ENTRY_HIP(nagp_iekf_update1, hipMemcpy(m, dev + o_m, (size_t)S * 8, hipMemcpyDeviceToHost));
+  ENTRY_HIP(nagp_iekf_update1, hipMemcpy(P, dev + o_P, (size_t)S * S * 8, hipMemcpyDeviceToHost));
+  if (K) ENTRY_HIP(nagp_iekf_update1, hipMemcpy(K, dev + o_K, (size_t)S * 8, hipMemcpyDeviceToHost));
+  ENTRY_HIP(nagp_iekf_update1, hipMemcpy(ms, dev + o_ms, 16, hipMemcpyDeviceToHost));
   if (MU) *MU = ms[0];
   if (Sinn) *Sinn = ms[1];
   (void)hipFree(dev);
@@ -174,13 +174,12 @@ extern "C" int nagp_fastfb_run(int32_t S, const double* A, const double* AKHA, c
   double* dev = nullptr;
   if (hipMalloc(&dev, total * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", total * sizeof(double)); }
   int st = NAGP_OK;
-#define FB_HIP(x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string("nagp_fastfb_run: " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
-  FB_HIP(hipMemcpy(dev + o_A, A, SS * 8, hipMemcpyHostToDevice));
-  FB_HIP(hipMemcpy(dev + o_B, AKHA, SS * 8, hipMemcpyHostToDevice));
-  if (G) FB_HIP(hipMemcpy(dev + o_G, G, SS * 8, hipMemcpyHostToDevice));
-  FB_HIP(hipMemcpy(dev + o_ha, HA, (size_t)S * 8, hipMemcpyHostToDevice));
-  FB_HIP(hipMemcpy(dev + o_k, K, (size_t)S * 8, hipMemcpyHostToDevice));
-  FB_HIP(hipMemcpy(dev + o_y, y, (size_t)T * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_run, hipMemcpy(dev + o_A, A, SS * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_run, hipMemcpy(dev + o_B, AKHA, SS * 8, hipMemcpyHostToDevice));
+  if (G) ENTRY_HIP(nagp_fastfb_run, hipMemcpy(dev + o_G, G, SS * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_run, hipMemcpy(dev + o_ha, HA, (size_t)S * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_run, hipMemcpy(dev + o_k, K, (size_t)S * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_run, hipMemcpy(dev + o_y, y, (size_t)T * 8, hipMemcpyHostToDevice));
   const int NT = std::max(64, roundup64(S));
   if (st == NAGP_OK) st = set_lds(fastfb_filter_kernel, lds);
   if (st == NAGP_OK) st = set_lds(fastfb_smoother_kernel, lds);
@@ -206,17 +205,16 @@ extern "C" int nagp_fastfb_run(int32_t S, const double* A, const double* AKHA, c
       hipLaunchKernelGGL(fastfb_smoother_kernel, dim3(nss), dim3(NT), lds, 0, fp);
     }
   }
-  FB_HIP(hipGetLastError());
-  FB_HIP(hipDeviceSynchronize());
-  FB_HIP(hipMemcpy(MS, dev + o_ms, (size_t)T * S * 8, hipMemcpyDeviceToHost));
+  ENTRY_HIP(nagp_fastfb_run, hipGetLastError());
+  ENTRY_HIP(nagp_fastfb_run, hipDeviceSynchronize());
+  ENTRY_HIP(nagp_fastfb_run, hipMemcpy(MS, dev + o_ms, (size_t)T * S * 8, hipMemcpyDeviceToHost));
   if (sum_v2) {
     std::vector<double> part((size_t)ns);
-    FB_HIP(hipMemcpy(part.data(), dev + o_sv, (size_t)ns * 8, hipMemcpyDeviceToHost));
+    ENTRY_HIP(nagp_fastfb_run, hipMemcpy(part.data(), dev + o_sv, (size_t)ns * 8, hipMemcpyDeviceToHost));
     double acc = 0.0;
     for (int j = 0; j < ns; ++j) acc += part[j];      // fixed order
     *sum_v2 = acc;
   }
-#undef FB_HIP
   (void)hipFree(dev);
   return st;
 }
@@ -280,22 +278,21 @@ extern "C" int nagp_fastfb_sample(int32_t S, const double* A, const double* AKHA
   double* dev = nullptr;
   if (hipMalloc(&dev, total * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", total * sizeof(double)); }
   int st = NAGP_OK;
-#define FS_HIP(x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string("nagp_fastfb_sample: " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
-  FS_HIP(hipMemcpy(dev + o_A, A, SS * 8, hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(dev + o_B, AKHA, SS * 8, hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(dev + o_G, G, SS * 8, hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(dev + o_lq, Lq, SS * 8, hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(dev + o_lp, Lp, SS * 8, hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(dev + o_k, K, (size_t)S * 8, hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(dev + o_h, H, (size_t)S * 8, hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(dev + o_ha, HA, (size_t)S * 8, hipMemcpyHostToDevice));
-  FS_HIP(hipMemcpy(dev + o_y, y, (size_t)T * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_A, A, SS * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_B, AKHA, SS * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_G, G, SS * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_lq, Lq, SS * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_lp, Lp, SS * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_k, K, (size_t)S * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_h, H, (size_t)S * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_ha, HA, (size_t)S * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_y, y, (size_t)T * 8, hipMemcpyHostToDevice));
   if (ns > 1) {                                                 // the span matrices that do not depend on y: A^L, G^L, G^(last span)
     std::vector<double> ph(3 * S * SP);
     fbs_matrix_power(A, S, L, ph.data());
     fbs_matrix_power(G, S, L, ph.data() + S * SP);
     fbs_matrix_power(G, S, (T - 1) - (int64_t)(nss - 1) * L, ph.data() + 2 * S * SP);
-    FS_HIP(hipMemcpy(dev + o_pha, ph.data(), ph.size() * 8, hipMemcpyHostToDevice));
+    ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(dev + o_pha, ph.data(), ph.size() * 8, hipMemcpyHostToDevice));
   }
   const int NT = std::max(64, roundup64(S));
   if (st == NAGP_OK) st = set_lds(fbs_prior_kernel<false>, lds);
@@ -341,12 +338,11 @@ extern "C" int nagp_fastfb_sample(int32_t S, const double* A, const double* AKHA
       }
       hipLaunchKernelGGL(fbs_smoother_kernel<false>, dim3(nss, nbk), dim3(NT), lds, 0, fq);
     }
-    FS_HIP(hipGetLastError());
-    FS_HIP(hipDeviceSynchronize());
-    if (Ydraw) FS_HIP(hipMemcpy(Ydraw + (size_t)i0 * T, dev + o_yd, (size_t)nbk * T * 8, hipMemcpyDeviceToHost));
-    if (Xdraw) FS_HIP(hipMemcpy(Xdraw + (size_t)i0 * TS, dev + o_xs, (size_t)nbk * TS * 8, hipMemcpyDeviceToHost));
+    ENTRY_HIP(nagp_fastfb_sample, hipGetLastError());
+    ENTRY_HIP(nagp_fastfb_sample, hipDeviceSynchronize());
+    if (Ydraw) ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(Ydraw + (size_t)i0 * T, dev + o_yd, (size_t)nbk * T * 8, hipMemcpyDeviceToHost));
+    if (Xdraw) ENTRY_HIP(nagp_fastfb_sample, hipMemcpy(Xdraw + (size_t)i0 * TS, dev + o_xs, (size_t)nbk * TS * 8, hipMemcpyDeviceToHost));
   }
-#undef FS_HIP
   (void)hipFree(dev);
   return st;
 }
@@ -535,11 +531,10 @@ extern "C" int nagp_reconstruct(int32_t D, int32_t N, int64_t T, const double* E
   for (int d = 0; d < D; ++d)
     for (int j = 0; j < N; ++j) Wr[(size_t)d * N + j] = Wnmf[d + (size_t)D * j];
   int st = NAGP_OK;
-#define RC_HIP(x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string("nagp_reconstruct: " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
-  RC_HIP(hipMemcpy(dev + o_W, Wr.data(), nW * 8, hipMemcpyHostToDevice));
-  RC_HIP(hipMemcpy(dev + o_E, Eft, nMT * 8, hipMemcpyHostToDevice));      // M x T column-major = [T][M]
-  RC_HIP(hipMemcpy(dev + o_V, Varft, nMT * 8, hipMemcpyHostToDevice));
-  if (ngh) { RC_HIP(hipMemcpy(dev + o_gx, gh_x, ngh * 8, hipMemcpyHostToDevice)); RC_HIP(hipMemcpy(dev + o_gw, gh_w, ngh * 8, hipMemcpyHostToDevice)); }
+  ENTRY_HIP(nagp_reconstruct, hipMemcpy(dev + o_W, Wr.data(), nW * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_reconstruct, hipMemcpy(dev + o_E, Eft, nMT * 8, hipMemcpyHostToDevice));      // M x T column-major = [T][M]
+  ENTRY_HIP(nagp_reconstruct, hipMemcpy(dev + o_V, Varft, nMT * 8, hipMemcpyHostToDevice));
+  if (ngh) { ENTRY_HIP(nagp_reconstruct, hipMemcpy(dev + o_gx, gh_x, ngh * 8, hipMemcpyHostToDevice)); ENTRY_HIP(nagp_reconstruct, hipMemcpy(dev + o_gw, gh_w, ngh * 8, hipMemcpyHostToDevice)); }
   ReconPar rp{D, N, M, T, link_kind, link_shift, dev + o_W, dev + o_E, dev + o_V, (int)ngh, dev + o_gx, dev + o_gw, n_samples, seed,
               dev + o_es, dev + o_vs, dev + o_em, dev + o_vm};
   if (st == NAGP_OK) {
@@ -550,13 +545,12 @@ extern "C" int nagp_reconstruct(int32_t D, int32_t N, int64_t T, const double* E
       hipLaunchKernelGGL(recon_moments_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), (nW + 2 * ngh) * sizeof(double), 0, rp);
     }
   }
-  RC_HIP(hipGetLastError());
-  RC_HIP(hipDeviceSynchronize());
-  RC_HIP(hipMemcpy(Esig, dev + o_es, (size_t)T * 8, hipMemcpyDeviceToHost));
-  RC_HIP(hipMemcpy(Vsig, dev + o_vs, (size_t)T * 8, hipMemcpyDeviceToHost));
-  RC_HIP(hipMemcpy(Eft_mod, dev + o_em, (size_t)N * T * 8, hipMemcpyDeviceToHost));
-  RC_HIP(hipMemcpy(Varft_mod, dev + o_vm, (size_t)N * T * 8, hipMemcpyDeviceToHost));
-#undef RC_HIP
+  ENTRY_HIP(nagp_reconstruct, hipGetLastError());
+  ENTRY_HIP(nagp_reconstruct, hipDeviceSynchronize());
+  ENTRY_HIP(nagp_reconstruct, hipMemcpy(Esig, dev + o_es, (size_t)T * 8, hipMemcpyDeviceToHost));
+  ENTRY_HIP(nagp_reconstruct, hipMemcpy(Vsig, dev + o_vs, (size_t)T * 8, hipMemcpyDeviceToHost));
+  ENTRY_HIP(nagp_reconstruct, hipMemcpy(Eft_mod, dev + o_em, (size_t)N * T * 8, hipMemcpyDeviceToHost));
+  ENTRY_HIP(nagp_reconstruct, hipMemcpy(Varft_mod, dev + o_vm, (size_t)N * T * 8, hipMemcpyDeviceToHost));
   (void)hipFree(dev);
   return st;
 }
@@ -599,13 +593,12 @@ extern "C" int nagp_reconstruct_sources(int32_t D, int32_t N, int64_t T, const d
   for (int d = 0; d < D; ++d)
     for (int j = 0; j < N; ++j) Wr[(size_t)d * N + j] = Wnmf[d + (size_t)D * j];
   int st = NAGP_OK;
-#define RC_HIP(x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string("nagp_reconstruct_sources: " #x " -> ") + hipGetErrorString(_e); st = NAGP_EHIP; } } } while (0)
-  RC_HIP(hipMemcpy(dev + o_W, Wr.data(), nW * 8, hipMemcpyHostToDevice));
-  RC_HIP(hipMemcpy(dev + o_E, Eft, nMT * 8, hipMemcpyHostToDevice));      // M x T column-major = [T][M]
-  RC_HIP(hipMemcpy(dev + o_V, Varft, nMT * 8, hipMemcpyHostToDevice));
-  RC_HIP(hipMemcpy(dev + o_off, off, sizeof off, hipMemcpyHostToDevice));
-  if (ngh) { RC_HIP(hipMemcpy(dev + o_gx, o->gh_x, ngh * 8, hipMemcpyHostToDevice)); RC_HIP(hipMemcpy(dev + o_gw, o->gh_w, ngh * 8, hipMemcpyHostToDevice)); }
-  if (npt) { RC_HIP(hipMemcpy(dev + o_wn, o->wn, npt * 8, hipMemcpyHostToDevice)); RC_HIP(hipMemcpy(dev + o_xn, o->xn_unscaled, npt * N * 8, hipMemcpyHostToDevice)); }
+  ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(dev + o_W, Wr.data(), nW * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(dev + o_E, Eft, nMT * 8, hipMemcpyHostToDevice));      // M x T column-major = [T][M]
+  ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(dev + o_V, Varft, nMT * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(dev + o_off, off, sizeof off, hipMemcpyHostToDevice));
+  if (ngh) { ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(dev + o_gx, o->gh_x, ngh * 8, hipMemcpyHostToDevice)); ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(dev + o_gw, o->gh_w, ngh * 8, hipMemcpyHostToDevice)); }
+  if (npt) { ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(dev + o_wn, o->wn, npt * 8, hipMemcpyHostToDevice)); ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(dev + o_xn, o->xn_unscaled, npt * N * 8, hipMemcpyHostToDevice)); }
   auto buf = [&](size_t n, size_t at) -> double* { return n ? dev + at : nullptr; };
   ReconSrcPar rp{D, N, M, J, T, sq ? 1 : 0, o->link_kind, o->link_shift, dev + o_W, dev + o_E, dev + o_V, reinterpret_cast<const int*>(dev + o_off),
                  (int)ngh, dev + o_gx, dev + o_gw, (int)npt, dev + o_wn, dev + o_xn, o->n_samples, o->seed,
@@ -622,17 +615,17 @@ extern "C" int nagp_reconstruct_sources(int32_t D, int32_t N, int64_t T, const d
       hipLaunchKernelGGL(recon_src_moments_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), (ldsW + 2 * ngh) * sizeof(double), 0, rp);
     }
   }
-  RC_HIP(hipGetLastError());
-  RC_HIP(hipDeviceSynchronize());
-  if (n_es) RC_HIP(hipMemcpy(out->Esig, dev + o_es, n_es * 8, hipMemcpyDeviceToHost));
-  if (n_vs) RC_HIP(hipMemcpy(out->Vsig, dev + o_vs, n_vs * 8, hipMemcpyDeviceToHost));
-  if (n_ej) RC_HIP(hipMemcpy(out->Esrc, dev + o_ej, n_ej * 8, hipMemcpyDeviceToHost));      // [T][J] = J x T column-major
-  if (n_vj) RC_HIP(hipMemcpy(out->Vsrc, dev + o_vj, n_vj * 8, hipMemcpyDeviceToHost));
-  if (n_en) RC_HIP(hipMemcpy(out->Eenv, dev + o_en, n_en * 8, hipMemcpyDeviceToHost));
-  if (n_em) RC_HIP(hipMemcpy(out->Eft_mod, dev + o_em, n_em * 8, hipMemcpyDeviceToHost));
-  if (n_vm) RC_HIP(hipMemcpy(out->Varft_mod, dev + o_vm, n_vm * 8, hipMemcpyDeviceToHost));
-#undef RC_HIP
+  ENTRY_HIP(nagp_reconstruct_sources, hipGetLastError());
+  ENTRY_HIP(nagp_reconstruct_sources, hipDeviceSynchronize());
+  if (n_es) ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(out->Esig, dev + o_es, n_es * 8, hipMemcpyDeviceToHost));
+  if (n_vs) ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(out->Vsig, dev + o_vs, n_vs * 8, hipMemcpyDeviceToHost));
+  if (n_ej) ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(out->Esrc, dev + o_ej, n_ej * 8, hipMemcpyDeviceToHost));      // [T][J] = J x T column-major
+  if (n_vj) ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(out->Vsrc, dev + o_vj, n_vj * 8, hipMemcpyDeviceToHost));
+  if (n_en) ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(out->Eenv, dev + o_en, n_en * 8, hipMemcpyDeviceToHost));
+  if (n_em) ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(out->Eft_mod, dev + o_em, n_em * 8, hipMemcpyDeviceToHost));
+  if (n_vm) ENTRY_HIP(nagp_reconstruct_sources, hipMemcpy(out->Varft_mod, dev + o_vm, n_vm * 8, hipMemcpyDeviceToHost));
   (void)hipFree(dev);
   return st;
 }
 
+#undef ENTRY_HIP

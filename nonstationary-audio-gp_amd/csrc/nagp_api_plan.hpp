@@ -307,9 +307,11 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
     // fixed-site launches with one tile per thread: whole waves beyond the tile threads for the state lanes (gf_filter_kernel: soff)
     p->NT_fl = p->NT_f;
     if (!ekf && p->TPT_f == 1 && roundup64(slots) + roundup64(sh.S) <= 512) p->NT_fl = std::max(p->NT_f, roundup64(slots) + roundup64(sh.S));
-    // split blocks: every filter launch has the geometry of the fixed-site one (gf_filter_kernel<TPT_f, ., ., 512, 0, true>)
+    // split blocks: every filter launch has the geometry of the fixed-site one (the CPL instantiations of gf_filter_kernel, TPT_f tiles per thread under the 512-thread bound)
     // (fixed-site launches of 513 .. 1024 lower tiles: one tile per thread under the 768- / 1024-thread bound, as for unsplit models)
     if (split) { p->TPT_a = p->TPT_f; p->NT_a = p->NT_f; p->LB_a = 512; p->NT_l = p->wide_l ? roundup64(slots) : p->NT_f; p->NT_fl = p->NT_f; }
+    // 768-thread bound when the tiles fit: three waves per SIMD = 168 registers per lane (no spills; 30 spilled at the 1024 bound)
+    p->LB_l = !p->wide_l ? 512 : (p->NT_l <= 768 ? 768 : 1024);
   }
   p->want_PS = (o->flags & 0x4u) != 0;
   p->need_PF = (o->kind != NAGP_KIND_IHGP) && !(o->mode == NAGP_MODE_NLML && (o->ep_itts == 1 || ekf));
@@ -724,7 +726,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
     p->lds_ih = ihgp_filter_lds_doubles(sh, t, p->tb.NG, p->hph_lds, p->kb_ih) * sizeof(double);
     if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp filter: LDS %zu B, hph table in LDS %d, cubature tables in LDS %d, block-structured mom %d, mom LDS %zu B\n", p->lds_ih, p->hph_lds, p->cache_f, p->src_f, mom_lds_doubles(t) * sizeof(double));
     // the ADF sweep in the sparse-point form (ihgp_adf_kernel): plain NMF likelihood, <= 320 sigma points, unstructured Wnmf
-    // (plans with a block of 5 .. 8 states, BS = 8: the general ADF kernel ihgp_filter_kernel<MV, false, 8>; the affine scans are instantiated for both strides)
+    // (plans with a block of 5 .. 8 states, BS = 8: the general ADF kernel ihgp_filter_kernel at block stride 8; the affine scans are instantiated for both strides)
     if (sh.BS == 4 && p->sp.enabled && !p->src_f && sh.M <= 64 && sh.D <= 4 * MSP_DT && o->n_pts <= MSP_NT + 64 && (o->n_pts + 3) / 4 <= MSP_NW * MSP_NST) {
       p->kb_sp = IH_KB; p->hph_sp = 1;
       auto need = [&]() { return ihgp_adf_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16; };
@@ -732,20 +734,12 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
       if (need() > 156 * 1024) p->hph_sp = 0;
       if (need() <= 156 * 1024) {
         p->sp_ih = 1; p->lds_sp = need();
-        switch (o->cub_dim) {
-          case 1: PLAN_TRY(set_lds(ihgp_adf_kernel<1>, p->lds_sp)); break; case 2: PLAN_TRY(set_lds(ihgp_adf_kernel<2>, p->lds_sp)); break;
-          case 3: PLAN_TRY(set_lds(ihgp_adf_kernel<3>, p->lds_sp)); break; case 4: PLAN_TRY(set_lds(ihgp_adf_kernel<4>, p->lds_sp)); break;
-          case 5: PLAN_TRY(set_lds(ihgp_adf_kernel<5>, p->lds_sp)); break; case 6: PLAN_TRY(set_lds(ihgp_adf_kernel<6>, p->lds_sp)); break;
-          default: PLAN_TRY(set_lds(ihgp_adf_kernel<7>, p->lds_sp)); break;
-        }
         // role-specialised waves: two serial + six worker waves, one sigma point per worker lane, the cubature sums from bin sums (msr_build_desc)
         const size_t need8 = ihgp_adf8_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16;
         if (p->sp.bdesc && need8 <= 156 * 1024 && dev.ih_roles) {
           p->sp_ih8 = 1; p->lds_sp8 = need8;
-#define SL8(V) do { if (dev.ih_tables) PLAN_TRY(set_lds((ihgp_adf8_kernel<V, true>), need8)); else PLAN_TRY(set_lds((ihgp_adf8_kernel<V, false>), need8)); } while (0)
-          switch (o->cub_dim) { case 1: SL8(1); break; case 2: SL8(2); break; case 3: SL8(3); break; case 4: SL8(4); break; case 5: SL8(5); break; case 6: SL8(6); break; default: SL8(7); break; }
-#undef SL8
         }
+        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SP, o->cub_dim, p->sp_ih8, dev.ih_tables), p->sp_ih8 ? p->lds_sp8 : p->lds_sp));
       }
     }
     // likModulatorPreCalcwn: the role-specialised sweep of nagp_momsq.hpp
@@ -756,22 +750,18 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
       if (needq() > 156 * 1024) p->hph_sq = 0;
       if (needq() <= 156 * 1024) {
         p->sq_ih = 1; p->lds_sq = needq();
-        switch (o->cub_dim) {
-          case 1: PLAN_TRY(set_lds(ihgp_adf8sq_kernel<1>, p->lds_sq)); break; case 2: PLAN_TRY(set_lds(ihgp_adf8sq_kernel<2>, p->lds_sq)); break;
-          case 3: PLAN_TRY(set_lds(ihgp_adf8sq_kernel<3>, p->lds_sq)); break; case 4: PLAN_TRY(set_lds(ihgp_adf8sq_kernel<4>, p->lds_sq)); break;
-          case 5: PLAN_TRY(set_lds(ihgp_adf8sq_kernel<5>, p->lds_sq)); break; default: PLAN_TRY(set_lds(ihgp_adf8sq_kernel<6>, p->lds_sq)); break;
-        }
+        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SQ, o->cub_dim, true, false), p->lds_sq));
       }
     }
     if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);
     if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B)\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8);
-#define SL(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, false>, p->lds_ih))
-#define SLS(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, true>, p->lds_ih))
-#define SL8(V) PLAN_TRY(set_lds(ihgp_filter_kernel<V, false, 8>, p->lds_ih))
-    if (sh.BS == 8) { NAGP_MV_SWITCH9(mom_variant(mc), SL8) } else if (p->src_f) { NAGP_MV_SWITCH9(mom_variant(mc), SLS) } else { NAGP_MV_SWITCH9(mom_variant(mc), SL) }
-#undef SL
-#undef SLS
-#undef SL8
+    PLAN_TRY(set_kernel(p->k.ih_filter, pick_ih_filter(mom_variant(mc), p->src_f, sh.BS == 8), p->lds_ih));
+    for (int mode = 0; mode < 2; ++mode) {      // the affine scans and the sequential scan use no dynamic LDS
+      PLAN_TRY(set_kernel(p->k.aff_compose[mode], pick_aff_compose(mode, sh.BS), 0));
+      PLAN_TRY(set_kernel(p->k.aff_boundary[mode], pick_aff_boundary(mode, sh.BS), 0));
+      PLAN_TRY(set_kernel(p->k.aff_apply[mode], pick_aff_apply(mode, sh.BS), 0));
+    }
+    PLAN_TRY(set_kernel(p->k.ih_scan, pick_ih_scan(sh.BS), 0));
   } else {
     if (!ekf) p->DG_f = pick_DG(o->lik_kind, o->n_pts, p->NT_a, sh.D, o->cub_dim);
     MomCfg t = mc; t.DG = p->DG_f; t.cache_tabs = ekf ? 0 : 1; t.store_a = (!ekf && o->lik_kind == NAGP_LIK_POWER_NMF_SQRT) ? 1 : 0;
@@ -814,105 +804,25 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
       if (need <= cap) {
         p->a8_gf = 1; p->lds_a8 = need;
         if (p->pipeline && B <= 128) p->lds_a8 = 160 * 1024;      // (the whole LDS of the CU, as for the other filter launches below)
-#define SA8(TP, V) do { if (p->a8_st) PLAN_TRY(set_lds((gf_adf8_kernel<2, V, true>), p->lds_a8)); else PLAN_TRY(set_lds((gf_adf8_kernel<TP, V, false>), p->lds_a8)); } while (0)
-#define SA8V(TP) switch (o->cub_dim) { case 1: SA8(TP, 1); break; case 2: SA8(TP, 2); break; case 3: SA8(TP, 3); break; \
-          case 4: SA8(TP, 4); break; case 5: SA8(TP, 5); break; case 6: SA8(TP, 6); break; default: SA8(TP, 7); break; }
-        if (p->a8_tpt == 1) SA8V(1) else SA8V(2)
-#undef SA8V
-#undef SA8
+        PLAN_TRY(set_kernel(p->k.adf8, pick_gf_adf8(p->a8_tpt, o->cub_dim, p->a8_st), p->lds_a8));
       }
     }
     if (dev.stamps) fprintf(stderr, "[nagp plan] gf ADF sweep with role-specialised waves: %d (tiles per thread %d, ring %d steps, LDS %zu B)\n", p->a8_gf, p->a8_tpt, p->kb_a8, p->lds_a8);
     p->lds_gain = (((p->TPT == 1) ? gain_lds_doubles_staged(sh) : gain_lds_doubles(sh)) + gain_cpl_doubles(sh)) * sizeof(double);     // (rts_gain_kernel: STAGE)
     p->lds_scan = span_lds_doubles(sh, p->LP1, p->LP2) * sizeof(double);
-    if (split) {
-      if (ekf) {
-        switch (p->TPT_f) {
-          case 1: PLAN_TRY(set_lds((gf_filter_kernel<1, 1, 0, 512, 0, true>), p->lds_filter)); break;
-          case 2: PLAN_TRY(set_lds((gf_filter_kernel<2, 1, 0, 512, 0, true>), p->lds_filter)); break;
-          default: PLAN_TRY(set_lds((gf_filter_kernel<4, 1, 0, 512, 0, true>), p->lds_filter)); break;
-        }
-      } else {
-#define SLC1(V) PLAN_TRY(set_lds((gf_filter_kernel<1, 0, V, 512, 0, true>), p->lds_filter))
-#define SLC2(V) PLAN_TRY(set_lds((gf_filter_kernel<2, 0, V, 512, 0, true>), p->lds_filter))
-#define SLC4(V) PLAN_TRY(set_lds((gf_filter_kernel<4, 0, V, 512, 0, true>), p->lds_filter))
-        switch (p->TPT_f) {
-          case 1: NAGP_MV_SWITCH(mom_variant(mc), SLC1) SLC1(-1); break;
-          case 2: NAGP_MV_SWITCH(mom_variant(mc), SLC2) SLC2(-1); break;
-          default: NAGP_MV_SWITCH(mom_variant(mc), SLC4) SLC4(-1); break;
-        }
-        if (p->wide_l && p->NT_l <= 768) PLAN_TRY(set_lds((gf_filter_kernel<1, 0, -1, 768, 0, true>), p->lds_filter));
-        else if (p->wide_l) PLAN_TRY(set_lds((gf_filter_kernel<1, 0, -1, 1024, 0, true>), p->lds_filter));
-#undef SLC1
-#undef SLC2
-#undef SLC4
-      }
-      switch (p->TPT) {
-        case 1: PLAN_TRY(set_lds((rts_gain_kernel<1, 512, true>), p->lds_gain)); break;
-        case 2: PLAN_TRY(set_lds((rts_gain_kernel<2, 512, true>), p->lds_gain)); break;
-        case 3: PLAN_TRY(set_lds((rts_gain_kernel<3, 512, true>), p->lds_gain)); break;
-        case 4: PLAN_TRY(set_lds((rts_gain_kernel<4, 512, true>), p->lds_gain)); break;
-        default: PLAN_TRY(set_lds((rts_gain_kernel<8, 512, true>), p->lds_gain)); break;      // (46 .. 64 tile rows: tiles in scratch, as for unsplit models)
-      }
-    }
-    if (ekf) {
-      switch (p->TPT_f) {
-        case 1: PLAN_TRY(set_lds(gf_filter_kernel<1, 1, 0>, p->lds_filter)); break;
-        case 2: PLAN_TRY(set_lds(gf_filter_kernel<2, 1, 0>, p->lds_filter)); break;
-        default: PLAN_TRY(set_lds(gf_filter_kernel<4, 1, 0>, p->lds_filter)); break;
-      }
-    } else {
-#define SL1(V) PLAN_TRY(set_lds(gf_filter_kernel<1, 0, V, 256>, p->lds_filter))
-#define SL2(V) PLAN_TRY(set_lds(gf_filter_kernel<2, 0, V, 256>, p->lds_filter))
-#define SL3(V) PLAN_TRY(set_lds(gf_filter_kernel<3, 0, V, 256>, p->lds_filter))
-#define SL4(V) PLAN_TRY(set_lds(gf_filter_kernel<4, 0, V, 256>, p->lds_filter))
-#define SL5(V) PLAN_TRY(set_lds(gf_filter_kernel<4, 0, V, 512>, p->lds_filter))
-#define NAGP_SP_SWITCH(TP, CALLSP) switch (mom_variant(mc)) { case 1: CALLSP(TP, 1); break; case 2: CALLSP(TP, 2); break; case 3: CALLSP(TP, 3); break; \
-        case 4: CALLSP(TP, 4); break; case 5: CALLSP(TP, 5); break; case 6: CALLSP(TP, 6); break; default: CALLSP(TP, 7); break; }
-#define SLSP(TP, V) PLAN_TRY(set_lds(gf_filter_kernel<TP, 0, V, 256, 1>, p->lds_filter))
-#define NAGP_SQ_SWITCH(TP, CALLSQ) switch (mom_variant(mc)) { case 1: CALLSQ(TP, 1); break; case 2: CALLSQ(TP, 2); break; case 3: CALLSQ(TP, 3); break; \
-        case 4: CALLSQ(TP, 4); break; case 5: CALLSQ(TP, 5); break; default: CALLSQ(TP, 6); break; }
-#define SLSQ(TP, V) PLAN_TRY(set_lds(gf_filter_kernel<TP, 0, V, 256, 2>, p->lds_filter))
-      if (p->sq_gf) {
-        switch (p->TPT_a) { case 1: NAGP_SQ_SWITCH(1, SLSQ) break; case 2: NAGP_SQ_SWITCH(2, SLSQ) break; case 3: NAGP_SQ_SWITCH(3, SLSQ) break; default: NAGP_SQ_SWITCH(4, SLSQ) break; }
-      } else
-#undef SLSQ
-      if (p->sp_gf) {
-        switch (p->TPT_a) { case 1: NAGP_SP_SWITCH(1, SLSP) break; case 2: NAGP_SP_SWITCH(2, SLSP) break; case 3: NAGP_SP_SWITCH(3, SLSP) break; default: NAGP_SP_SWITCH(4, SLSP) break; }
-      } else if (p->LB_a == 512) { NAGP_MV_SWITCH(mom_variant(mc), SL5) }
-      else switch (p->TPT_a) {
-        case 1: NAGP_MV_SWITCH(mom_variant(mc), SL1) break;
-        case 2: NAGP_MV_SWITCH(mom_variant(mc), SL2) break;
-        case 3: NAGP_MV_SWITCH(mom_variant(mc), SL3) break;
-        default: NAGP_MV_SWITCH(mom_variant(mc), SL4) break;
-      }
-#undef SLSP
-      // 768-thread bound when the tiles fit: three waves per SIMD = 168 registers per lane (no spills; 30 spilled at the 1024 bound)
-      if (p->wide_l && p->NT_l <= 768) PLAN_TRY(set_lds(gf_filter_kernel<1, 0, -1, 768>, p->lds_filter));
-      else if (p->wide_l) PLAN_TRY(set_lds(gf_filter_kernel<1, 0, -1, 1024>, p->lds_filter));
-      else switch (p->TPT_f) {   // mom-free kernel of the fixed-site steps
-        case 1: PLAN_TRY(set_lds(gf_filter_kernel<1, 0, -1>, p->lds_filter)); break;
-        case 2: PLAN_TRY(set_lds(gf_filter_kernel<2, 0, -1>, p->lds_filter)); break;
-        default: PLAN_TRY(set_lds(gf_filter_kernel<4, 0, -1>, p->lds_filter)); break;
-      }
-#undef SL1
-#undef SL2
-#undef SL3
-#undef SL4
-#undef SL5
+    if (ekf) PLAN_TRY(set_kernel(p->k.ekf, pick_gf_ekf(p->TPT_f, split), p->lds_filter));
+    else {
+      const MomForm form = p->sq_gf ? FORM_SQ : (p->sp_gf ? FORM_SP : FORM_GENERAL);      // (neither with split blocks)
+      PLAN_TRY(set_kernel(p->k.adf, pick_gf_adf(p->TPT_a, p->LB_a, mom_variant(mc), form, split), p->lds_filter));
+      PLAN_TRY(set_kernel(p->k.fixed, pick_gf_fixed(p->TPT_f, p->LB_l, split, false), p->lds_filter));   // mom-free kernel of the fixed-site steps
     }
     if (!split && nt > 1024 && nt <= 1536 && sh.M * (sh.M + 1) / 2 <= 768 && sh.S <= 768 && !dev.no_gain768) {
       p->gain768 = 1;
       p->lds_gain = gain_lds_doubles_staged(sh) * sizeof(double);
-      PLAN_TRY(set_lds(rts_gain_kernel<2, 768>, p->lds_gain));
     }
-    switch (p->TPT) {
-      case 1: PLAN_TRY(set_lds(rts_gain_kernel<1>, p->lds_gain)); PLAN_TRY(set_lds(rts_compose_kernel<1>, p->lds_scan)); PLAN_TRY(set_lds(rts_boundary_kernel<1>, p->lds_scan)); PLAN_TRY(set_lds(rts_apply_kernel<1>, p->lds_scan)); break;
-      case 2: PLAN_TRY(set_lds(rts_gain_kernel<2>, p->lds_gain)); PLAN_TRY(set_lds(rts_compose_kernel<2>, p->lds_scan)); PLAN_TRY(set_lds(rts_boundary_kernel<2>, p->lds_scan)); PLAN_TRY(set_lds(rts_apply_kernel<2>, p->lds_scan)); break;
-      case 3: PLAN_TRY(set_lds(rts_gain_kernel<3>, p->lds_gain)); PLAN_TRY(set_lds(rts_compose_kernel<3>, p->lds_scan)); PLAN_TRY(set_lds(rts_boundary_kernel<3>, p->lds_scan)); PLAN_TRY(set_lds(rts_apply_kernel<3>, p->lds_scan)); break;
-      case 4: PLAN_TRY(set_lds(rts_gain_kernel<4>, p->lds_gain)); PLAN_TRY(set_lds(rts_compose_kernel<4>, p->lds_scan)); PLAN_TRY(set_lds(rts_boundary_kernel<4>, p->lds_scan)); PLAN_TRY(set_lds(rts_apply_kernel<4>, p->lds_scan)); break;
-      default: PLAN_TRY(set_lds(rts_gain_kernel<8>, p->lds_gain)); PLAN_TRY(set_lds(rts_compose_kernel<8>, p->lds_scan)); PLAN_TRY(set_lds(rts_boundary_kernel<8>, p->lds_scan)); PLAN_TRY(set_lds(rts_apply_kernel<8>, p->lds_scan)); break;
-    }
+    // (split blocks: the VALU gain kernel with the cross tiles; 8 tiles per thread = 46 .. 64 tile rows, tiles in scratch)
+    PLAN_TRY(set_kernel(p->k.gain, pick_gain(p->TPT, split ? GAIN_CPL : (p->gain768 ? GAIN_768 : GAIN_PLAIN)), p->lds_gain));
+    for (SpanPass pass : {SPAN_COMPOSE, SPAN_BOUNDARY, SPAN_APPLY}) PLAN_TRY(set_kernel(p->k.span[pass], pick_span(pass, p->TPT), p->lds_scan));
   }
   // rts_gain_mfma_kernel (16x16 tiles on the matrix cores, the dependence chain of the blocked Cholesky on a wave of its own) serves every
   // plan whose smoother passes take dense (G, Delta); NAGP_NO_GAIN_MFMA=1 (developer switch) keeps the 4x4-tile VALU kernel
@@ -964,20 +874,12 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
         PLAN_HIP(hipStreamSynchronize(p->stream));
       }
     }
-#define SETG(N) PLAN_TRY(set_lds((rts_gain_mfma_kernel<N, false>), lg)); PLAN_TRY(set_lds((rts_gain_mfma_kernel<N, true>), lg))
-    switch (p->mfma_sp / 16) { case 1: SETG(1); break; case 2: SETG(2); break; case 3: SETG(3); break; case 4: SETG(4); break; case 5: SETG(5); break;
-                               case 6: SETG(6); break; case 7: SETG(7); break; case 8: SETG(8); break; case 9: SETG(9); break; default: SETG(10); break; }
-#undef SETG
+    PLAN_TRY(set_kernel(p->k.gain_mfma, pick_gain_mfma(p->mfma_sp / 16, p->gain_inv), lg));
   }
-  if (p->big_sp) {
-#define SETB(N) PLAN_TRY(set_lds(rts_big_kernel<N, 0>, p->lds_mfma)); PLAN_TRY(set_lds(rts_big_kernel<N, 1>, p->lds_mfma)); \
-    PLAN_TRY(set_lds(rts_big_kernel<N, 2>, p->lds_mfma)); PLAN_TRY(set_lds(rts_big_phi_kernel<N>, p->lds_mfma))
-    switch (p->mfma_sp / 16) { case 5: SETB(5); break; case 6: SETB(6); break; case 7: SETB(7); break; case 8: SETB(8); break; case 9: SETB(9); break; default: SETB(10); break; }
-#undef SETB
-  } else if (p->mfma_sp) {
-#define SETM(N) PLAN_TRY(set_lds(rts_compose_mfma_kernel<N>, p->lds_mfma)); PLAN_TRY(set_lds(rts_boundary_mfma_kernel<N>, p->lds_mfma)); PLAN_TRY(set_lds(rts_apply_mfma_kernel<N>, p->lds_mfma))
-    switch (p->mfma_sp / 16) { case 1: SETM(1); break; case 2: SETM(2); break; case 3: SETM(3); break; case 4: SETM(4); break; case 5: SETM(5); break; default: SETM(6); break; }
-#undef SETM
+  if (p->mfma_sp) {
+    for (SpanPass pass : {SPAN_COMPOSE, SPAN_BOUNDARY, SPAN_APPLY})
+      PLAN_TRY(set_kernel(p->k.span_m[pass], p->big_sp ? pick_span_big(pass, p->mfma_sp / 16) : pick_span_mfma(pass, p->mfma_sp / 16), p->lds_mfma));
+    if (p->big_sp) PLAN_TRY(set_kernel(p->k.big_phi, pick_big_phi(p->mfma_sp / 16), p->lds_mfma));
   }
   if (!ekf) {
     p->DG_ep = pick_DG(o->lik_kind, o->n_pts, 256, sh.D, o->cub_dim);
@@ -990,26 +892,20 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
     if (!p->src_ep && ep_lds_doubles(sh, t) * sizeof(double) > 64 * 1024) t.cache_tabs = 0;
     p->cache_ep = t.cache_tabs; p->sta_ep = t.store_a;
     p->lds_ep = ep_lds_doubles(sh, t) * sizeof(double);
-#define SL(V) PLAN_TRY(set_lds(ep_site_kernel<V>, p->lds_ep))
-    NAGP_MV_SWITCH9(mom_variant(mc), SL)
-#undef SL
     // site refresh in the staged sparse-point form (the conditions of the ADF launches: likModulatorNMFPower on a fully symmetric rule)
     if (!split && p->sp.enabled && !p->src_ep && sh.M <= 64 && sh.D <= 4 * MSP_DT && o->cub_dim <= MSP_MAXCD && o->n_pts <= MSP_NT + 64 &&
         (o->n_pts + 3) / 4 <= MSP_NW * MSP_NST && !dev.no_sparse_ep) {
       p->sp_ep = 1;
       p->lds_ep_sp = ep_sp_lds_doubles(sh, o->cub_dim) * sizeof(double);
-#define SLS(V) PLAN_TRY(set_lds(ep_site_sp_kernel<V>, p->lds_ep_sp))
-      switch (o->cub_dim) { case 1: SLS(1); break; case 2: SLS(2); break; case 3: SLS(3); break; case 4: SLS(4); break; case 5: SLS(5); break; case 6: SLS(6); break; default: SLS(7); break; }
-#undef SLS
     }
     // ... and with likModulatorPreCalcwn in the staged form of nagp_momsq.hpp
     if (!split && p->sq_ok && !p->src_ep && sh.M <= 64 && !dev.no_sparse_ep) {
       p->sq_ep = 1;
       p->lds_ep_sq = ep_sq_lds_doubles(sh, o->cub_dim) * sizeof(double);
-#define SLQ(V) PLAN_TRY(set_lds(ep_site_sq_kernel<V>, p->lds_ep_sq))
-      switch (o->cub_dim) { case 1: SLQ(1); break; case 2: SLQ(2); break; case 3: SLQ(3); break; case 4: SLQ(4); break; case 5: SLQ(5); break; default: SLQ(6); break; }
-#undef SLQ
     }
+    if (p->sq_ep) PLAN_TRY(set_kernel(p->k.site, pick_ep_site(FORM_SQ, o->cub_dim), p->lds_ep_sq));
+    else if (p->sp_ep) PLAN_TRY(set_kernel(p->k.site, pick_ep_site(FORM_SP, o->cub_dim), p->lds_ep_sp));
+    else PLAN_TRY(set_kernel(p->k.site, pick_ep_site(FORM_GENERAL, mom_variant(mc)), p->lds_ep));
   }
   p->nlZ.assign((size_t)B * o->ep_itts, 0.0);
   p->mdM.assign((size_t)B * o->ep_itts, 0.0);

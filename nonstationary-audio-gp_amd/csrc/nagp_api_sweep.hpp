@@ -18,88 +18,26 @@ static int launch_filter(nagp_plan* p, const FilterPar& fp_in, int n_win = 0) {
   int nt_ekf = p->NT_f;
   if (ekf && p->NT_f + 64 <= 512 && p->sh.N <= 64) { nt_ekf = p->NT_f + 64; fp.spl_wave = 1; }   // one extra wave for the link
   Timed t(p, adf ? NAGP_K_FILTER : NAGP_K_FILTER_LIN);
-  dim3 g(p->B), bl(p->NT_f);
-  const dim3 gw(p->B, n_win > 0 ? n_win : 1);
-  // fixed-site launches (no step calls mom): the sequential kernel, or its windowed instantiation
-#define LFIX(TP, LBV, CP, NTH) do { \
-    if (n_win > 0) hipLaunchKernelGGL((gf_filter_kernel<TP, 0, -1, LBV, 0, CP, true>), gw, dim3(NTH), p->lds_filter, p->stream, p->sh, p->b, mc, fp); \
-    else hipLaunchKernelGGL((gf_filter_kernel<TP, 0, -1, LBV, 0, CP>), g, dim3(NTH), p->lds_filter, p->stream, p->sh, p->b, mc, fp); } while (0)
   if (n_win > 0 && adf) FAIL(NAGP_EINVAL, "windowed launch of a pass that calls mom");
+  const dim3 g(p->B, n_win > 0 ? n_win : 1);
+  const Kern<GfFn>* k; int nth;
+  if (ekf) { k = &p->k.ekf; nth = nt_ekf; }
+  else if (adf && p->a8_gf && fp.mom_all && fp.k_end - fp.k_begin > 1) {
+    // sweep 1 (mom at every step): role-specialised waves
+    k = &p->k.adf8; nth = MSR_NT;
+    fp.kb = p->kb_a8; mc.sp = p->sp;
+  } else if (adf) { k = &p->k.adf; nth = p->NT_a; }
+  else {
+    // fixed-site launches (no step calls mom): the sequential kernel, or its windowed instantiation
+    // (NT_fl differs from NT_f only for the one-tile-per-thread launches of unsplit models)
+    k = n_win > 0 ? &p->k.fixed_win : &p->k.fixed; nth = p->wide_l ? p->NT_l : p->NT_fl;
+  }
   if (p->sh.Ms < p->sh.M) {      // split blocks: one geometry (the fixed-site one) for every launch, the general mom code
     fp.cpl_doubles = (int)filter_cpl_doubles(p->sh); fp.cpl_chunk = filter_cpl_chunk(p->sh);
     mc.sp = MomSp{};
-#define LFC(TP, ME, V) hipLaunchKernelGGL((gf_filter_kernel<TP, ME, V, 512, 0, true>), g, dim3(ekf ? nt_ekf : p->NT_f), p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-#define LFC1(V) LFC(1, 0, V)
-#define LFC2(V) LFC(2, 0, V)
-#define LFC4(V) LFC(4, 0, V)
-    if (ekf) switch (p->TPT_f) { case 1: LFC(1, 1, 0); break; case 2: LFC(2, 1, 0); break; default: LFC(4, 1, 0); break; }
-    else if (adf) switch (p->TPT_f) { case 1: NAGP_MV_SWITCH(mom_variant(mc), LFC1) break; case 2: NAGP_MV_SWITCH(mom_variant(mc), LFC2) break; default: NAGP_MV_SWITCH(mom_variant(mc), LFC4) break; }
-    else if (p->wide_l && p->NT_l <= 768) LFIX(1, 768, true, p->NT_l);
-    else if (p->wide_l) LFIX(1, 1024, true, p->NT_l);
-    else switch (p->TPT_f) { case 1: LFIX(1, 512, true, p->NT_f); break; case 2: LFIX(2, 512, true, p->NT_f); break; default: LFIX(4, 512, true, p->NT_f); break; }
-#undef LFC
-#undef LFC1
-#undef LFC2
-#undef LFC4
-  } else
-  if (ekf) {
-#define LF(TP) hipLaunchKernelGGL((gf_filter_kernel<TP, 1, 0>), g, dim3(nt_ekf), p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-    switch (p->TPT_f) { case 1: LF(1); break; case 2: LF(2); break; default: LF(4); break; }
-#undef LF
-  } else {
-    if (adf && p->a8_gf && fp.mom_all && fp.k_end - fp.k_begin > 1) {
-      // sweep 1 (mom at every step): role-specialised waves
-      FilterPar fa = fp; fa.kb = p->kb_a8;
-      MomCfg ma = mc; ma.sp = p->sp;
-#define LA8(TP, V) do { if (p->a8_st) hipLaunchKernelGGL((gf_adf8_kernel<2, V, true>), g, dim3(MSR_NT), p->lds_a8, p->stream, p->sh, p->b, ma, fa); \
-        else hipLaunchKernelGGL((gf_adf8_kernel<TP, V, false>), g, dim3(MSR_NT), p->lds_a8, p->stream, p->sh, p->b, ma, fa); } while (0)
-#define LA8V(TP) switch (mc.cdim) { case 1: LA8(TP, 1); break; case 2: LA8(TP, 2); break; case 3: LA8(TP, 3); break; \
-        case 4: LA8(TP, 4); break; case 5: LA8(TP, 5); break; case 6: LA8(TP, 6); break; default: LA8(TP, 7); break; }
-      if (p->a8_tpt == 1) LA8V(1) else LA8V(2)
-#undef LA8V
-#undef LA8
-    } else
-    if (adf) {
-      dim3 ba(p->NT_a);
-#define LF1(V) hipLaunchKernelGGL((gf_filter_kernel<1, 0, V, 256>), g, ba, p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-#define LF2(V) hipLaunchKernelGGL((gf_filter_kernel<2, 0, V, 256>), g, ba, p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-#define LF3(V) hipLaunchKernelGGL((gf_filter_kernel<3, 0, V, 256>), g, ba, p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-#define LF4(V) hipLaunchKernelGGL((gf_filter_kernel<4, 0, V, 256>), g, ba, p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-#define LF5(V) hipLaunchKernelGGL((gf_filter_kernel<4, 0, V, 512>), g, ba, p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-#define LFSP(TP, V) hipLaunchKernelGGL((gf_filter_kernel<TP, 0, V, 256, 1>), g, ba, p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-#define LFSQ(TP, V) hipLaunchKernelGGL((gf_filter_kernel<TP, 0, V, 256, 2>), g, ba, p->lds_filter, p->stream, p->sh, p->b, mc, fp)
-      if (p->sq_gf) {
-        switch (p->TPT_a) { case 1: NAGP_SQ_SWITCH(1, LFSQ) break; case 2: NAGP_SQ_SWITCH(2, LFSQ) break; case 3: NAGP_SQ_SWITCH(3, LFSQ) break; default: NAGP_SQ_SWITCH(4, LFSQ) break; }
-      } else
-#undef LFSQ
-      if (p->sp_gf) {
-        switch (p->TPT_a) { case 1: NAGP_SP_SWITCH(1, LFSP) break; case 2: NAGP_SP_SWITCH(2, LFSP) break; case 3: NAGP_SP_SWITCH(3, LFSP) break; default: NAGP_SP_SWITCH(4, LFSP) break; }
-      } else
-#undef LFSP
-      if (p->LB_a == 512) { NAGP_MV_SWITCH(mom_variant(mc), LF5) }
-      else switch (p->TPT_a) {
-        case 1: NAGP_MV_SWITCH(mom_variant(mc), LF1) break;
-        case 2: NAGP_MV_SWITCH(mom_variant(mc), LF2) break;
-        case 3: NAGP_MV_SWITCH(mom_variant(mc), LF3) break;
-        default: NAGP_MV_SWITCH(mom_variant(mc), LF4) break;
-      }
-#undef LF1
-#undef LF2
-#undef LF3
-#undef LF4
-#undef LF5
-    } else if (p->wide_l) {
-      if (p->NT_l <= 768) LFIX(1, 768, false, p->NT_l);
-      else LFIX(1, 1024, false, p->NT_l);
-    } else {   // no step of this launch calls mom
-      switch (p->TPT_f) {
-        case 1: LFIX(1, 512, false, p->NT_fl); break;
-        case 2: LFIX(2, 512, false, p->NT_f); break;
-        default: LFIX(4, 512, false, p->NT_f); break;
-      }
-    }
   }
-#undef LFIX
+  if (!k->fn) FAIL(NAGP_EINVAL, "filter launch of a kind the plan was not set up for");
+  hipLaunchKernelGGL(k->fn, g, dim3(nth), k->lds, p->stream, p->sh, p->b, mc, fp);
   HIP_TRY(hipGetLastError());
   return NAGP_OK;
 }
@@ -219,32 +157,12 @@ static int launch_gain_chunk(nagp_plan* p, const SweepCtx& sc, int c, int slot, 
   dim3 gr(g.nk, p->B), bl(p->NT);
   if (gp.dense_sp && p->gain_mfma) {
     const int ntl = p->mfma_sp / 16;
-    const size_t lg = gainm_lds_doubles(ntl, sh) * sizeof(double);
     const dim3 gr8((unsigned)((g.nk + 7) / 8 * 8), (unsigned)p->B);      // (the steps of one XCD contiguous: nagp_gain_mfma.hpp)
     gp.ainv = p->gain_inv ? p->d_ainv : nullptr;
-#define LG(N) do { if (p->gain_inv) hipLaunchKernelGGL((rts_gain_mfma_kernel<N, true>), gr8, dim3(64 * (N + 1)), lg, st, sh, b, gp); \
-                   else hipLaunchKernelGGL((rts_gain_mfma_kernel<N, false>), gr8, dim3(64 * (N + 1)), lg, st, sh, b, gp); } while (0)
-    switch (ntl) { case 1: LG(1); break; case 2: LG(2); break; case 3: LG(3); break; case 4: LG(4); break; case 5: LG(5); break;
-                   case 6: LG(6); break; case 7: LG(7); break; case 8: LG(8); break; case 9: LG(9); break; default: LG(10); break; }
-#undef LG
-  } else
-  if (sh.Ms < sh.M) {      // split blocks
-    gp.cpl_doubles = (int)gain_cpl_doubles(sh);
-    switch (p->TPT) {
-      case 1: hipLaunchKernelGGL((rts_gain_kernel<1, 512, true>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-      case 2: hipLaunchKernelGGL((rts_gain_kernel<2, 512, true>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-      case 3: hipLaunchKernelGGL((rts_gain_kernel<3, 512, true>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-      case 4: hipLaunchKernelGGL((rts_gain_kernel<4, 512, true>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-      default: hipLaunchKernelGGL((rts_gain_kernel<8, 512, true>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-    }
-  } else
-  if (p->gain768) hipLaunchKernelGGL((rts_gain_kernel<2, 768>), gr, dim3(768), p->lds_gain, st, sh, b, gp);
-  else switch (p->TPT) {
-    case 1: hipLaunchKernelGGL((rts_gain_kernel<1>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-    case 2: hipLaunchKernelGGL((rts_gain_kernel<2>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-    case 3: hipLaunchKernelGGL((rts_gain_kernel<3>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-    case 4: hipLaunchKernelGGL((rts_gain_kernel<4>), gr, bl, p->lds_gain, st, sh, b, gp); break;
-    default: hipLaunchKernelGGL((rts_gain_kernel<8>), gr, bl, p->lds_gain, st, sh, b, gp); break;
+    hipLaunchKernelGGL(p->k.gain_mfma.fn, gr8, dim3(64 * (ntl + 1)), p->k.gain_mfma.lds, st, sh, b, gp);
+  } else {
+    if (sh.Ms < sh.M) gp.cpl_doubles = (int)gain_cpl_doubles(sh);      // split blocks
+    hipLaunchKernelGGL(p->k.gain.fn, gr, p->gain768 ? dim3(768) : bl, p->k.gain.lds, st, sh, b, gp);
   }
   HIP_TRY(hipGetLastError());
   return NAGP_OK;
@@ -272,32 +190,23 @@ static MfmaPar mfma_par(nagp_plan* p, const SweepCtx& sc, int c, int slot) {
   return mp;
 }
 
+// workgroup of the MFMA span passes: a wave per 16 columns for the column-owner kernels, else 256 threads
+static dim3 span_m_block(const nagp_plan* p, const SweepCtx& sc) { return dim3(sc.mode == SM_BIG ? 64 * (p->mfma_sp / 16) : 256); }
+
 // pass 1 of the span scheme (one workgroup per span): reads the chunk's (G, Delta, delta), writes its (Phi, C, c)
 static int launch_compose_chunk(nagp_plan* p, const SweepCtx& sc, int c, int slot, hipStream_t st) {
   const Shape& sh = p->sh; const ChunkGeom& g = sc.ch[c];
   Bufs b = p->b; b.Gbuf = p->slotG[slot]; b.dbuf = p->slotD[slot]; b.gpstride = p->slot_gps[slot];
   Timed t(p, NAGP_K_SCAN, st);
-  if (sc.mode == SM_BIG) {
-    MfmaPar mp = mfma_par(p, sc, c, slot);
-    const int ntl = p->mfma_sp / 16;
-    dim3 gr(g.ns, p->B), bl(64 * ntl);
-#define LB(N) do { \
-      hipLaunchKernelGGL((rts_big_phi_kernel<N>), gr, bl, p->lds_mfma, st, sh, b, mp); \
-      hipLaunchKernelGGL((rts_big_kernel<N, 0>), gr, bl, p->lds_mfma, st, sh, b, mp); } while (0)
-    switch (ntl) { case 5: LB(5); break; case 6: LB(6); break; case 7: LB(7); break; case 8: LB(8); break; case 9: LB(9); break; default: LB(10); break; }
-#undef LB
-  } else if (sc.mode == SM_MFMA) {
-    MfmaPar mp = mfma_par(p, sc, c, slot);
-    dim3 gr(g.ns, p->B), bl(256);
-#define LM(N) hipLaunchKernelGGL((rts_compose_mfma_kernel<N>), gr, bl, p->lds_mfma, st, sh, b, mp)
-    switch (p->mfma_sp / 16) { case 1: LM(1); break; case 2: LM(2); break; case 3: LM(3); break; case 4: LM(4); break; case 5: LM(5); break; default: LM(6); break; }
-#undef LM
-  } else {
+  dim3 gr(g.ns, p->B);
+  if (sc.mode == SM_VALU) {
     SpanPar sp = span_par(p, sc, c, slot);
-    dim3 gr(g.ns, p->B), bl(p->NT);
-#define LS(TP) hipLaunchKernelGGL((rts_compose_kernel<TP>), gr, bl, p->lds_scan, st, sh, b, sp)
-    switch (p->TPT) { case 1: LS(1); break; case 2: LS(2); break; case 3: LS(3); break; case 4: LS(4); break; default: LS(8); break; }
-#undef LS
+    hipLaunchKernelGGL(p->k.span[SPAN_COMPOSE].fn, gr, dim3(p->NT), p->k.span[SPAN_COMPOSE].lds, st, sh, b, sp);
+  } else {
+    MfmaPar mp = mfma_par(p, sc, c, slot);
+    const dim3 bl = span_m_block(p, sc);
+    if (sc.mode == SM_BIG) hipLaunchKernelGGL(p->k.big_phi.fn, gr, bl, p->k.big_phi.lds, st, sh, b, mp);
+    hipLaunchKernelGGL(p->k.span_m[SPAN_COMPOSE].fn, gr, bl, p->k.span_m[SPAN_COMPOSE].lds, st, sh, b, mp);
   }
   HIP_TRY(hipGetLastError());
   return NAGP_OK;
@@ -310,25 +219,12 @@ static int launch_boundary_chunk(nagp_plan* p, const SweepCtx& sc, int c, int sl
   Bufs b = p->b; b.Gbuf = p->slotG[slot]; b.dbuf = p->slotD[slot]; b.gpstride = p->slot_gps[slot];
   Timed t(p, NAGP_K_SCAN, st);
   dim3 g2(p->B);
-  if (sc.mode == SM_BIG) {
-    MfmaPar mp = mfma_par(p, sc, c, slot);
-    const int ntl = p->mfma_sp / 16;
-    dim3 bl(64 * ntl);
-#define LB(N) hipLaunchKernelGGL((rts_big_kernel<N, 1>), g2, bl, p->lds_mfma, st, sh, b, mp)
-    switch (ntl) { case 5: LB(5); break; case 6: LB(6); break; case 7: LB(7); break; case 8: LB(8); break; case 9: LB(9); break; default: LB(10); break; }
-#undef LB
-  } else if (sc.mode == SM_MFMA) {
-    MfmaPar mp = mfma_par(p, sc, c, slot);
-    dim3 bl(256);
-#define LM(N) hipLaunchKernelGGL((rts_boundary_mfma_kernel<N>), g2, bl, p->lds_mfma, st, sh, b, mp)
-    switch (p->mfma_sp / 16) { case 1: LM(1); break; case 2: LM(2); break; case 3: LM(3); break; case 4: LM(4); break; case 5: LM(5); break; default: LM(6); break; }
-#undef LM
-  } else {
+  if (sc.mode == SM_VALU) {
     SpanPar sp = span_par(p, sc, c, slot);
-    dim3 bl(p->NT);
-#define LS(TP) hipLaunchKernelGGL((rts_boundary_kernel<TP>), g2, bl, p->lds_scan, st, sh, b, sp)
-    switch (p->TPT) { case 1: LS(1); break; case 2: LS(2); break; case 3: LS(3); break; case 4: LS(4); break; default: LS(8); break; }
-#undef LS
+    hipLaunchKernelGGL(p->k.span[SPAN_BOUNDARY].fn, g2, dim3(p->NT), p->k.span[SPAN_BOUNDARY].lds, st, sh, b, sp);
+  } else {
+    MfmaPar mp = mfma_par(p, sc, c, slot);
+    hipLaunchKernelGGL(p->k.span_m[SPAN_BOUNDARY].fn, g2, span_m_block(p, sc), p->k.span_m[SPAN_BOUNDARY].lds, st, sh, b, mp);
   }
   HIP_TRY(hipGetLastError());
   return NAGP_OK;
@@ -338,25 +234,13 @@ static int launch_apply_chunk(nagp_plan* p, const SweepCtx& sc, int c, int slot,
   const Shape& sh = p->sh; const ChunkGeom& g = sc.ch[c];
   Bufs b = p->b; b.Gbuf = p->slotG[slot]; b.dbuf = p->slotD[slot]; b.gpstride = p->slot_gps[slot];
   Timed t(p, NAGP_K_SCAN, st);
-  if (sc.mode == SM_BIG) {
-    MfmaPar mp = mfma_par(p, sc, c, slot);
-    const int ntl = p->mfma_sp / 16;
-    dim3 gr(g.ns, p->B), bl(64 * ntl);
-#define LB(N) hipLaunchKernelGGL((rts_big_kernel<N, 2>), gr, bl, p->lds_mfma, st, sh, b, mp)
-    switch (ntl) { case 5: LB(5); break; case 6: LB(6); break; case 7: LB(7); break; case 8: LB(8); break; case 9: LB(9); break; default: LB(10); break; }
-#undef LB
-  } else if (sc.mode == SM_MFMA) {
-    MfmaPar mp = mfma_par(p, sc, c, slot);
-    dim3 gr(g.ns, p->B), bl(256);
-#define LM(N) hipLaunchKernelGGL((rts_apply_mfma_kernel<N>), gr, bl, p->lds_mfma, st, sh, b, mp)
-    switch (p->mfma_sp / 16) { case 1: LM(1); break; case 2: LM(2); break; case 3: LM(3); break; case 4: LM(4); break; case 5: LM(5); break; default: LM(6); break; }
-#undef LM
-  } else {
+  dim3 gr(g.ns, p->B);
+  if (sc.mode == SM_VALU) {
     SpanPar sp = span_par(p, sc, c, slot);
-    dim3 gr(g.ns, p->B), bl(p->NT);
-#define LS(TP) hipLaunchKernelGGL((rts_apply_kernel<TP>), gr, bl, p->lds_scan, st, sh, b, sp)
-    switch (p->TPT) { case 1: LS(1); break; case 2: LS(2); break; case 3: LS(3); break; case 4: LS(4); break; default: LS(8); break; }
-#undef LS
+    hipLaunchKernelGGL(p->k.span[SPAN_APPLY].fn, gr, dim3(p->NT), p->k.span[SPAN_APPLY].lds, st, sh, b, sp);
+  } else {
+    MfmaPar mp = mfma_par(p, sc, c, slot);
+    hipLaunchKernelGGL(p->k.span_m[SPAN_APPLY].fn, gr, span_m_block(p, sc), p->k.span_m[SPAN_APPLY].lds, st, sh, b, mp);
   }
   HIP_TRY(hipGetLastError());
   return NAGP_OK;
@@ -414,25 +298,12 @@ static int launch_apply_merged(nagp_plan* p, const SweepCtx& sc, int n_own, hipS
   Bufs b = p->b; b.Gbuf = p->slotG[sc.slot_of[0]]; b.dbuf = p->slotD[sc.slot_of[0]]; b.gpstride = p->slot_gps[sc.slot_of[0]];
   Timed t(p, NAGP_K_SCAN, st);
   dim3 gr(tot, p->B);
-  if (sc.mode == SM_BIG) {
-    MfmaPar mp = mfma_par(p, sc, 0, sc.slot_of[0]); mp.tab = p->h_tab; mp.ntab = n_own;
-    const int ntl = p->mfma_sp / 16;
-    dim3 bl(64 * ntl);
-#define LB(N) hipLaunchKernelGGL((rts_big_kernel<N, 2>), gr, bl, p->lds_mfma, st, sh, b, mp)
-    switch (ntl) { case 5: LB(5); break; case 6: LB(6); break; case 7: LB(7); break; case 8: LB(8); break; case 9: LB(9); break; default: LB(10); break; }
-#undef LB
-  } else if (sc.mode == SM_MFMA) {
-    MfmaPar mp = mfma_par(p, sc, 0, sc.slot_of[0]); mp.tab = p->h_tab; mp.ntab = n_own;
-    dim3 bl(256);
-#define LM(N) hipLaunchKernelGGL((rts_apply_mfma_kernel<N>), gr, bl, p->lds_mfma, st, sh, b, mp)
-    switch (p->mfma_sp / 16) { case 1: LM(1); break; case 2: LM(2); break; case 3: LM(3); break; case 4: LM(4); break; case 5: LM(5); break; default: LM(6); break; }
-#undef LM
-  } else {
+  if (sc.mode == SM_VALU) {
     SpanPar sp = span_par(p, sc, 0, sc.slot_of[0]); sp.tab = p->h_tab; sp.ntab = n_own;
-    dim3 bl(p->NT);
-#define LS(TP) hipLaunchKernelGGL((rts_apply_kernel<TP>), gr, bl, p->lds_scan, st, sh, b, sp)
-    switch (p->TPT) { case 1: LS(1); break; case 2: LS(2); break; case 3: LS(3); break; case 4: LS(4); break; default: LS(8); break; }
-#undef LS
+    hipLaunchKernelGGL(p->k.span[SPAN_APPLY].fn, gr, dim3(p->NT), p->k.span[SPAN_APPLY].lds, st, sh, b, sp);
+  } else {
+    MfmaPar mp = mfma_par(p, sc, 0, sc.slot_of[0]); mp.tab = p->h_tab; mp.ntab = n_own;
+    hipLaunchKernelGGL(p->k.span_m[SPAN_APPLY].fn, gr, span_m_block(p, sc), p->k.span_m[SPAN_APPLY].lds, st, sh, b, mp);
   }
   HIP_TRY(hipGetLastError());
   return NAGP_OK;
@@ -518,26 +389,10 @@ static int launch_ep(nagp_plan* p, double alpha, double damp, int clamp, int wri
   if (mixture_rule(p)) { ep.w_old = 1.0 - damp; ep.w_new = damp / alpha; }
   else { ep.w_old = 1.0 - damp * alpha; ep.w_new = damp; }
   Timed t(p, NAGP_K_EPSITE, st);
-  dim3 g((unsigned)((ep.k_end - ep.k_begin + ep.steps_per_wg - 1) / ep.steps_per_wg), p->B), bl(256);
-  if (p->sq_ep) {
-    MomCfg ms = mc; ms.sp = MomSp{}; ms.sp.c0 = p->sq_c0; ms.src = MomSrc{};
-#define LEQ(V) hipLaunchKernelGGL(ep_site_sq_kernel<V>, g, dim3(256), p->lds_ep_sq, st, sh, p->b, ms, ep)
-    switch (ms.cdim) { case 1: LEQ(1); break; case 2: LEQ(2); break; case 3: LEQ(3); break; case 4: LEQ(4); break; case 5: LEQ(5); break; default: LEQ(6); break; }
-#undef LEQ
-    HIP_TRY(hipGetLastError());
-    return NAGP_OK;
-  }
-  if (p->sp_ep) {
-    MomCfg ms = mc; ms.sp = p->sp; ms.src = MomSrc{};
-#define LES(V) hipLaunchKernelGGL(ep_site_sp_kernel<V>, g, dim3(MSP_NT), p->lds_ep_sp, st, sh, p->b, ms, ep)
-    switch (ms.cdim) { case 1: LES(1); break; case 2: LES(2); break; case 3: LES(3); break; case 4: LES(4); break; case 5: LES(5); break; case 6: LES(6); break; default: LES(7); break; }
-#undef LES
-    HIP_TRY(hipGetLastError());
-    return NAGP_OK;
-  }
-#define LE(V) hipLaunchKernelGGL(ep_site_kernel<V>, g, bl, p->lds_ep, st, sh, p->b, mc, ep)
-  NAGP_MV_SWITCH9(mom_variant(mc), LE)
-#undef LE
+  dim3 g((unsigned)((ep.k_end - ep.k_begin + ep.steps_per_wg - 1) / ep.steps_per_wg), p->B);
+  if (p->sq_ep) { mc.sp = MomSp{}; mc.sp.c0 = p->sq_c0; mc.src = MomSrc{}; }      // the staged forms (plan creation chose the kernel)
+  else if (p->sp_ep) { mc.sp = p->sp; mc.src = MomSrc{}; }
+  hipLaunchKernelGGL(p->k.site.fn, g, dim3(p->sp_ep && !p->sq_ep ? MSP_NT : 256), p->k.site.lds, st, sh, p->b, mc, ep);
   HIP_TRY(hipGetLastError());
   return NAGP_OK;
 }
@@ -859,19 +714,16 @@ static int exec_ihgp(nagp_plan* p) {
     ap.spanbuf = p->d_affspan; ap.bnd = p->d_affbnd; ap.vprev = p->d_vprev;
     const dim3 g((unsigned)((ap.ns * sh.M + 255) / 256), B), bl(256);
     Timed t(p, mode == 0 ? NAGP_K_FILTER_LIN : NAGP_K_SCAN);
-#define LAFF(MO, BSV) do { hipLaunchKernelGGL((ihgp_aff_compose_kernel<MO, BSV>), g, bl, 0, p->stream, sh, p->b, p->tb, ap); \
-                           hipLaunchKernelGGL((ihgp_aff_boundary_kernel<MO, BSV>), dim3(B), dim3(64), 0, p->stream, sh, p->b, ap, itt); \
-                           hipLaunchKernelGGL((ihgp_aff_apply_kernel<MO, BSV>), g, bl, 0, p->stream, sh, p->b, p->tb, ap); } while (0)
-    if (sh.BS == 8) { if (mode == 0) LAFF(0, 8); else LAFF(1, 8); }      // (blocks of 5 .. 8 states: 8 x 8 maps per thread)
-    else { if (mode == 0) LAFF(0, 4); else LAFF(1, 4); }
-#undef LAFF
+    const int mo = mode == 0 ? 0 : 1;
+    hipLaunchKernelGGL(p->k.aff_compose[mo].fn, g, bl, p->k.aff_compose[mo].lds, p->stream, sh, p->b, p->tb, ap);
+    hipLaunchKernelGGL(p->k.aff_boundary[mo].fn, dim3(B), dim3(64), p->k.aff_boundary[mo].lds, p->stream, sh, p->b, ap, itt);
+    hipLaunchKernelGGL(p->k.aff_apply[mo].fn, g, bl, p->k.aff_apply[mo].lds, p->stream, sh, p->b, p->tb, ap);
     HIP_TRY(hipGetLastError());
     return NAGP_OK;
   };
   for (int itt = 1; itt <= I; ++itt) {
     // forward: sweep 1 is the sequential ADF filter; later sweeps have fixed sites for k < T-1 (an affine
     // recursion, run parallel in time) and one ADF step at k = T-1
-    const bool seq8 = sh.BS == 8;     // blocks of 5 .. 8 states: the general ADF kernel at block stride 8
     const bool seq = p->dev.ih_seq && !p->sq_ih && !p->sp_ih && !p->src_f;      // developer switch: the sequential kernels (general ADF filter, ihgp_scan_kernel) for every sweep instead of the affine scans
     if (itt > 1 && !seq) RUN(affine(0, sh.T - 1, itt));
     IhgpPar ip{itt, p->damping[itt - 1], itt == 1 ? 1 : 0, (itt == 1 || seq) ? (int64_t)0 : (int64_t)(sh.T - 1)};
@@ -880,30 +732,12 @@ static int exec_ihgp(nagp_plan* p) {
     ip.w_old = 1.0 - ip.ep_damp; ip.w_new = mix ? ip.ep_damp / o.ep_fraction : ip.ep_damp; ip.mom_alpha = mix ? o.ep_fraction : 1.0;
     {
       Timed t(p, itt == 1 ? NAGP_K_FILTER : NAGP_K_FILTER_LIN);
-#define LI(V) hipLaunchKernelGGL((ihgp_filter_kernel<V, false>), dim3(B), dim3(p->NT_ih), p->lds_ih, p->stream, sh, p->b, mcf, p->tb, ip)
-#define LIS(V) hipLaunchKernelGGL((ihgp_filter_kernel<V, true>), dim3(B), dim3(p->NT_ih), p->lds_ih, p->stream, sh, p->b, mcf, p->tb, ip)
-      if (p->sq_ih) {
-        IhgpPar ia = ip; ia.hph_lds = p->hph_sq; ia.kb = p->kb_sq;
+      if (p->sq_ih || p->sp_ih) {      // the sparse-point / role-specialised / staged-sqrt sweep (plan creation chose the kernel)
+        IhgpPar ia = ip; ia.hph_lds = p->sq_ih ? p->hph_sq : p->hph_sp; ia.kb = p->sq_ih ? p->kb_sq : p->kb_sp;
         MomSp sq{}; sq.c0 = p->sq_c0;
-#define LQ(V) hipLaunchKernelGGL((ihgp_adf8sq_kernel<V>), dim3(B), dim3(MSQ_NT), p->lds_sq, p->stream, sh, p->b, mcf, sq, p->tb, ia)
-        switch (mcf.cdim) { case 1: LQ(1); break; case 2: LQ(2); break; case 3: LQ(3); break; case 4: LQ(4); break; case 5: LQ(5); break; default: LQ(6); break; }
-#undef LQ
-      } else if (p->sp_ih) {
-        IhgpPar ia = ip; ia.hph_lds = p->hph_sp; ia.kb = p->kb_sp;
-#define LA(V) hipLaunchKernelGGL((ihgp_adf_kernel<V>), dim3(B), dim3(MSP_NT), p->lds_sp, p->stream, sh, p->b, mcf, p->sp, p->tb, ia)
-#define LA8(V) do { if (p->dev.ih_tables) hipLaunchKernelGGL((ihgp_adf8_kernel<V, true>), dim3(B), dim3(MSR_NT), p->lds_sp8, p->stream, sh, p->b, mcf, p->sp, p->tb, ia); \
-                    else hipLaunchKernelGGL((ihgp_adf8_kernel<V, false>), dim3(B), dim3(MSR_NT), p->lds_sp8, p->stream, sh, p->b, mcf, p->sp, p->tb, ia); } while (0)
-        if (p->sp_ih8) switch (mcf.cdim) { case 1: LA8(1); break; case 2: LA8(2); break; case 3: LA8(3); break; case 4: LA8(4); break; case 5: LA8(5); break; case 6: LA8(6); break; default: LA8(7); break; }
-        else switch (mcf.cdim) { case 1: LA(1); break; case 2: LA(2); break; case 3: LA(3); break; case 4: LA(4); break; case 5: LA(5); break; case 6: LA(6); break; default: LA(7); break; }
-#undef LA
-#undef LA8
-      } else if (seq8) {
-#define LI8(V) hipLaunchKernelGGL((ihgp_filter_kernel<V, false, 8>), dim3(B), dim3(p->NT_ih), p->lds_ih, p->stream, sh, p->b, mcf, p->tb, ip)
-        NAGP_MV_SWITCH9(mom_variant(mcf), LI8)
-#undef LI8
-      } else if (p->src_f) { NAGP_MV_SWITCH9(mom_variant(mcf), LIS) } else { NAGP_MV_SWITCH9(mom_variant(mcf), LI) }
-#undef LI
-#undef LIS
+        const int nth = p->sq_ih ? MSQ_NT : (p->sp_ih8 ? MSR_NT : MSP_NT);
+        hipLaunchKernelGGL(p->k.ih_adf.fn, dim3(B), dim3(nth), p->k.ih_adf.lds, p->stream, sh, p->b, mcf, p->sq_ih ? sq : p->sp, p->tb, ia);
+      } else hipLaunchKernelGGL(p->k.ih_filter.fn, dim3(B), dim3(p->NT_ih), p->k.ih_filter.lds, p->stream, sh, p->b, mcf, p->tb, ip);
     }
     HIP_TRY(hipGetLastError());
     RUN(reduce_sum(p, p->b.lZ, itt == 1 ? 0 : sh.T - 1, sh.T, 0));
@@ -913,8 +747,7 @@ static int exec_ihgp(nagp_plan* p) {
     if (sh.T > 1 && !seq) RUN(affine(1, sh.T - 1, itt));
     else {   // T = 1, no smoothing step: P = zeros (ihgp_ep_modulator_nmf.m:364) -> maxDiffP = |H PSP H'|   (or a plan of the sequential kernels)
       Timed t(p, NAGP_K_SCAN);
-      if (seq8) hipLaunchKernelGGL(ihgp_scan_kernel<8>, dim3(B), dim3(64), 0, p->stream, sh, p->b, p->tb, p->d_vprev);
-      else hipLaunchKernelGGL(ihgp_scan_kernel<4>, dim3(B), dim3(64), 0, p->stream, sh, p->b, p->tb, p->d_vprev);
+      hipLaunchKernelGGL(p->k.ih_scan.fn, dim3(B), dim3(64), p->k.ih_scan.lds, p->stream, sh, p->b, p->tb, p->d_vprev);
     }
     if (itt < I) {
       RUN(zero_async(p, p->d_lZs, (size_t)B * sh.T * sizeof(double)));
@@ -1064,11 +897,7 @@ extern "C" int nagp_plan_set_windows(nagp_plan* p, int32_t n_windows, int32_t ov
   if (st == NAGP_OK) st = dalloc(p, &p->d_win_cmp, (size_t)p->B * P * 2);
   if (st == NAGP_OK) {
     // the windowed instantiation launch_filter will pick: the same LDS need as its sequential twin
-    const bool split = p->sh.Ms < p->sh.M;
-#define SLW(TP, LBV) (split ? set_lds((gf_filter_kernel<TP, 0, -1, LBV, 0, true, true>), p->lds_filter) : set_lds((gf_filter_kernel<TP, 0, -1, LBV, 0, false, true>), p->lds_filter))
-    if (p->wide_l) st = (p->NT_l <= 768) ? SLW(1, 768) : SLW(1, 1024);
-    else st = (p->TPT_f == 1) ? SLW(1, 512) : (p->TPT_f == 2 ? SLW(2, 512) : SLW(4, 512));
-#undef SLW
+    st = set_kernel(p->k.fixed_win, pick_gf_fixed(p->TPT_f, p->LB_l, p->sh.Ms < p->sh.M, true), p->k.fixed.lds);
   }
   if (st == NAGP_OK) {
     const hipError_t e = hipMemcpy(p->d_win, w.data(), w.size() * sizeof(FilterWin), hipMemcpyHostToDevice);

@@ -263,6 +263,41 @@ def test_developer_switches_set_by_tests_and_tools_exist_and_are_read_in_one_pla
     assert body.count('getenv(') >= 1 and c_src.count('getenv(') == body.count('getenv('), 'getenv outside read_dev_switches'
 
 
+def test_kernel_ladders_are_written_once_in_the_kernels_header():
+    """The kernels a plan launches are resolved at plan creation by the pickers of csrc/nagp_api_kernels.hpp and launched through the
+    plan's table.  (a) Plan creation (nagp_api_plan.hpp) and the launch sites (nagp_api_sweep.hpp) name none of those kernel families with
+    explicit template arguments -- a second copy of a ladder over template arguments would have to.  (b) set_lds( is applied to those
+    families only by set_kernel in that header: the other parts neither call it at all (plan, sweep) nor on a kernel of these families."""
+    csrc = os.path.join(ROOT, 'nonstationary-audio-gp_amd', 'csrc')
+    def text(name):
+        with open(os.path.join(csrc, name), errors='replace') as f:
+            return f.read()
+    families = ['gf_filter_kernel', 'gf_adf8_kernel', 'rts_gain_kernel', 'rts_gain_mfma_kernel',
+                'rts_compose_kernel', 'rts_boundary_kernel', 'rts_apply_kernel',
+                'rts_compose_mfma_kernel', 'rts_boundary_mfma_kernel', 'rts_apply_mfma_kernel', 'rts_big_kernel', 'rts_big_phi_kernel',
+                'ep_site_kernel', 'ep_site_sp_kernel', 'ep_site_sq_kernel',
+                'ihgp_filter_kernel', 'ihgp_adf_kernel', 'ihgp_adf8_kernel', 'ihgp_adf8sq_kernel',
+                'ihgp_aff_compose_kernel', 'ihgp_aff_boundary_kernel', 'ihgp_aff_apply_kernel', 'ihgp_scan_kernel']
+    named = re.compile(r'\b(%s)\b' % '|'.join(families))
+    with_args = re.compile(r'\b(%s)\s*<' % '|'.join(families))
+    kern = text('nagp_api_kernels.hpp')
+    assert {m.group(1) for m in with_args.finditer(kern)} == set(families)      # the scan sees what it should: every family is picked there
+    for part in ('nagp_api_plan.hpp', 'nagp_api_sweep.hpp'):
+        src = text(part)
+        hits = ['%s:%d %s' % (part, src.count('\n', 0, m.start()) + 1, m.group(0)) for m in with_args.finditer(src)]
+        assert not hits, 'kernel named with template arguments outside nagp_api_kernels.hpp: %s' % hits
+        assert 'set_lds(' not in src, part
+    head = 'static int set_kernel('
+    assert kern.count(head) == 1
+    body = kern[kern.index(head):]
+    body = body[:body.index('\n}\n')]
+    # in the header: the definition of set_lds and its one call, inside set_kernel
+    assert body.count('set_lds(') == 1 and kern.count('set_lds(') == 2 and kern.count('static int set_lds(') == 1
+    for part in ('nagp_api.hip', 'nagp_api_entry.hpp'):      # (the per-call entry points set and launch their own kernels)
+        bad = [ln for ln in text(part).splitlines() if 'set_lds(' in ln and named.search(ln)]
+        assert not bad, (part, bad)
+
+
 def test_measmodel_handle_raises_the_documented_error():
     H = np.zeros((5, 7)); H[np.arange(5), [0, 1, 2, 3, 5]] = 1.0
     mm = nagp.MeasModel(H, np.ones((3, 2)), 3, 2)
