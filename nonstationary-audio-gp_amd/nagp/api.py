@@ -513,11 +513,9 @@ def _giekf_grad_slices(blk, p1, p2, kernel1, kernel2, consistent):
     return dA, dQ, dPi
 
 
-def giekf_nlml_grad(blk, Wnmf, lik_param, p1, p2, kernel1, kernel2, yall, consistent=False, device=0):
-    """(edata, gdata) of the EKF energy and its gradient recursion on the GPU (nagp_giekf_nlml_grad).
-    consistent=False: the reference's statements as written -- 1+3D+2N slices, the last D*N of them with the Jacobian derivative
-    taken w.r.t. an entry of W while dm, dP carry the kernel parameter of the same index (:438-444), unbalanced dF / dPinf.
-    consistent=True: the gradient of the energy w.r.t. [sigma2, sig1, len1, omega, sig2, len2, W(:)] (1+3D+2N+D*N entries)."""
+def _giekf_grad_inputs(blk, p1, p2, kernel1, kernel2, consistent):
+    """(dA, dQ, dPinf, dR, hess, w_index, w_direct) of nagp_giekf_nlml_grad: the slices of _giekf_grad_slices with the three flag
+    vectors of the literal form, or -- consistent -- with D*N zero slices for the entries of W(:) appended and every flag set for them."""
     D, N, S = blk.D, blk.N, blk.S
     dA, dQ, dPi = _giekf_grad_slices(blk, p1, p2, kernel1, kernel2, consistent)
     n_k = 1 + 3 * D + 2 * N
@@ -530,8 +528,17 @@ def giekf_nlml_grad(blk, Wnmf, lik_param, p1, p2, kernel1, kernel2, yall, consis
         nk = n_k - D * N
         idx = np.arange(n_k)
         hess = (idx < nk).astype(np.int32); widx = np.where(idx < nk, -1, idx - nk).astype(np.int32); wdir = np.zeros(n_k, np.int32)
+    dR = np.zeros(dA.shape[0]); dR[0] = 1.0
+    return dA, dQ, dPi, dR, hess, widx, wdir
+
+
+def giekf_nlml_grad(blk, Wnmf, lik_param, p1, p2, kernel1, kernel2, yall, consistent=False, device=0):
+    """(edata, gdata) of the EKF energy and its gradient recursion on the GPU (nagp_giekf_nlml_grad).
+    consistent=False: the reference's statements as written -- 1+3D+2N slices, the last D*N of them with the Jacobian derivative
+    taken w.r.t. an entry of W while dm, dP carry the kernel parameter of the same index (:438-444), unbalanced dF / dPinf.
+    consistent=True: the gradient of the energy w.r.t. [sigma2, sig1, len1, omega, sig2, len2, W(:)] (1+3D+2N+D*N entries)."""
+    dA, dQ, dPi, dR, hess, widx, wdir = _giekf_grad_inputs(blk, p1, p2, kernel1, kernel2, consistent)
     n_par = dA.shape[0]
-    dR = np.zeros(n_par); dR[0] = 1.0
     prob = _Problem(blk, Wnmf, lik_param, stationary_Q=True)
     cm = lambda a: L.f64(np.ascontiguousarray(np.transpose(a, (0, 2, 1))), 'C')       # every slice column-major
     dAc, dQc, dPc = cm(dA), cm(dQ), cm(dPi)
