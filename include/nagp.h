@@ -252,6 +252,51 @@ int nagp_fastfb_sample(int32_t S, const double* A, const double* AKHA, const dou
                        double* Xdraw /* n_draws x (S x T column-major); may be NULL */,
                        double* MS    /* S x T: S_y(y); may be NULL */, int32_t device);
 
+/* The exact form of the stationary filterbank: the Kalman filter and RTS smoother of unifying_prob_tf/kernel_ss_kalmanSlowFB_rewrite.m
+ * (the `slow = 1` branch of kernel_ss_probFB.m) with a time-varying covariance and an observation variance of its own at every step --
+ * what the missing-data experiment of demo_stationary_filterbank.m:178-199 runs with vary = 1e-4 on observed steps and 1e5 inside the gaps,
+ * what gives true posterior covariances at the ends of a series and inside gaps, and the exact log-likelihood.
+ * Per series, from m = 0, P = P0 (:55-84):  k >= 1: m = A m, P = A P A' + Q;  s = H P H' + vary_k, K = P H'/s, v = y_k - H m, m += K v,
+ * P -= K H P;  lik -= 1/2 log 2 pi + 1/2 log s + 1/2 v^2/s.  Backward (:100-134), k = T-2 .. 0:  PSkp = A PS_k A' + Q, G = PS_k A' / PSkp,
+ * m = MS_k + G (m - A MS_k), P = PS_k + G (P - PSkp) G'.  filter_only != 0 (the .m's KF = 1): the outputs are the filtered moments.
+ * Two deliberate differences from the .m:
+ *   - a NaN y_k skips that step's update and its lik term (the library's "NaN = missing", the vary_k -> infinity limit); the .m has no
+ *     guard and returns NaN everywhere;
+ *   - the smoothed moments are computed by the adjoint recursion r_k = H'v_k/s_k + C_k'A'r_{k+1}, N_k = H'H/s_k + C_k'A'N_{k+1}A C_k
+ *     (C_k = I - K_k H), MS_k = m-_k + P-_k r_k, PS_k = P-_k - P-_k N_k P-_k on the predicted pair (m-_k, P-_k), which is the RTS result
+ *     in exact arithmetic and factorises nothing: the jitter retry of :114-121 has no counterpart.
+ * One model serves n_series independent series (each its own y and vary); they run concurrently and a series' result does not depend
+ * on its batch mates.  A, Q: S x S column-major, block diagonal with blocks of `block` states; only the lower triangles of P0 and of
+ * the blocks of Q are read.  sub_idx selects the rows and columns of the covariances returned in Psub (n_sub = S, 0..S-1: all of PS_k);
+ * Psub is symmetric to the bit.  Outputs per series: lik; MS, Pdiag (S x T column-major); Psub (n_sub x n_sub x T).
+ * All of the following is decided on the host before any device call.
+ * NAGP_EINVAL: a NULL input; S, T or n_series < 1; block < 1 or S % block != 0; a vary entry negative or not finite; sub_idx not strictly
+ *   ascending inside [0, S); Psub without n_sub > 0 or n_sub > 0 without Psub; lik, MS, Pdiag, Psub all NULL.
+ * NAGP_EUNSUPPORTED: S > 128 (the covariance of a series lives in the 160 KiB LDS of one workgroup); block > 8; a non-zero of A or Q
+ *   outside the declared blocks (dense transitions are not served).
+ * NAGP_ENOMEM: the per-step storage of one series does not fit the device-memory budget of a call, 48 GiB.  A series takes
+ *     8 T (W + 2 + S + [Pdiag: S] + n_sub^2) bytes,   W = 2 S^2 + 3 S + 2  (smoother: m-, P-, v, 1/s, K, r, N)  or  S^2 + S  (filter_only),
+ *   plus 8 (2 S^2 + 2 S block + S) + 4 n_sub + 4096 bytes per call; a batch whose series do not all fit runs in device batches of as many
+ *   series as do.  There is no checkpointing or recompute scheme: a single series beyond the budget is refused.
+ * NAGP_ENOTPD (after the run; every output is written): an innovation variance s <= 0, possible only with vary_k = 0; that series has
+ *   lik = NaN, the other series of the batch are unaffected. */
+int nagp_slowfb_run(int32_t S, int32_t block,
+                    const double* A, const double* Q,   /* S x S column-major, block diagonal, blocks of `block` states */
+                    const double* H,                    /* S entries: the observation row */
+                    const double* P0,                   /* S x S symmetric: covariance of the first state (mean 0) */
+                    int32_t n_series, const double* y,  /* n_series x T, series-major; NaN = missing */
+                    const double* vary,                 /* n_series x T: observation variance of every step, >= 0 */
+                    int64_t T, int32_t filter_only,
+                    int32_t n_sub, const int32_t* sub_idx, /* 0-based, strictly ascending; n_sub = 0 with Psub = NULL */
+                    double* lik,                        /* n_series */
+                    double* MS,                         /* n_series blocks of S x T column-major; may be NULL */
+                    double* Pdiag,                      /* n_series blocks of S x T: marginal variances; may be NULL */
+                    double* Psub,                       /* n_series blocks of n_sub x n_sub x T: P(sub_idx, sub_idx, k); may be NULL */
+                    int32_t device);
+/* Device time of the three kernels of the last nagp_slowfb_run on this thread, in ms (HIP events, summed over its device batches):
+ * ms[0] forward filter, ms[1] backward recursion (0 with filter_only), ms[2] the time-parallel combination. */
+int nagp_slowfb_timings(double* ms /* 3 */);
+
 /* What the drivers do next with Eft / Varft (demo_toy_modulators_nmf.m:119-158, the same block in the other
  * demos): the reconstructed signal sig = sum_d (W link(g))_d z_d and the modulator amplitudes link(g_n) under the independent
  * posterior marginals z_d ~ N(Eft_d, Varft_d), g_n ~ N(Eft_{D+n}, Varft_{D+n}) of every time step:

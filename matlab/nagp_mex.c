@@ -21,6 +21,10 @@
  *   [MS, sum_v2] = nagp_mex('fastfb', A, AKHA, HA, K, G ([] = filter only), y [,device])                       nagp_fastfb_run
  *   [Ydraw, Xdraw, MS] = nagp_mex('fastfb_sample', A, AKHA, HA, K, G, H, R, Lp, Lq, y, n_draws, seed [,device])   nagp_fastfb_sample
  *                                    Ydraw T x n_draws, Xdraw S x T x n_draws (computed only when asked for), MS S x T
+ *   [lik, MS, Pcov] = nagp_mex('slowfb', A, Q, H, P0, block, y, vary, filter_only, cov, sub_idx [,device])       nagp_slowfb_run
+ *                                    y, vary T x n_series; cov 0: none, 1: Pcov = marginal variances S x T x n_series, 2: Pcov =
+ *                                    P(sub_idx, sub_idx, k), n_sub x n_sub x T x n_series (sub_idx int32, 0-based, ascending; [] unless cov = 2);
+ *                                    lik n_series x 1, MS S x T x n_series
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
  *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
@@ -225,6 +229,38 @@ static void cmd_fastfb_sample(int nlhs, mxArray* plhs[], int nrhs, const mxArray
                              mxGetPr(plhs[0]), nlhs > 1 ? mxGetPr(plhs[1]) : NULL, nlhs > 2 ? mxGetPr(plhs[2]) : NULL, dev));
 }
 
+static void cmd_slowfb(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('slowfb', A, Q, H, P0, block, y, vary, filter_only, cov, sub_idx [,device]) -> [lik, MS, Pcov]: the exact filterbank filter / smoother with
+     an observation variance per step (kernel_ss_kalmanSlowFB_rewrite.m:55-84, :100-134); means and covariances only when asked for */
+  size_t n, S, T, ns, nv, nsub = 0; const double *A, *Q, *H, *P0, *y, *vary; const int32_t* sub = NULL; int32_t dev, cov; mwSize d[4];
+  double *MS = NULL, *Pd = NULL, *Ps = NULL;
+  if (nrhs < 11 || nrhs > 12 || nlhs > 3) mexErrMsgIdAndTxt("nagp:arg", "usage: [lik,MS,Pcov] = nagp_mex('slowfb',A,Q,H,P0,block,y,vary,filter_only,cov,sub_idx[,device])");
+  A = dvec(prhs[1], "A", &n); S = mxGetM(prhs[1]);
+  if (!A || n != S * S) mexErrMsgIdAndTxt("nagp:arg", "A must be S x S");
+  Q = dvec(prhs[2], "Q", &n); if (n != S * S) mexErrMsgIdAndTxt("nagp:arg", "Q must be S x S");
+  H = dvec(prhs[3], "H", &n); if (n != S) mexErrMsgIdAndTxt("nagp:arg", "H must have S entries");
+  P0 = dvec(prhs[4], "P0", &n); if (n != S * S) mexErrMsgIdAndTxt("nagp:arg", "P0 must be S x S");
+  y = dvec(prhs[6], "y", &n); T = mxGetM(prhs[6]);
+  if (!y || !T) mexErrMsgIdAndTxt("nagp:arg", "y must not be empty (T x n_series)");
+  ns = n / T;
+  vary = dvec(prhs[7], "vary", &nv);
+  if (nv != n || mxGetM(prhs[7]) != T) mexErrMsgIdAndTxt("nagp:arg", "vary must have the size of y (T x n_series)");
+  cov = (int32_t)mxGetScalar(prhs[9]);
+  if (cov < 0 || cov > 2) mexErrMsgIdAndTxt("nagp:arg", "cov must be 0 (none), 1 (marginal variances) or 2 (sub_idx)");
+  if (cov == 2) {
+    if (!mxIsInt32(prhs[10]) || mxIsEmpty(prhs[10])) mexErrMsgIdAndTxt("nagp:arg", "sub_idx must be int32 (0-based) and not empty with cov = 2");
+    sub = (const int32_t*)mxGetData(prhs[10]); nsub = mxGetNumberOfElements(prhs[10]);
+  }
+  dev = nrhs > 11 ? (int32_t)mxGetScalar(prhs[11]) : 0;
+  plhs[0] = mxCreateDoubleMatrix((mwSize)ns, 1, mxREAL);
+  if (nlhs > 1) { d[0] = S; d[1] = T; d[2] = (mwSize)ns; plhs[1] = mxCreateNumericArray(3, d, mxDOUBLE_CLASS, mxREAL); MS = mxGetPr(plhs[1]); }
+  if (nlhs > 2 && cov == 1) { d[0] = S; d[1] = T; d[2] = (mwSize)ns; plhs[2] = mxCreateNumericArray(3, d, mxDOUBLE_CLASS, mxREAL); Pd = mxGetPr(plhs[2]); }
+  if (nlhs > 2 && cov == 2) { d[0] = nsub; d[1] = nsub; d[2] = T; d[3] = (mwSize)ns; plhs[2] = mxCreateNumericArray(4, d, mxDOUBLE_CLASS, mxREAL); Ps = mxGetPr(plhs[2]); }
+  if (nlhs > 2 && cov == 0) plhs[2] = mxCreateDoubleMatrix(0, 0, mxREAL);
+  fail_if(nagp_slowfb_run((int32_t)S, (int32_t)mxGetScalar(prhs[5]), A, Q, H, P0, (int32_t)ns, y, vary, (int64_t)T, mxGetScalar(prhs[8]) != 0.0,
+                          Ps ? (int32_t)nsub : 0, Ps ? sub : NULL, mxGetPr(plhs[0]), MS, Pd, Ps, dev));
+}
+
 static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])  (demo_toy_modulators_nmf.m:119-158) */
   size_t n, nv, ngx, ngw, D, N, M, T; const double *E, *V, *W, *gx, *gw; int32_t dev; mxArray* o[4]; int i;
@@ -332,6 +368,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!strcmp(cmd, "iekf_update1")) cmd_iekf_update1(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fastfb")) cmd_fastfb(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fastfb_sample")) cmd_fastfb_sample(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "slowfb")) cmd_slowfb(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);

@@ -348,6 +348,125 @@ extern "C" int nagp_fastfb_sample(int32_t S, const double* A, const double* AKHA
 }
 
 // ---------------------------------------------------------------------------------------------
+// stationary filterbank, exact form: Kalman filter / smoother with per-step observation variances (see include/nagp.h, nagp_slowfb.hpp)
+constexpr size_t SFB_BUDGET_BYTES = (size_t)48 << 30;     // device memory of one call: the series run in device batches under it
+static thread_local double g_sfb_ms[3] = {0.0, 0.0, 0.0};
+
+typedef void (*SfbFn)(SfbPar);
+#define SFB_TABLE(name) {nullptr, name<1>, name<2>, name<3>, name<4>, name<5>, name<6>, name<7>, name<8>}
+static const SfbFn sfb_forward_tab[9] = SFB_TABLE(sfb_forward_kernel);
+static const SfbFn sfb_backward_tab[9] = SFB_TABLE(sfb_backward_kernel);
+static const SfbFn sfb_combine_tab[9] = SFB_TABLE(sfb_combine_kernel);
+#undef SFB_TABLE
+
+extern "C" int nagp_slowfb_timings(double* ms) {
+  if (!ms) FAIL(NAGP_EINVAL, "null argument");
+  for (int i = 0; i < 3; ++i) ms[i] = g_sfb_ms[i];
+  return NAGP_OK;
+}
+
+extern "C" int nagp_slowfb_run(int32_t S, int32_t block, const double* A, const double* Q, const double* H, const double* P0,
+                               int32_t n_series, const double* y, const double* vary, int64_t T, int32_t filter_only,
+                               int32_t n_sub, const int32_t* sub_idx, double* lik, double* MS, double* Pdiag, double* Psub,
+                               int32_t device) {
+  if (!A || !Q || !H || !P0 || !y || !vary) FAIL(NAGP_EINVAL, "null argument");
+  if (S < 1 || T < 1 || n_series < 1) FAIL(NAGP_EINVAL, "bad sizes (S=%d T=%lld n_series=%d)", S, (long long)T, n_series);
+  if (block < 1 || S % block != 0) FAIL(NAGP_EINVAL, "block=%d does not divide S=%d", block, S);
+  if (n_sub < 0 || (n_sub > 0) != (Psub != nullptr) || (n_sub > 0 && !sub_idx)) FAIL(NAGP_EINVAL, "Psub and n_sub=%d are not consistent", n_sub);
+  for (int i = 0; i < n_sub; ++i)
+    if (sub_idx[i] < 0 || sub_idx[i] >= S || (i > 0 && sub_idx[i] <= sub_idx[i - 1]))
+      FAIL(NAGP_EINVAL, "sub_idx[%d] = %d: the indices must ascend strictly inside [0, S)", i, sub_idx[i]);
+  if (!lik && !MS && !Pdiag && !Psub) FAIL(NAGP_EINVAL, "no output requested");
+  for (size_t e = 0, n = (size_t)n_series * T; e < n; ++e)
+    if (!(vary[e] >= 0.0) || !std::isfinite(vary[e])) FAIL(NAGP_EINVAL, "vary[%zu] = %g: an observation variance must be finite and >= 0", e, vary[e]);
+  if (S > 128) FAIL(NAGP_EUNSUPPORTED, "S=%d: the covariance of a series lives in the LDS of one workgroup (S <= 128)", S);
+  if (block > 8) FAIL(NAGP_EUNSUPPORTED, "block=%d: blocks of at most 8 states", block);
+  for (int j = 0; j < S; ++j)
+    for (int i = 0; i < S; ++i)
+      if (i / block != j / block && (A[i + (size_t)j * S] != 0.0 || Q[i + (size_t)j * S] != 0.0))
+        FAIL(NAGP_EUNSUPPORTED, "A or Q has a non-zero at (%d, %d), outside the blocks of %d states: dense transitions are not served", i, j, block);
+  const DevSwitches dev_sw = read_dev_switches();
+  const bool fo = filter_only != 0;
+  const size_t SS = (size_t)S * S, ns2 = (size_t)n_sub * n_sub;
+  const int nblk = S / block, NTL = (S + 15) / 16;
+  // the budget rule of include/nagp.h
+  const size_t per_series = 8 * (size_t)T * ((fo ? SS + S : 2 * SS + 3 * (size_t)S + 2) + 2 + S + (Pdiag ? S : 0) + ns2);
+  const size_t fixed = 8 * (2 * SS + 2 * (size_t)S * block + S) + 4 * (size_t)n_sub + 4096;
+  const size_t budget = dev_sw.sfb_budget_mb ? (size_t)dev_sw.sfb_budget_mb << 20 : SFB_BUDGET_BYTES;
+  if (fixed + per_series > budget) FAIL(NAGP_ENOMEM, "one series takes %zu B of device memory (budget %zu B)", fixed + per_series, budget);
+  const int nb = (int)std::min<size_t>({(size_t)n_series, (budget - fixed) / per_series, (size_t)32768});
+  if (hipSetDevice(device) != hipSuccess) FAIL(NAGP_EHIP, "hipSetDevice(%d)", device);
+  // the diagonal blocks of A and Q; the lower triangle of P0, mirrored
+  std::vector<double> hb(2 * (size_t)S * block + SS);
+  for (int I = 0; I < nblk; ++I)
+    for (int j = 0; j < block; ++j)
+      for (int i = 0; i < block; ++i) {
+        const size_t src = (size_t)(I * block + i) + (size_t)(I * block + j) * S, dst = (size_t)I * block * block + i + (size_t)j * block;
+        hb[dst] = A[src]; hb[(size_t)S * block + dst] = Q[src];
+      }
+  for (int j = 0; j < S; ++j)
+    for (int i = 0; i < S; ++i) hb[2 * (size_t)S * block + i + (size_t)j * S] = (i >= j) ? P0[i + (size_t)j * S] : P0[j + (size_t)i * S];
+  // one device block (doubles): Ab | Qb | P0 | H | sub (int) | per batch: y | vary | lik | flag (int) | pm | pP | v | 1/s | K | r | N | MS | Pdiag | Psub
+  const size_t TS = (size_t)T * S, TSS = (size_t)T * SS, nbz = (size_t)nb;
+  const size_t o_ab = 0, o_qb = o_ab + (size_t)S * block, o_p0 = o_qb + (size_t)S * block, o_h = o_p0 + SS, o_sub = o_h + S,
+               o_y = o_sub + (size_t)n_sub / 2 + 1, o_vr = o_y + nbz * T, o_lik = o_vr + nbz * T, o_fl = o_lik + nbz, o_pm = o_fl + nbz / 2 + 1,
+               o_pP = o_pm + nbz * TS, o_v = o_pP + nbz * TSS, o_si = o_v + (fo ? 0 : nbz * T), o_K = o_si + (fo ? 0 : nbz * T),
+               o_r = o_K + (fo ? 0 : nbz * TS), o_N = o_r + (fo ? 0 : nbz * TS), o_ms = o_N + (fo ? 0 : nbz * TSS),
+               o_pd = o_ms + nbz * TS, o_ps = o_pd + (Pdiag ? nbz * TS : 0), total = o_ps + nbz * ns2 * T + 2;
+  double* dev = nullptr;
+  if (hipMalloc(&dev, total * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", total * sizeof(double)); }
+  int st = NAGP_OK;
+  ENTRY_HIP(nagp_slowfb_run, hipMemcpy(dev + o_ab, hb.data(), hb.size() * 8, hipMemcpyHostToDevice));      // Ab | Qb | P0 are adjacent
+  ENTRY_HIP(nagp_slowfb_run, hipMemcpy(dev + o_h, H, (size_t)S * 8, hipMemcpyHostToDevice));
+  if (n_sub) ENTRY_HIP(nagp_slowfb_run, hipMemcpy(dev + o_sub, sub_idx, (size_t)n_sub * 4, hipMemcpyHostToDevice));
+  const SfbFn kf = sfb_forward_tab[block], kb = sfb_backward_tab[block], kc = sfb_combine_tab[NTL];
+  const size_t lds_s = sfb_seq_lds_doubles(S, block) * sizeof(double), lds_c = sfb_combine_lds_doubles(16 * NTL) * sizeof(double);
+  if (st == NAGP_OK) st = set_lds(kf, lds_s);
+  if (st == NAGP_OK && !fo) st = set_lds(kb, lds_s);
+  if (st == NAGP_OK) st = set_lds(kc, lds_c);
+  const int NT = (S > 64) ? 512 : 256;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 4; ++i) ENTRY_HIP(nagp_slowfb_run, hipEventCreate(&ev[i]));
+  g_sfb_ms[0] = g_sfb_ms[1] = g_sfb_ms[2] = 0.0;
+  bool notpd = false;
+  for (int i0 = 0; i0 < n_series && st == NAGP_OK; i0 += nb) {
+    const int nbk = std::min(nb, n_series - i0);
+    ENTRY_HIP(nagp_slowfb_run, hipMemcpy(dev + o_y, y + (size_t)i0 * T, (size_t)nbk * T * 8, hipMemcpyHostToDevice));
+    ENTRY_HIP(nagp_slowfb_run, hipMemcpy(dev + o_vr, vary + (size_t)i0 * T, (size_t)nbk * T * 8, hipMemcpyHostToDevice));
+    SfbPar sp{};
+    sp.S = S; sp.nblk = nblk; sp.T = T; sp.filter_only = fo ? 1 : 0;
+    sp.Ab = dev + o_ab; sp.Qb = dev + o_qb; sp.H = dev + o_h; sp.P0 = dev + o_p0; sp.y = dev + o_y; sp.vary = dev + o_vr;
+    sp.pm = dev + o_pm; sp.pP = dev + o_pP; sp.vv = dev + o_v; sp.sinv = dev + o_si; sp.K = dev + o_K; sp.r = dev + o_r; sp.N = dev + o_N;
+    sp.lik = dev + o_lik; sp.flag = reinterpret_cast<int*>(dev + o_fl);
+    sp.n_sub = n_sub; sp.sub = reinterpret_cast<const int*>(dev + o_sub);
+    sp.MS = dev + o_ms; sp.Pdiag = Pdiag ? dev + o_pd : nullptr; sp.Psub = Psub ? dev + o_ps : nullptr;
+    if (st == NAGP_OK) {
+      (void)hipEventRecord(ev[0], 0);
+      hipLaunchKernelGGL(kf, dim3(nbk), dim3(NT), lds_s, 0, sp);
+      (void)hipEventRecord(ev[1], 0);
+      if (!fo && (MS || Pdiag || Psub)) hipLaunchKernelGGL(kb, dim3(nbk), dim3(NT), lds_s, 0, sp);      // lik alone needs no backward pass
+      (void)hipEventRecord(ev[2], 0);
+      if (MS || Pdiag || Psub) hipLaunchKernelGGL(kc, dim3((unsigned)T, nbk), dim3(256), lds_c, 0, sp);
+      (void)hipEventRecord(ev[3], 0);
+    }
+    ENTRY_HIP(nagp_slowfb_run, hipGetLastError());
+    ENTRY_HIP(nagp_slowfb_run, hipDeviceSynchronize());
+    for (int i = 0; i < 3 && st == NAGP_OK; ++i) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[i], ev[i + 1]) == hipSuccess) g_sfb_ms[i] += ms; }
+    std::vector<int> fl((size_t)nbk, 0);
+    ENTRY_HIP(nagp_slowfb_run, hipMemcpy(fl.data(), dev + o_fl, (size_t)nbk * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < nbk; ++i) notpd = notpd || fl[i] != 0;
+    if (lik) ENTRY_HIP(nagp_slowfb_run, hipMemcpy(lik + i0, dev + o_lik, (size_t)nbk * 8, hipMemcpyDeviceToHost));
+    if (MS) ENTRY_HIP(nagp_slowfb_run, hipMemcpy(MS + (size_t)i0 * TS, dev + o_ms, (size_t)nbk * TS * 8, hipMemcpyDeviceToHost));
+    if (Pdiag) ENTRY_HIP(nagp_slowfb_run, hipMemcpy(Pdiag + (size_t)i0 * TS, dev + o_pd, (size_t)nbk * TS * 8, hipMemcpyDeviceToHost));
+    if (Psub) ENTRY_HIP(nagp_slowfb_run, hipMemcpy(Psub + (size_t)i0 * ns2 * T, dev + o_ps, (size_t)nbk * ns2 * T * 8, hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 4; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
+  (void)hipFree(dev);
+  if (st == NAGP_OK && notpd) FAIL(NAGP_ENOTPD, "an innovation variance s <= 0 (possible only with vary = 0): lik of that series is NaN");
+  return st;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Multi-GPU batched call (see include/nagp.h): problems round robin over the devices, one host thread + plan per device,
 // RCCL all-reduce of the per-sweep nlZ sums.
 extern "C" int nagp_batch_partition(int32_t n_problems, int32_t n_gpus, int32_t* dev_of) {

@@ -11,5 +11,6 @@ from .ss import ss_modulators, ss_modulators_nmf, lti_disc, sigmoid, inv_sigmoid
 from .cubature import utp_ws, gauher, mvhermgauss_unit  # noqa: F401
 from .plan import Plan, batch_run, batch_partition  # noqa: F401
 from .fastfb import get_disc_model, kernel_ss_kalmanFastFB, kernel_ss_sampleFastFB  # noqa: F401
+from .slowfb import kernel_ss_kalmanSlowFB, slowfb_run  # noqa: F401
 from .train import nlml_batch, fd_value_and_gradient  # noqa: F401
 from .recon import reconstruct_signal, reconstruct_sources  # noqa: F401
