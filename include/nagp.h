@@ -297,6 +297,40 @@ int nagp_slowfb_run(int32_t S, int32_t block,
  * ms[0] forward filter, ms[1] backward recursion (0 with filter_only), ms[2] the time-parallel combination. */
 int nagp_slowfb_timings(double* ms /* 3 */);
 
+/* The factorisation that gives the reference's real-audio drivers their W (demo_nonstationary_filterbank.m:93-97,
+ * experiments/train_GTFNMF.m:64-89): the fixed-point NMF of experiments/nmf/nmf_fp.m and nmf_inf_fp.m on the sub-band amplitudes
+ * A = abs(Z') (T x D, >= 0), A ~ H W with W K x D and H T x K (H is T x K in the code, whatever the header comment of the .m says).
+ * One iteration, kept literally (nmf_fp.m:65-87; the objective is getObj_nmf_temp.m:48-54, :134):
+ *     AHat = H W + vary;  H = ((A .* AHat.^-2) W') ./ (AHat.^-1 W') .* H;             Obj(end+1) = sum(A ./ (H W + vary) + log(H W + vary)) / T
+ *     AHat = H W;         W = (H' (A .* AHat.^-2)) ./ (H' AHat.^-1) .* W;  W = diag(1 ./ sum(W,2)) W;   Obj(end+1) = the same with the new W
+ * -- vary IS added in the H update and in the objective and is NOT added in the W update (:81), as in the .m.  update_w = 0 runs the
+ * first line only, one Obj per iteration: nmf_inf_fp.m:50-55.  getObj_nmf_temp renormalises W and goes through exp(log(.)); on a W whose
+ * rows already sum to 1 that is a few ulp, and the kernels skip both.
+ * n_problems independent problems (the restarts of nmf_fp.m:44-56) share A and vary and run concurrently; a problem's result does not depend
+ * on its batch mates, and every sum over t is formed in a fixed order (per-workgroup partial sums, reduced by a second kernel; no
+ * floating-point atomics): the same call gives the same bits.  All matrices column-major; W0 / W: n_problems blocks of K x D; H0 / H:
+ * n_problems blocks of T x K; Obj: (update_w ? 2 : 1) * n_its entries per problem, problem-major.
+ * The entry point does not normalise W0: that is the caller's line (nmf_fp.m:63, nmf_inf_fp.m:37-40).  n_its = 0 copies W0, H0 through.
+ * A row of A that is entirely zero with vary = 0 gives what IEEE arithmetic gives in the .m too (H(t,:) = 0/..., then NaN); it is not refused.
+ * All of the following is decided on the host before any device call.
+ * NAGP_EINVAL: A, W0 or H0 NULL; n_problems, T, D or K < 1; n_its < 0; an input that is not finite; a negative entry of A or vary; an
+ *   entry of H0 that is not > 0; a negative entry of W0; a W0 with an all-zero row or column.
+ * NAGP_EUNSUPPORTED: D > 64 or K > 16 (W lives in the LDS, H(t,:) in registers, K is padded to one MFMA tile).
+ * NAGP_ENOMEM: one problem does not fit the device-memory budget of a call, 8 GiB.  A call takes 8 T D (twice with vary) + 4096 bytes and
+ *   every problem 8 (T K + K D + ceil(T / 256) (2 K D + 2) + its Obj entries) bytes; a batch whose problems do not all fit runs in
+ *   device batches of as many problems as do, with results bit-equal to an unbatched call. */
+int nagp_nmf_fp(int32_t n_problems, int64_t T, int32_t D, int32_t K,
+                const double* A,    /* T x D, shared */
+                const double* vary, /* T x D shared, or NULL = zeros */
+                const double* W0,   /* K x D x n_problems */
+                const double* H0,   /* T x K x n_problems */
+                int32_t n_its, int32_t update_w,
+                double* W, double* H,   /* as W0 / H0; either may be NULL */
+                double* Obj,            /* (update_w ? 2 : 1) * n_its per problem, problem-major; may be NULL */
+                int32_t device);
+/* Device time of the enqueued kernel sequence of the last nagp_nmf_fp on this thread, in ms (HIP events, summed over its device batches). */
+int nagp_nmf_timings(double* ms /* 1 */);
+
 /* What the drivers do next with Eft / Varft (demo_toy_modulators_nmf.m:119-158, the same block in the other
  * demos): the reconstructed signal sig = sum_d (W link(g))_d z_d and the modulator amplitudes link(g_n) under the independent
  * posterior marginals z_d ~ N(Eft_d, Varft_d), g_n ~ N(Eft_{D+n}, Varft_{D+n}) of every time step:

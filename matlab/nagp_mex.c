@@ -25,6 +25,9 @@
  *                                    y, vary T x n_series; cov 0: none, 1: Pcov = marginal variances S x T x n_series, 2: Pcov =
  *                                    P(sub_idx, sub_idx, k), n_sub x n_sub x T x n_series (sub_idx int32, 0-based, ascending; [] unless cov = 2);
  *                                    lik n_series x 1, MS S x T x n_series
+ *   [W, H, Obj] = nagp_mex('nmf_fp', A, vary, W0, H0, n_its, update_w [,device])                               nagp_nmf_fp
+ *                                    A T x D; vary T x D or [] (= zeros); W0 K x D x P, H0 T x K x P (P problems on the same A); W, H as
+ *                                    W0, H0; Obj ((update_w ? 2 : 1) * n_its) x P
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
  *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
@@ -261,6 +264,32 @@ static void cmd_slowfb(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
                           Ps ? (int32_t)nsub : 0, Ps ? sub : NULL, mxGetPr(plhs[0]), MS, Pd, Ps, dev));
 }
 
+static void cmd_nmf_fp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('nmf_fp', A, vary, W0, H0, n_its, update_w [,device]) -> [W, H, Obj]: the fixed-point NMF of experiments/nmf/nmf_fp.m:65-87 (update_w ~= 0)
+     or nmf_inf_fp.m:42-55 (update_w = 0) on P problems that share A and vary; W0 is used as given (the wrappers normalise it) */
+  size_t n, nv, nw, nh, T, D, K, P; const double *A, *vary, *W0, *H0; int32_t dev, n_its, uw; mwSize d[3]; mxArray* o[3]; int i;
+  if (nrhs < 7 || nrhs > 8 || nlhs > 3) mexErrMsgIdAndTxt("nagp:arg", "usage: [W,H,Obj] = nagp_mex('nmf_fp',A,vary,W0,H0,n_its,update_w[,device])");
+  A = dvec(prhs[1], "A", &n); T = mxGetM(prhs[1]);
+  if (!A || !T) mexErrMsgIdAndTxt("nagp:arg", "A must not be empty (T x D)");
+  D = n / T;
+  vary = dvec(prhs[2], "vary", &nv);
+  if (vary && (nv != n || mxGetM(prhs[2]) != T)) mexErrMsgIdAndTxt("nagp:arg", "vary must have the size of A (T x D) or be []");
+  W0 = dvec(prhs[3], "W0", &nw); K = mxGetM(prhs[3]);
+  if (!W0 || !K || nw % (K * D) != 0) mexErrMsgIdAndTxt("nagp:arg", "W0 must be K x D x P with the D of A");
+  P = nw / (K * D);
+  H0 = dvec(prhs[4], "H0", &nh);
+  if (!H0 || mxGetM(prhs[4]) != T || nh != T * K * P) mexErrMsgIdAndTxt("nagp:arg", "H0 must be T x K x P with the T of A and the K, P of W0");
+  n_its = (int32_t)mxGetScalar(prhs[5]); uw = mxGetScalar(prhs[6]) != 0.0;
+  if (n_its < 0) mexErrMsgIdAndTxt("nagp:arg", "n_its must be >= 0");
+  dev = nrhs > 7 ? (int32_t)mxGetScalar(prhs[7]) : 0;
+  d[0] = K; d[1] = D; d[2] = P; o[0] = mxCreateNumericArray(3, d, mxDOUBLE_CLASS, mxREAL);
+  d[0] = T; d[1] = K; d[2] = P; o[1] = mxCreateNumericArray(3, d, mxDOUBLE_CLASS, mxREAL);
+  o[2] = mxCreateDoubleMatrix((mwSize)((uw ? 2 : 1) * (size_t)n_its), (mwSize)P, mxREAL);
+  fail_if(nagp_nmf_fp((int32_t)P, (int64_t)T, (int32_t)D, (int32_t)K, A, vary, W0, H0, n_its, uw, mxGetPr(o[0]), mxGetPr(o[1]),
+                      n_its ? mxGetPr(o[2]) : NULL, dev));
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
+}
+
 static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])  (demo_toy_modulators_nmf.m:119-158) */
   size_t n, nv, ngx, ngw, D, N, M, T; const double *E, *V, *W, *gx, *gw; int32_t dev; mxArray* o[4]; int i;
@@ -369,6 +398,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "fastfb")) cmd_fastfb(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fastfb_sample")) cmd_fastfb_sample(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "slowfb")) cmd_slowfb(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "nmf_fp")) cmd_nmf_fp(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);

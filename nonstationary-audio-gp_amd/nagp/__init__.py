@@ -12,5 +12,6 @@ from .cubature import utp_ws, gauher, mvhermgauss_unit  # noqa: F401
 from .plan import Plan, batch_run, batch_partition  # noqa: F401
 from .fastfb import get_disc_model, kernel_ss_kalmanFastFB, kernel_ss_sampleFastFB  # noqa: F401
 from .slowfb import kernel_ss_kalmanSlowFB, slowfb_run  # noqa: F401
+from .nmf import nmf_run, nmf_fp, nmf_inf_fp, nmf_init, kernel_ss_probFB, getFBLDSOutput_tau  # noqa: F401
 from .train import nlml_batch, fd_value_and_gradient  # noqa: F401
 from .recon import reconstruct_signal, reconstruct_sources  # noqa: F401
