@@ -331,6 +331,42 @@ int nagp_nmf_fp(int32_t n_problems, int64_t T, int32_t D, int32_t K,
 /* Device time of the enqueued kernel sequence of the last nagp_nmf_fp on this thread, in ms (HIP events, summed over its device batches). */
 int nagp_nmf_timings(double* ms /* 1 */);
 
+/* The objective that unifying_prob_tf/fit_probSTFT_SD.m minimises, the first call of every real-audio driver of the reference
+ * (demo_nonstationary_filterbank.m:56, experiments/train_GTFNMF.m:56): get_Obj_pSTFT_{exp,matern32,matern52}.m (form = 0) and
+ * get_Obj_pSTFT_all.m (form = 1) with its gradient, for a batch of problems.  With the transforms of :61-67,
+ *     mVar = minVar + exp(theta(1:D)),  om = limOm(:,1) + (limOm(:,2) - limOm(:,1)) ./ (1 + exp(-theta(D+1:2D))),  lam likewise from limLam,
+ * and the grid omegas = [linspace(0, pi, ceil(N/2)), -omegas(floor(N/2):-1:1)] (:72-74; 0 and pi twice for even N, pi once for odd N),
+ *     spec_i = vary + sum_d (1 - lam_d^2) S_d(omegas_i),   Obj = (sum_i log spec_i + sum_i specTar_i / spec_i + bet sum_d mVar_d) / N,
+ * and dObj as each file writes it (the cosh(theta/2)^-2 / 4 factors, bet dVar on the variance part only, the / N).
+ * Quirks kept: the generic file sets len = sqrt(5) / lam for every kernel except exp (1 / lam) and matern32 (sqrt(3) / lam), so matern72
+ * runs with sqrt(5) against cf_matern72_to_ss's lambda = sqrt(7) / len (_all.m:81-94); ss_func(mVar, len, 4).
+ * The generic file's complex solves are evaluated through their closed form (the rotation diagonalises the product model into two
+ * Matern companion systems in omega -+ om, each a power of 1 / (lm^2 + (omega -+ om)^2)), which for exp, matern32 and matern52 IS the
+ * kernel-specific file: form = 0 and form = 1 give the same bits for those three (csrc/nagp_pstft.hpp).
+ * theta: 3 D per problem, problem-major.  specTar: N entries shared by the problems (spec_stride = 0) or N per problem (spec_stride = N).
+ * minVar (D), limOm, limLam (D x 2 column-major) are shared.  dObj = NULL: the objective only (the same Obj bits).
+ * Every sum over the frequencies is formed in a fixed order (a butterfly inside a wave, waves and workgroups in ascending order; no
+ * floating-point atomics): a problem's result is the same to the bit alone, in a batch, and however the call is cut into device batches.
+ * All of the following is decided on the host before any device call.
+ * NAGP_EUNSUPPORTED: a kernel other than the four NAGP_PSTFT_* (se is not served); form = 0 with NAGP_PSTFT_MATERN72 (no such file);
+ *   D > 64 (the per-component constants live in the LDS); one problem beyond the device-memory budget of a call, 1 GiB: a call takes
+ *   8 (5 D + N when specTar is shared) + 4096 bytes and every problem 8 (ceil(N / 256) (3 D + 2, objective only: 2) + 6 D + 3 + N when
+ *   specTar is per problem) bytes -- no O(N D) scratch: the gradient pass recomputes S_d.  A batch whose problems do not all fit runs in
+ *   device batches of as many as do.
+ * NAGP_EINVAL: a NULL input or Obj; n_problems or D < 1; form not 0 or 1; N < 4; spec_stride not 0 or N; an input that is not finite;
+ *   specTar < 0; vary < 0; minVar < 0; limOm or limLam with upper <= lower; limLam outside [0, 1] (beyond it a component's spectrum is
+ *   negative); vary = 0 for a problem none of whose components has 0 < lam < 1 in float64 -- spec would be 0.  A limLam range with
+ *   0 < lower and upper < 1 rules that out for every theta; fit_probSTFT_SD's own ranges [0, lam_max] do so for every theta that has
+ *   not saturated onto the lower end. */
+enum { NAGP_PSTFT_EXP = 0, NAGP_PSTFT_MATERN32 = 1, NAGP_PSTFT_MATERN52 = 2, NAGP_PSTFT_MATERN72 = 3 };
+int nagp_pstft_obj(int32_t n_problems, int32_t kernel, int32_t form /* 0 closed, 1 generic */, int32_t D, int64_t N,
+                   const double* theta /* n_problems x 3D */, const double* specTar, int64_t spec_stride /* 0 = shared, N = per problem */,
+                   const double* vary, const double* bet /* n_problems each */,
+                   const double* minVar /* D */, const double* limOm, const double* limLam /* D x 2, column-major */,
+                   double* Obj /* n_problems */, double* dObj /* n_problems x 3D, or NULL = objective only */, int32_t device);
+/* Device time of the two kernels of the last nagp_pstft_obj on this thread, in ms (HIP events, summed over its device batches). */
+int nagp_pstft_timings(double* ms /* 1 */);
+
 /* What the drivers do next with Eft / Varft (demo_toy_modulators_nmf.m:119-158, the same block in the other
  * demos): the reconstructed signal sig = sum_d (W link(g))_d z_d and the modulator amplitudes link(g_n) under the independent
  * posterior marginals z_d ~ N(Eft_d, Varft_d), g_n ~ N(Eft_{D+n}, Varft_{D+n}) of every time step:

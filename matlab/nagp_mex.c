@@ -28,6 +28,10 @@
  *   [W, H, Obj] = nagp_mex('nmf_fp', A, vary, W0, H0, n_its, update_w [,device])                               nagp_nmf_fp
  *                                    A T x D; vary T x D or [] (= zeros); W0 K x D x P, H0 T x K x P (P problems on the same A); W, H as
  *                                    W0, H0; Obj ((update_w ? 2 : 1) * n_its) x P
+ *   [Obj, dObj] = nagp_mex('pstft_obj', kernel, form, theta, vary, specTar, minVar, limOm, limLam, bet [,device])  nagp_pstft_obj
+ *                                    kernel 'exp' | 'matern32' | 'matern52' | 'matern72'; form 0 (get_Obj_pSTFT_<kernel>.m) or 1
+ *                                    (get_Obj_pSTFT_all.m); theta 3D x P; specTar N x 1 (shared) or N x P; vary, bet scalars or P entries;
+ *                                    minVar D x 1, limOm, limLam D x 2; Obj P x 1, dObj 3D x P (formed only with two outputs)
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
  *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
@@ -290,6 +294,39 @@ static void cmd_nmf_fp(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[
   for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
 }
 
+static void cmd_pstft_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('pstft_obj', kernel, form, theta, vary, specTar, minVar, limOm, limLam, bet [,device]) -> [Obj, dObj]: the objective of
+     unifying_prob_tf/get_Obj_pSTFT_<kernel>.m (form 0) / get_Obj_pSTFT_all.m (form 1) for P problems; dObj only when asked for */
+  static const char* names[4] = {"exp", "matern32", "matern52", "matern72"};
+  char kn[16]; size_t nt, nv, ns, nm, no, nl, nb, D, P, N, q; const double *theta, *vary, *spec, *minVar, *limOm, *limLam, *bet;
+  double *vy, *bt; int32_t dev, form, kernel = -1; int i; mxArray* o[2] = {NULL, NULL};
+  if (nrhs < 10 || nrhs > 11 || nlhs > 2) mexErrMsgIdAndTxt("nagp:arg", "usage: [Obj,dObj] = nagp_mex('pstft_obj',kernel,form,theta,vary,specTar,minVar,limOm,limLam,bet[,device])");
+  if (!mxIsChar(prhs[1]) || mxGetString(prhs[1], kn, sizeof kn)) mexErrMsgIdAndTxt("nagp:arg", "kernel must be a string");
+  for (i = 0; i < 4; ++i) if (!strcmp(kn, names[i])) kernel = i;
+  if (kernel < 0) mexErrMsgIdAndTxt("nagp:arg", "kernel '%s': exp, matern32, matern52 and matern72 are served", kn);
+  form = (int32_t)mxGetScalar(prhs[2]);
+  theta = dvec(prhs[3], "theta", &nt);
+  minVar = dvec(prhs[6], "minVar", &nm); D = nm;
+  if (!theta || !minVar || !D || nt % (3 * D) != 0 || mxGetM(prhs[3]) != 3 * D) mexErrMsgIdAndTxt("nagp:arg", "theta must be 3D x P with the D of minVar");
+  P = nt / (3 * D);
+  spec = dvec(prhs[5], "specTar", &ns);
+  N = (spec && mxGetN(prhs[5]) == 1 && mxGetM(prhs[5]) == ns) ? ns : (spec ? mxGetM(prhs[5]) : 0);
+  if (!N || (ns != N && ns != N * P)) mexErrMsgIdAndTxt("nagp:arg", "specTar must be N x 1 or N x P");
+  limOm = dvec(prhs[7], "limOm", &no); limLam = dvec(prhs[8], "limLam", &nl);
+  if (!limOm || !limLam || no != 2 * D || nl != 2 * D || mxGetM(prhs[7]) != D || mxGetM(prhs[8]) != D) mexErrMsgIdAndTxt("nagp:arg", "limOm and limLam must be D x 2");
+  vary = dvec(prhs[4], "vary", &nv); bet = dvec(prhs[9], "bet", &nb);
+  if (!vary || !bet || (nv != 1 && nv != P) || (nb != 1 && nb != P)) mexErrMsgIdAndTxt("nagp:arg", "vary and bet must be scalars or hold P entries");
+  dev = nrhs > 10 ? (int32_t)mxGetScalar(prhs[10]) : 0;
+  vy = (double*)mxCalloc(P, sizeof *vy); bt = (double*)mxCalloc(P, sizeof *bt);
+  for (q = 0; q < P; ++q) { vy[q] = vary[nv == 1 ? 0 : q]; bt[q] = bet[nb == 1 ? 0 : q]; }
+  o[0] = mxCreateDoubleMatrix((mwSize)P, 1, mxREAL);
+  if (nlhs > 1) o[1] = mxCreateDoubleMatrix((mwSize)(3 * D), (mwSize)P, mxREAL);
+  fail_if(nagp_pstft_obj((int32_t)P, kernel, form, (int32_t)D, (int64_t)N, theta, spec, ns == N ? 0 : (int64_t)N, vy, bt, minVar, limOm, limLam,
+                         mxGetPr(o[0]), o[1] ? mxGetPr(o[1]) : NULL, dev));
+  mxFree(vy); mxFree(bt);
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
+}
+
 static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])  (demo_toy_modulators_nmf.m:119-158) */
   size_t n, nv, ngx, ngw, D, N, M, T; const double *E, *V, *W, *gx, *gw; int32_t dev; mxArray* o[4]; int i;
@@ -399,6 +436,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "fastfb_sample")) cmd_fastfb_sample(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "slowfb")) cmd_slowfb(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "nmf_fp")) cmd_nmf_fp(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "pstft_obj")) cmd_pstft_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);

@@ -579,6 +579,109 @@ extern "C" int nagp_nmf_fp(int32_t n_problems, int64_t T, int32_t D, int32_t K, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// objective and gradient of the filterbank spectrum fit, get_Obj_pSTFT_{exp,matern32,matern52,all}.m (see include/nagp.h, nagp_pstft.hpp)
+constexpr size_t PSTFT_BUDGET_BYTES = (size_t)1 << 30;    // device memory of one call: the problems run in device batches under it
+static thread_local double g_pstft_ms = 0.0;
+
+typedef void (*PstftFn)(PstftPar);
+static const PstftFn pstft_pass_tab[4] = {pstft_pass_kernel<1>, pstft_pass_kernel<2>, pstft_pass_kernel<3>, pstft_pass_kernel<4>};
+static const PstftFn pstft_finish_tab[4] = {pstft_finish_kernel<1>, pstft_finish_kernel<2>, pstft_finish_kernel<3>, pstft_finish_kernel<4>};
+
+extern "C" int nagp_pstft_timings(double* ms) {
+  if (!ms) FAIL(NAGP_EINVAL, "null argument");
+  ms[0] = g_pstft_ms;
+  return NAGP_OK;
+}
+
+extern "C" int nagp_pstft_obj(int32_t n_problems, int32_t kernel, int32_t form, int32_t D, int64_t N, const double* theta, const double* specTar,
+                              int64_t spec_stride, const double* vary, const double* bet, const double* minVar, const double* limOm,
+                              const double* limLam, double* Obj, double* dObj, int32_t device) {
+  if (!theta || !specTar || !vary || !bet || !minVar || !limOm || !limLam || !Obj) FAIL(NAGP_EINVAL, "null argument");
+  if (n_problems < 1 || D < 1) FAIL(NAGP_EINVAL, "bad sizes (n_problems=%d D=%d)", n_problems, D);
+  if (kernel < NAGP_PSTFT_EXP || kernel > NAGP_PSTFT_MATERN72) FAIL(NAGP_EUNSUPPORTED, "kernel %d: exp, matern32, matern52 and matern72 are served (se is not)", kernel);
+  if (form != 0 && form != 1) FAIL(NAGP_EINVAL, "form = %d: 0 (closed) or 1 (generic)", form);
+  if (form == 0 && kernel == NAGP_PSTFT_MATERN72) FAIL(NAGP_EUNSUPPORTED, "matern72 has no closed-form file: use form = 1 (get_Obj_pSTFT_all)");
+  if (D > PSTFT_MAXD) FAIL(NAGP_EUNSUPPORTED, "D=%d: at most %d components", D, PSTFT_MAXD);
+  if (N < 4) FAIL(NAGP_EINVAL, "N=%lld: at least 4 frequencies", (long long)N);
+  if (spec_stride != 0 && spec_stride != N) FAIL(NAGP_EINVAL, "spec_stride = %lld: 0 (shared) or N", (long long)spec_stride);
+  for (int d = 0; d < D; ++d) {
+    if (!std::isfinite(minVar[d]) || minVar[d] < 0.0) FAIL(NAGP_EINVAL, "minVar[%d] = %g: finite and >= 0", d, minVar[d]);
+    if (!std::isfinite(limOm[d]) || !std::isfinite(limOm[D + d]) || !(limOm[D + d] > limOm[d])) FAIL(NAGP_EINVAL, "limOm(%d, :) = [%g, %g]: finite, upper > lower", d, limOm[d], limOm[D + d]);
+    if (!std::isfinite(limLam[d]) || !std::isfinite(limLam[D + d]) || !(limLam[D + d] > limLam[d])) FAIL(NAGP_EINVAL, "limLam(%d, :) = [%g, %g]: finite, upper > lower", d, limLam[d], limLam[D + d]);
+    if (limLam[d] < 0.0 || limLam[D + d] > 1.0) FAIL(NAGP_EINVAL, "limLam(%d, :) = [%g, %g]: inside [0, 1], where every component's spectrum is >= 0", d, limLam[d], limLam[D + d]);
+  }
+  for (size_t e = 0, n = (size_t)n_problems * 3 * D; e < n; ++e)
+    if (!std::isfinite(theta[e])) FAIL(NAGP_EINVAL, "theta[%zu] = %g", e, theta[e]);
+  for (size_t e = 0, n = spec_stride ? (size_t)n_problems * N : (size_t)N; e < n; ++e)
+    if (!std::isfinite(specTar[e]) || specTar[e] < 0.0) FAIL(NAGP_EINVAL, "specTar[%zu] = %g: the target spectrum must be finite and >= 0", e, specTar[e]);
+  for (int q = 0; q < n_problems; ++q) {
+    if (!std::isfinite(vary[q]) || vary[q] < 0.0) FAIL(NAGP_EINVAL, "vary[%d] = %g: finite and >= 0", q, vary[q]);
+    if (!std::isfinite(bet[q])) FAIL(NAGP_EINVAL, "bet[%d] = %g", q, bet[q]);
+    if (vary[q] == 0.0) {                                   // spec = 0 at every frequency unless one component has 0 < lam < 1
+      bool pos = false;
+      for (int d = 0; d < D && !pos; ++d) {
+        const double lam = limLam[d] + (limLam[D + d] - limLam[d]) / (1.0 + std::exp(-theta[(size_t)q * 3 * D + 2 * D + d]));
+        pos = lam > 0.0 && lam < 1.0;
+      }
+      if (!pos) FAIL(NAGP_EINVAL, "problem %d: vary = 0 and no component with 0 < lam < 1: the model spectrum is zero", q);
+    }
+  }
+  const DevSwitches dev_sw = read_dev_switches();
+  const int grad = dObj ? 1 : 0, n_out = grad ? 3 * D + 2 : 2;
+  const int64_t nwg64 = (N + PSTFT_NT - 1) / PSTFT_NT;
+  if (nwg64 > 0x7fffffff / n_out) FAIL(NAGP_EUNSUPPORTED, "N=%lld: too many frequencies", (long long)N);
+  const int nwg = (int)nwg64;
+  // the budget rule of include/nagp.h
+  const size_t fixed = 8 * ((spec_stride ? 0 : (size_t)N) + 5 * (size_t)D) + 4096;
+  const size_t per_problem = 8 * ((spec_stride ? (size_t)N : 0) + (size_t)nwg * n_out + 6 * (size_t)D + 3);
+  const size_t budget = dev_sw.pstft_budget_mb ? (size_t)dev_sw.pstft_budget_mb << 20 : PSTFT_BUDGET_BYTES;
+  if (fixed + per_problem > budget) FAIL(NAGP_EUNSUPPORTED, "one problem takes %zu B of device memory (budget %zu B)", fixed + per_problem, budget);
+  const int nb = (int)std::min<size_t>({(size_t)n_problems, (budget - fixed) / per_problem, (size_t)32768});
+  if (hipSetDevice(device) != hipSuccess) FAIL(NAGP_EHIP, "hipSetDevice(%d)", device);
+  // one device block (doubles): minVar | limOm | limLam | specTar (shared) | per batch: theta | vary | bet | specTar | part | Obj | dObj
+  const size_t nbz = (size_t)nb, Dz = (size_t)D, Nz = (size_t)N;
+  const size_t o_mv = 0, o_lo = o_mv + Dz, o_ll = o_lo + 2 * Dz, o_ss = o_ll + 2 * Dz, o_th = o_ss + (spec_stride ? 0 : Nz), o_vy = o_th + nbz * 3 * Dz,
+               o_bt = o_vy + nbz, o_sp = o_bt + nbz, o_pt = o_sp + (spec_stride ? nbz * Nz : 0), o_ob = o_pt + nbz * nwg * n_out, o_dg = o_ob + nbz,
+               total = o_dg + nbz * 3 * Dz + 2;
+  double* dev = nullptr;
+  if (hipMalloc(&dev, total * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", total * sizeof(double)); }
+  int st = NAGP_OK;
+  ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dev + o_mv, minVar, Dz * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dev + o_lo, limOm, 2 * Dz * 8, hipMemcpyHostToDevice));
+  ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dev + o_ll, limLam, 2 * Dz * 8, hipMemcpyHostToDevice));
+  if (!spec_stride) ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dev + o_ss, specTar, Nz * 8, hipMemcpyHostToDevice));
+  const PstftFn kp = pstft_pass_tab[kernel], kfin = pstft_finish_tab[kernel];
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  for (int i = 0; i < 2; ++i) ENTRY_HIP(nagp_pstft_obj, hipEventCreate(&ev[i]));
+  g_pstft_ms = 0.0;
+  for (int i0 = 0; i0 < n_problems && st == NAGP_OK; i0 += nb) {
+    const int nbk = std::min(nb, n_problems - i0);
+    ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dev + o_th, theta + (size_t)i0 * 3 * Dz, (size_t)nbk * 3 * Dz * 8, hipMemcpyHostToDevice));
+    ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dev + o_vy, vary + i0, (size_t)nbk * 8, hipMemcpyHostToDevice));
+    ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dev + o_bt, bet + i0, (size_t)nbk * 8, hipMemcpyHostToDevice));
+    if (spec_stride) ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dev + o_sp, specTar + (size_t)i0 * Nz, (size_t)nbk * Nz * 8, hipMemcpyHostToDevice));
+    PstftPar pp{};
+    pp.N = N; pp.D = D; pp.nwg = nwg; pp.grad = grad; pp.kappa = kernel == NAGP_PSTFT_MATERN72 ? std::sqrt(7.0 / 5.0) : 1.0;
+    pp.theta = dev + o_th; pp.specTar = spec_stride ? dev + o_sp : dev + o_ss; pp.spec_stride = spec_stride; pp.vary = dev + o_vy; pp.bet = dev + o_bt;
+    pp.minVar = dev + o_mv; pp.limOm = dev + o_lo; pp.limLam = dev + o_ll; pp.part = dev + o_pt; pp.Obj = dev + o_ob; pp.dObj = dev + o_dg;
+    if (st == NAGP_OK) {
+      (void)hipEventRecord(ev[0], 0);
+      hipLaunchKernelGGL(kp, dim3((unsigned)nwg, (unsigned)nbk), dim3(PSTFT_NT), 0, 0, pp);
+      hipLaunchKernelGGL(kfin, dim3((unsigned)nbk), dim3(PSTFT_FIN_NT), 0, 0, pp);
+      (void)hipEventRecord(ev[1], 0);
+    }
+    ENTRY_HIP(nagp_pstft_obj, hipGetLastError());
+    ENTRY_HIP(nagp_pstft_obj, hipDeviceSynchronize());
+    if (st == NAGP_OK) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) g_pstft_ms += ms; }
+    ENTRY_HIP(nagp_pstft_obj, hipMemcpy(Obj + i0, dev + o_ob, (size_t)nbk * 8, hipMemcpyDeviceToHost));
+    if (grad) ENTRY_HIP(nagp_pstft_obj, hipMemcpy(dObj + (size_t)i0 * 3 * Dz, dev + o_dg, (size_t)nbk * 3 * Dz * 8, hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
+  (void)hipFree(dev);
+  return st;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Multi-GPU batched call (see include/nagp.h): problems round robin over the devices, one host thread + plan per device,
 // RCCL all-reduce of the per-sweep nlZ sums.
 extern "C" int nagp_batch_partition(int32_t n_problems, int32_t n_gpus, int32_t* dev_of) {

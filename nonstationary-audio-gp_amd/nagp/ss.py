@@ -71,6 +71,21 @@ def kernel_block_derivs(kernel, sigma2, ell):
     return (np.zeros((n, n)), Pinf / sigma2), (dF_ell, dP_ell)
 
 
+def kernel_ss_derivs(kernel, sigma2, ell):
+    """The dF and dQc outputs of cf_<kernel>_to_ss w.r.t. (sigma2, ell), for all four kernels -- matern72 as cf_matern72_to_ss.m:134-150
+    writes them (dF's last row [196/ell^5, 84 sqrt(7)/ell^4, 84/ell^3, 4 sqrt(7)/ell^2], dQc = [Qc/sigma2, -7 Qc/ell]).  These are what
+    get_Obj_pSTFT_all.m:145 asks of ss_func.  Returns dF (n, n, 2) and dQc (2,).  (kernel_block_derivs serves the EKF gradient, which
+    needs dPinf and keeps to blocks of at most three states.)"""
+    F, _, Qc, _ = kernel_block(kernel, sigma2, ell)
+    n = F.shape[0]
+    binom = [math.comb(n, i) for i in range(n)]
+    lam = (1.0 if kernel == 'exp' else _SQ[kernel]) / ell
+    dF = np.zeros((n, n, 2))
+    for i in range(n):                                   # last row -C(n,i) lam^(n-i), lam = c / ell
+        dF[n - 1, i, 1] = binom[i] * (n - i) * lam ** (n - i) / ell
+    return dF, np.array([Qc / sigma2, -(2 * n - 1) * Qc / ell])
+
+
 class BlockSS:
     """Block-diagonal continuous-time model: lists of per-block (F, LQL', Pinf) and the H pattern."""
 
