@@ -735,9 +735,15 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
       if (need() <= 156 * 1024) {
         p->sp_ih = 1; p->lds_sp = need();
         // role-specialised waves: two serial + six worker waves, one sigma point per worker lane, the cubature sums from bin sums (msr_build_desc)
-        const size_t need8 = ihgp_adf8_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16;
-        if (p->sp.bdesc && need8 <= 156 * 1024 && dev.ih_roles) {
-          p->sp_ih8 = 1; p->lds_sp8 = need8;
+        // (its workspace is the larger one: where it alone does not fit, it gives up the same residents in the same order -- only one of the
+        // two kernels is launched, so the ring and the table setting are that kernel's)
+        if (p->sp.bdesc && dev.ih_roles) {
+          const int kb0 = p->kb_sp, hph0 = p->hph_sp;
+          auto need8 = [&]() { return ihgp_adf8_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16; };
+          if (need8() > 156 * 1024) p->kb_sp = 8;
+          if (need8() > 156 * 1024) p->hph_sp = 0;
+          if (need8() <= 156 * 1024) { p->sp_ih8 = 1; p->lds_sp8 = need8(); }
+          else { p->kb_sp = kb0; p->hph_sp = hph0; }
         }
         PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SP, o->cub_dim, p->sp_ih8, dev.ih_tables), p->sp_ih8 ? p->lds_sp8 : p->lds_sp));
       }

@@ -826,7 +826,7 @@ extern "C" int nagp_plan_execute(nagp_plan* p) {
     if (hipMemcpy(st, p->d_stamps, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
       if (p->opts.kind == NAGP_KIND_IHGP)
         for (int w = 0; w < 2; ++w)
-          fprintf(stderr, "[nagp stamps] %s: wait at B1 %llu | Q/v %llu | B2..B3 (direct stage 1b: wait at B2) %llu | weights %llu | wait at B4 %llu | bin sums %llu | - %llu | wait at B5 %llu\n",
+          fprintf(stderr, "[nagp stamps] %s: wait at B1 %llu | Q/v %llu (both 0 in the three-barrier schedule: Q/v on wave 0) | B2..B3 (direct stage 1b: wait at B2) %llu | weights %llu | wait at B4 %llu | bin sums %llu | - %llu | wait at B5 %llu\n",
                   w ? "last worker wave " : "first worker wave", st[8 + 8 * w], st[9 + 8 * w], st[10 + 8 * w], st[11 + 8 * w], st[12 + 8 * w], st[13 + 8 * w], st[14 + 8 * w], st[15 + 8 * w]);
     }
     if (p->opts.kind == NAGP_KIND_GF_EP && hipMemcpy(st, p->d_stamps, 64, hipMemcpyDeviceToHost) == hipSuccess)
@@ -834,7 +834,7 @@ extern "C" int nagp_plan_execute(nagp_plan* p) {
     if (p->opts.kind == NAGP_KIND_GIEKF && hipMemcpy(st, p->d_stamps, 64, hipMemcpyDeviceToHost) == hipSuccess)
       fprintf(stderr, "[nagp stamps] EKF step: loop top + mean prediction %llu | congruence + panel of wave 0 %llu | wait at B1 %llu | Jacobian partials %llu | P J' %llu | wave sums, gain, mean %llu | P -= K S K' %llu | outputs, PF stores, B5 %llu\n", st[4], st[5], st[0], st[1], st[2], st[3], st[6], st[7]);
     else if (hipMemcpy(st, p->d_stamps, 64, hipMemcpyDeviceToHost) == hipSuccess)
-      fprintf(stderr, "[nagp stamps] mom: p1a %llu p1b %llu p2 %llu p3 %llu | pre-mom %llu post-mom %llu | aux %llu %llu  (sparse-point IHGP sweep: p1a..p3 = A, B+1b, 2, wait at B1 ; pre..aux = reduce+outputs, site+state+ring, look-up, A m)\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]);
+      fprintf(stderr, "[nagp stamps] mom: p1a %llu p1b %llu p2 %llu p3 %llu | pre-mom %llu post-mom %llu | aux %llu %llu  (sparse-point IHGP sweep: p1a..p3 = A, B+1b, 2, wait at B1 ; role kernel: B1..B2 (three-barrier schedule: wait at B2), B2..B4, B4..B5, wait at B1 (three-barrier schedule: Q/v on wave 0, link tables on wave 1) ; pre..aux = reduce+outputs, site+state+ring, look-up, A m)\n", st[0], st[1], st[2], st[3], st[4], st[5], st[6], st[7]);
   }
 
   HIP_TRY(hipGetLastError());

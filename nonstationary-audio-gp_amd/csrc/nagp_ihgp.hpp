@@ -5,6 +5,7 @@
 //   ihgp_scan_kernel    backward mean recursion with looked-up steady-state smoother gains (:373-394)
 // The EP refresh (:397-436) reuses ep_site_kernel (parallel over steps).
 #pragma once
+#include <type_traits>
 #include "nagp_kernels.hpp"
 #include "nagp_momsq.hpp"
 
@@ -546,16 +547,35 @@ __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomC
 // The same sweep with role-specialised waves (nagp_momsp.hpp, role layout): 512 threads, waves 0 / 1 as above, waves 2..7 run the
 // parallel stages of the cubature in their own loop.  A wave holds the registers of its role only, which is what lets two
 // waves share a SIMD.
-// Barriers of a step, TAB = false (the product): B1 | Q / 2Q / v (workers), link tables (wave 1) | B2 | Gaussian weights straight from
-// Q, v and the link tables (msr_stage1b_direct); e table (wave 1) | B4 | bin sums | B5 | serial tail.  TAB = true (developer switch
-// NAGP_IH_TABLES=1, the form of the four-wave kernel): behind B2 the tables e / t1 / ve on wave 1 and q0 / s0 on workers 3 and 4, one more
-// barrier (B3), then the weights from those tables (msp_stage1b).
+// Barriers of a step, TAB = false and CD <= 6 (the product, "NB1"): THREE.  B2 | Gaussian weights straight from Q, v and the link tables
+// (msr_stage1b_direct); e table (wave 1) | B4 | bin sums; table words of the reduction (serial waves) | B5 | serial tail, head of step
+// k+1, then Q / 2Q / v on wave 0 (msr_qv_serial) and the link tables on wave 1 (msp_link), each from the wave's own fmu / HPH stores.
+// The two serial chains run side by side from B5 to B2; no barrier puts one behind the other.  Without a barrier between the tail of
+// step k and the cubature inputs of step k+1, every LDS region is ordered by construction:
+//   region                     writer (step k+1)                    last reader (step k)                         ordered by
+//   fmu / HPH, sub-bands       wave 0, head                         wave 0, msr_qv_serial                        same wave
+//   fmu / HPH, modulators      wave 1, head                         wave 1, msp_link                             same wave
+//     (msr_qv_serial never uses an entry beyond the sub-bands: with D = 4K it reads none, otherwise it discards what it read)
+//   Q / 2Q / v                 wave 0, B5(k) .. B2(k+1)             workers' weights, B2(k) .. B4(k)             B4, B5
+//   link tables lk / xg / xg2  wave 1, B5(k) .. B2(k+1)             workers' weights and level 2 of msr_sums, both ahead of B5(k);    B5
+//                                                                   msr_reduce_tab on the serial waves, B4(k) .. B5(k)
+//   e table                    wave 1, B2 .. B4                     level 2 of msr_sums, B4 .. B5                B5, B2
+//   level-2 results (part)     workers, B4 .. B5                    msr_reduce_bins, behind B5                   B2, B4 of step k+1
+//   c0 / c1 / c2, acc          as in the other schedule             (weights B2 .. B4, level 1 B4 .. B5; acc: one wave)
+//   wwt (static products)      wave 0, once                         wave 0                                       same lane
+// msr_reduce as a whole behind B5 would read l0_j and xg2_j(centre) while wave 1 -- whose tail is the shorter one -- may already be
+// writing the tables of step k+1; hence its split (msr_reduce_tab / msr_reduce_bins).
+// TAB = false, CD = 7 (the 2 x 35 outputs of Q / 2Q / v do not fit the lanes of wave 0) keeps FOUR: B1 | Q / 2Q / v (workers 0..2), link
+// tables (wave 1) | B2 | ... as above with msr_reduce behind B5.  TAB = true (developer switch NAGP_IH_TABLES=1, the form of the
+// four-wave kernel, the in-build cross-check): B1 as for CD = 7; behind B2 the tables e / t1 / ve on wave 1 and q0 / s0 on workers 3 and
+// 4, one more barrier (B3), then the weights from those tables (msp_stage1b).
 template <int CD, bool TAB>
 __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int NT = MSR_NT;
+  constexpr bool NB1 = !TAB && CD <= 6;              // the three-barrier schedule (see above)
   const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG;
   const int64_t T = sh.T;
   const int pb = blockIdx.x;
@@ -604,7 +624,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     // ================= worker role: the parallel stages of the cubature; the same barriers as the serial role below
     const MspLay lay = msp_layout(CD, D, 1);
     MsrW<CD> xw;
-    msr_setup_W<CD>(xw, mc, sp, sW, fmu, HPH, ws);
+    msr_setup_W<CD>(xw, mc, sp, sW, fmu, HPH, ws, !NB1);
     // developer diagnostics (NAGP_STAMPS): time lines of worker (NAGP_STAMP_WORKER & 7) in stamps[8..15] and of the last worker in
     // stamps[16..23]
     const int wk_slot = (wave == MSR_W0 + (ip.dbg_wave & 7)) ? 8 : ((wave == MSR_W0 + MSR_NWK - 1) ? 16 : -1);
@@ -619,10 +639,12 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
     __syncthreads();
     for (int kk = 0; kk < nb; ++kk) {
-      lds_barrier();                 // B1
-      WK_STAMP(0);                   // (wait at B1: the serial waves' tail and head)
-      msp_qv<CD>(xw, mc);            // workers 0..2
-      WK_STAMP(1);
+      if constexpr (!NB1) {
+        lds_barrier();                 // B1
+        WK_STAMP(0);                   // (wait at B1: the serial waves' tail and head)
+        msp_qv<CD>(xw, mc);            // workers 0..2
+        WK_STAMP(1);
+      }
       lds_barrier();                 // B2
       if constexpr (TAB) {
         if (wave == MSR_W0 + 3 || wave == MSR_W0 + 4) msr_q0_or_s0(xw, wave == MSR_W0 + 3, ws + lay.q0, ws + lay.s0);
@@ -630,7 +652,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
         WK_STAMP(2);                   // (B2 .. B3: tables on wave 1, q0 / s0 on workers 3, 4)
         msp_stage1b<CD>(xw, mc, sp, sn2a, ry[kk], ws);
       } else {
-        WK_STAMP(2);                   // (wait at B2: wave 1's link tables)
+        WK_STAMP(2);                   // (wait at B2: wave 1's link tables; NB1: the serial waves' tail, head, Q / v and link tables)
         msr_stage1b_direct<CD>(xw, sn2a, ry[kk]);
       }
       WK_STAMP(3);
@@ -659,14 +681,24 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   // ================= serial role (waves 0 and 1)
   MsrS<CD> x;
   msr_setup_S<CD>(x, mc, sp, fmu, HPH, ws);
+  MsrQ<CD> xq;                                       // NB1: Q / 2Q / v on wave 0
+  MsrRT rt;                                          //      table words of the reduction, read ahead of B5
+  if constexpr (NB1) msr_setup_Q<CD>(xq, mc, sW, fmu, HPH, ws);
 
+  // NB1: the two serial waves run separate copies of the loop below (WT = 0, 1: the wave index is a constant of the copy), so that each
+  // holds the registers of its own chain only -- wave 0 the W row and the operands of Q / 2Q / v, wave 1 the link chain's constants.
+  // Otherwise (WT = -1) one copy serves both, as before.
+  const int wave_rt = wave;
+  auto serial = [&](auto WV) __attribute__((always_inline)) {
+  constexpr int WT = decltype(WV)::value;
+  const int wave = (WT < 0) ? wave_rt : WT;
   // wave 0, lane d < D owns sub-band block d; wave 1, lane j < N owns modulator block D + j
   const int lane = tid & 63;
   const bool sub = (wave == 0) && lane < D;
   const bool act = sub || ((wave == 1) && lane < sh.N);
   const int n = (wave == 0) ? lane : D + lane;
   const int nn = act ? n : 0;
-  double A4[16], mreg[4] = {0, 0, 0, 0}, wrow[CD];
+  double A4[16], mreg[4] = {0, 0, 0, 0}, wrow[CD];      // (WT = 0: the W row is read again every step, p_w below)
   double hn = 0.0;
 #pragma unroll
   for (int j = 0; j < CD; ++j) wrow[j] = 0.0;
@@ -697,6 +729,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   const msp_wp p_fmu = (msp_wp)(fmu + nn), p_HPH = (msp_wp)(HPH + nn);
   const msp_rp p_hph = (msp_rp)(thph + (size_t)nn * NG);
   const msp_rp p_rg = (msp_rp)rg + opaque_zero();
+  const msp_rp p_w = (msp_rp)(sW + (sub ? n : 0) * CD);      // WT = 0: this sub-band's row of W, beside the reads of the reduction
   const double* g_wcol = tab + itab_wcol(sh, NG) + (size_t)nn * NG * 4;
   const double* g_hph = tab + itab_hph(sh, NG) + (size_t)nn * NG;
   double Rprev = (act && ip.k_start > 0) ? b.R[((size_t)pb * T + (ip.k_start - 1)) * M + n] : 0.0;
@@ -734,10 +767,16 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     }
   };
   if (wave <= 1) head(ip.k_start);
+  // NB1: the cubature's inputs of a step straight behind its head, each from this wave's own fmu / HPH stores (msp_wave_fence)
+  auto qv_or_link = [&]() {
+    msp_wave_fence();
+    if (wave == 0) msr_qv_serial<CD>(xq, mc); else msp_link<CD>(x, mc);
+  };
+  if constexpr (NB1) qv_or_link();
   // link tables of a step (the exp / log chain of the modulators' sigma-point coordinates, ~1 000 cycles on wave 1): evaluated BEHIND
   // barrier B1, beside the worker waves' Q / 2Q / v stage -- nothing reads them before the stages behind B2.  (Evaluated
   // ahead of B1 they were the tail of the serial chain: wave 0 waited ~800 cycles at B1 for them.)  ip.dbg_wave & 16: the old placement.
-  const bool link_early = (ip.dbg_wave & 16) != 0;
+  const bool link_early = !NB1 && (ip.dbg_wave & 16) != 0;
   if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }      // link tables of the first step
   if (stamp) st_a = __builtin_readcyclecounter();
 
@@ -749,11 +788,13 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     __syncthreads();
     for (int kk = 0; kk < nb; ++kk) {
       const int64_t k = k0 + kk;
-      lds_barrier();                 // B1: fmu, HPH of step k; its link tables (written by wave 1 on its way here)
-      IH_STAMP(3);
-      // (Q / 2Q / v: worker waves)
-      if (wave == 1 && !link_early) msp_link<CD>(x, mc);
-      lds_barrier();                 // B2
+      if constexpr (!NB1) {
+        lds_barrier();                 // B1: fmu, HPH of step k; its link tables (written by wave 1 on its way here)
+        IH_STAMP(3);
+        // (Q / 2Q / v: worker waves)
+        if (wave == 1 && !link_early) msp_link<CD>(x, mc);
+      }
+      lds_barrier();                 // B2 (NB1: Q / 2Q / v and the link tables of step k, written by waves 0 and 1 on their way here)
       IH_STAMP(0);
       if constexpr (TAB) {
         if (wave == 1) msp_tables<CD>(x, mc);
@@ -765,15 +806,19 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       lds_barrier();                 // B4
       IH_STAMP(1);
       // (bin sums: worker waves)
+      if constexpr (NB1) msr_reduce_tab<CD>(x, rt);      // the link-table words of the reduction: no reader of the tables is left behind B5
       lds_barrier();                 // B5
       IH_STAMP(2);
       {
-        msr_reduce<CD>(x);
+        double wr[CD];
+#pragma unroll
+        for (int j = 0; j < CD; ++j) wr[j] = (WT == 0) ? p_w[j] : wrow[j];      // (2 CD registers of wave 0's copy freed for msr_qv_serial)
+        if constexpr (NB1) msr_reduce_bins<CD>(x, rt); else msr_reduce<CD>(x);
         msp_wave_fence();
         if (act) {
           const int ko = kk * M;
           double Z, d1, d2;
-          msp_outputs<CD>(x.accp, sub, n - D, wrow, pEP1, mc.jitter, Z, d1, d2);
+          msp_outputs<CD>(x.accp, sub, n - D, wr, pEP1, mc.jitter, Z, d1, d2);
           if (stamp) { asm volatile("" :: "v"(d2)); IH_STAMP(4); }
           const double t_old = p_tt[ko], n_old = p_tn[ko];
           // site update (:265-266): -d2/(1+d2 HPH), (d1 - fmu d2)/(1+d2 HPH) through one reciprocal
@@ -803,7 +848,8 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
         }
         if (k + 1 < T) {
           head(k + 1);
-          if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }     // fmu / HPH of the modulators just written by this wave
+          if constexpr (NB1) { qv_or_link(); IH_STAMP(3); }      // (slot 3: Q / 2Q / v on wave 0, the link tables on wave 1)
+          else if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }     // fmu / HPH of the modulators just written by this wave
         }
       }
     }
@@ -821,6 +867,10 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   if (act && n_clamped) atomicAdd(&b.counters[(size_t)pb * 4 + 1], (unsigned long long)n_clamped);
   if (stamp)
     for (int i = 0; i < 8; ++i) mc.stamps[i] += st[i];
+  };
+  if constexpr (NB1) {
+    if (wave == 0) serial(std::integral_constant<int, 0>{}); else serial(std::integral_constant<int, 1>{});
+  } else serial(std::integral_constant<int, -1>{});
 }
 
 // The role-specialised sweep for likModulatorPreCalcwn (experiments/likModulatorPreCalcwn.m:28-86; nagp_momsq.hpp): 512 threads, waves

@@ -576,7 +576,7 @@ __device__ __forceinline__ void msp_outputs(msp_rp acc, bool sub, int jmod, cons
 
 // =====================================================================================================================
 // Role layout (LAY = 1): 512 threads.  Waves 0 and 1 carry the serial stages of the caller (wave 1 also evaluates the link
-// tables and e -- with t1 / ve in the table form of stage 1b); waves 2 .. 7 carry the parallel ones: Q / 2Q / v on waves 2..4,
+// tables and e -- with t1 / ve in the table form of stage 1b); waves 2 .. 7 carry the parallel ones: Q / 2Q / v on waves 2..4 (three-barrier schedule of ihgp_adf8_kernel: on wave 0, msr_qv_serial),
 // (table form: q0 / s0 on waves 5 / 6), one sigma point per lane of the six (<= 384 points), the cubature sums round the six.  The two roles run in separate loops of the
 // kernel, so a wave holds the registers of its own role only: two waves per SIMD within 256 registers each.
 //
@@ -662,9 +662,10 @@ __device__ __forceinline__ void msr_setup_S(MsrS<CD>& x, const MomCfg& c, const 
   }
 }
 
+// qv = false: Q / 2Q / v are formed on serial wave 0 (msr_setup_Q, msr_qv_serial), which then owns the wwt region; no worker lane takes a part
 template <int CD>
 __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const MomSp& sp, const double* Wl /* LDS D x CD */,
-                                             const double* fmu, const double* HPH, double* ws) {
+                                             const double* fmu, const double* HPH, double* ws, bool qv = true) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave - MSR_W0;     // wr = 0 .. 5
   const int nd = c.nd, D = c.D, npt = c.n_pts;
   const MspLay l = msp_layout(CD, D, 1);
@@ -685,7 +686,7 @@ __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const 
     x.q_kind = 0;
     x.q_out0 = x.q_out1 = x.q_out2 = x.q_out3 = (msp_wp)(ws + l.acc + 127);
     x.q_ww = x.q_src = (msp_rp)(ws + l.zero);
-    const int L = (wr >= 0 && wr < 3) ? wr * 64 + lane : -1;
+    const int L = (qv && wr >= 0 && wr < 3) ? wr * 64 + lane : -1;
     if (L >= 0) {
       const int g = L >> 2, sub = L & 3;
       const int nq = CD * (CD + 1) / 2;
@@ -761,6 +762,105 @@ __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const 
   }
 }
 
+// ---- Q / 2Q / v on serial wave 0 (the three-barrier schedule of ihgp_adf8_kernel): the nq + CD outputs of msr_setup_W's 4-lane groups on
+// aligned groups of TWO lanes, 2 (nq + CD) <= 64 lanes for CD <= 6.  Lane h of a pair carries the partial sums p_h and p_{h+2} of the 4-lane
+// form (p_sub: sub-bands d = sub + 4q, q < K, even and odd q in two chains added at the end), so every addition of msp_qv has its counterpart
+// here with the same operands in the same order: the results are the same bits.  Static products at ws[wwt + 64 t + lane], t = s K + q for
+// the term d = h + 2s + 4q of partial s (the region the workers' products take in the other schedules; written and read by the same lane).
+constexpr int MSR_QG = 4;       // terms per group of msr_qv_serial
+// what a lane keeps for the stage: two read and two write addresses (2Q sits CD*CD doubles behind Q); its kind follows from the lane index
+template <int CD>
+struct MsrQ { msp_rp ww, src; msp_wp out0, out1; };
+// kind of the output of lane pair g: 1: Q(j,j'), 2: v(j), 0: none
+template <int CD>
+__host__ __device__ inline int msr_qkind(int g) { return g < CD * (CD + 1) / 2 ? 1 : (g < CD * (CD + 1) / 2 + CD ? 2 : 0); }
+
+template <int CD>
+__device__ __forceinline__ void msr_setup_Q(MsrQ<CD>& x, const MomCfg& c, const double* Wl /* LDS D x CD */, const double* fmu, const double* HPH,
+                                             double* ws) {
+  constexpr int nq = CD * (CD + 1) / 2;
+  static_assert(2 * (nq + CD) <= 64, "the pairs of msr_qv_serial fill one wave up to CD = 6");
+  const int tid = threadIdx.x, D = c.D, K = msp_qterms(D);
+  const MspLay l = msp_layout(CD, D, 1);
+  x.out0 = x.out1 = (msp_wp)(ws + l.acc + 127);      // scratch slot
+  x.ww = x.src = (msp_rp)(ws + l.zero);
+  if (tid < 64) {
+    const int g = tid >> 1, h = tid & 1, kind = msr_qkind<CD>(g);
+    int j = 0, j2 = 0;
+    if (kind == 1) {
+      int r = g; j = 0;
+      while (r >= CD - j) { r -= CD - j; ++j; }
+      j2 = j + r;
+      x.out0 = (msp_wp)(ws + l.Q + j * CD + j2); x.out1 = (msp_wp)(ws + l.Q + j2 * CD + j);
+    } else if (kind == 2) {
+      j = g - nq;
+      x.out0 = (msp_wp)(ws + l.v + j);
+    }
+    for (int t = 0; t < 2 * K; ++t) {
+      const int s = t / K, q = t - s * K, d = h + 2 * s + 4 * q;
+      double v = 0.0;
+      if (kind && d < D) v = (kind == 1) ? Wl[d * CD + j] * Wl[d * CD + j2] : Wl[d * CD + j];
+      ws[l.wwt + t * 64 + tid] = v;
+    }
+    x.ww = (msp_rp)(ws + l.wwt + tid);
+    x.src = (msp_rp)(((kind == 1) ? HPH : fmu) + h);
+  }
+}
+// PAD (4K > D): the operands beyond the sub-bands -- the modulators' entries, which wave 1 may be writing at this moment, and the zero
+// padding -- are replaced by zero before they are used (msp_qv multiplies them by a zero product: the same sum for finite entries)
+template <int K, bool PAD>
+__device__ __forceinline__ void msr_qsum2(msp_rp ww, msp_rp src, int dlim, double& p, double& r) {
+  // groups of MSR_QG terms, the reads of the next group in flight while a group multiplies: one LDS latency, then the rate of the reads,
+  // with 2 MSR_QG terms in registers at a time (the serial role has few registers to spare beside its state).  The pins fix that order:
+  // a group's reads are issued behind the FMAs of the group two ahead of it.
+  constexpr int G = MSR_QG, NGR = 2 * K / G;
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};              // chain 2s + (q & 1): the even and the odd q of partial s, q ascending
+  double w[NGR][G], v[NGR][G];
+#pragma unroll
+  for (int g = 0; g < 2 && g < NGR; ++g)
+#pragma unroll
+    for (int u = 0; u < G; ++u) { const int t = G * g + u; w[g][u] = ww[64 * t]; v[g][u] = src[2 * (t / K) + 4 * (t % K)]; }
+#pragma unroll
+  for (int g = 0; g < NGR; ++g) {
+#pragma unroll
+    for (int u = 0; u < G; ++u) asm volatile("" : "+v"(w[g][u]), "+v"(v[g][u]));
+    if (PAD) {
+#pragma unroll
+      for (int u = 0; u < G; ++u) { const int t = G * g + u; v[g][u] = (2 * (t / K) + 4 * (t % K) < dlim) ? v[g][u] : 0.0; }
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) { const int t = G * g + u, ch = 2 * (t / K) + (t % K & 1); acc[ch] = fma(w[g][u], v[g][u], acc[ch]); }
+    if (g + 2 < NGR) {
+      asm volatile("" : "+v"(ww), "+v"(src), "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
+#pragma unroll
+      for (int u = 0; u < G; ++u) { const int t = G * (g + 2) + u; w[g + 2][u] = ww[64 * t]; v[g + 2][u] = src[2 * (t / K) + 4 * (t % K)]; }
+    }
+  }
+  p = acc[0] + acc[1]; r = acc[2] + acc[3];
+}
+// Q / 2Q / v of a step on wave 0, straight behind the head that wrote the sub-bands' fmu / HPH (the same lanes' stores: msp_wave_fence
+// between them); no barrier.  Every lane of the wave executes it.
+template <int CD>
+__device__ __forceinline__ void msr_qv_serial(const MsrQ<CD>& x, const MomCfg& c) {
+  const int lane = threadIdx.x & 63, kind = msr_qkind<CD>(lane >> 1);
+  if (kind) {
+    const int K = __builtin_amdgcn_readfirstlane(msp_qterms(c.D));
+    const bool pad = __builtin_amdgcn_readfirstlane(4 * K != c.D ? 1 : 0) != 0;
+    const int dlim = c.D - (lane & 1);               // operand 2s + 4q of this lane is a sub-band's while 2s + 4q < dlim
+    double p = 0.0, r = 0.0;
+    if (K == 4) { if (pad) msr_qsum2<4, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<4, false>(x.ww, x.src, dlim, p, r); }
+    else if (K == 8) { if (pad) msr_qsum2<8, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<8, false>(x.ww, x.src, dlim, p, r); }
+    else { if (pad) msr_qsum2<16, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<16, false>(x.ww, x.src, dlim, p, r); }
+    p += dpp_mov<0xB1>(p);                           // lane 0 of the pair: p0 + p1
+    r += dpp_mov<0xB1>(r);                           //                     p2 + p3
+    const double a = p + r;
+    if ((lane & 1) == 0) {
+      if (kind == 1) { x.out0[0] = a; x.out1[0] = a; x.out0[CD * CD] = 2.0 * a; x.out1[CD * CD] = 2.0 * a; }
+      else x.out0[0] = a;
+    }
+  }
+}
+
 // sum over the lanes of an aligned group of 1, 2 or 4 (grp bit 0: lane ^ 1 belongs to it, bit 1: lane ^ 2); every lane of the wave executes it
 __device__ __forceinline__ double msr_group_sum(double s, int grp) {
   const double n1 = dpp_mov<0xB1>(s);
@@ -808,6 +908,29 @@ __device__ __forceinline__ void msr_reduce(const X& x) {
 #pragma unroll
     for (int i = 0; i < MSR_RW; ++i) asm volatile("" : "+v"(r[i]));
     *x.r_dst = fma(r[5] * r[6], r[7], fma(r[1], r[2], fma(r[3], r[4], r[0])));
+  }
+}
+
+// msr_reduce in two parts (the three-barrier schedule of ihgp_adf8_kernel).  Of the eight operands the words a, c, f, g (1, 3, 6, 7) are
+// link-table or constant words (l0_j, xg2_j(centre), one, zero) and p, b, d, s (0, 2, 4, 5) level-2 results or the zero word
+// (msr_build_desc).  The table words are final from the barrier ahead of the weights on and are read AHEAD of the barrier behind the bin
+// sums, so that wave 1 may overwrite the link tables as soon as that barrier has released; the level-2 results are read behind it.
+struct MsrRT { double a, c, f, g; };
+template <int CD, class X>
+__device__ __forceinline__ void msr_reduce_tab(const X& x, MsrRT& t) {
+  t.a = t.c = t.f = t.g = 0.0;
+  if ((int)(threadIdx.x & 63) < msp_nacc(CD)) {
+    t.a = *x.r_p[1]; t.c = *x.r_p[3]; t.f = *x.r_p[6]; t.g = *x.r_p[7];
+  }
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t.a), "+v"(t.c), "+v"(t.f), "+v"(t.g) :: "memory");      // in registers before the barrier
+}
+template <int CD, class X>
+__device__ __forceinline__ void msr_reduce_bins(const X& x, const MsrRT& t) {
+  const int lane = threadIdx.x & 63;
+  if (lane < msp_nacc(CD)) {
+    double p = *x.r_p[0], b = *x.r_p[2], d = *x.r_p[4], s = *x.r_p[5];
+    asm volatile("" : "+v"(p), "+v"(b), "+v"(d), "+v"(s));
+    *x.r_dst = fma(s * t.f, t.g, fma(t.a, b, fma(t.c, d, p)));
   }
 }
 
