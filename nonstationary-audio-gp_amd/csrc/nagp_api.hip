@@ -75,6 +75,7 @@ struct DevSwitches {
   int nmf_budget_mb = 0;         // NAGP_NMF_BUDGET_MB (>= 1): device-memory budget of nagp_nmf_fp in MiB instead of NMF_BUDGET_BYTES
   int pstft_budget_mb = 0;       // NAGP_PSTFT_BUDGET_MB (>= 1): device-memory budget of nagp_pstft_obj in MiB instead of PSTFT_BUDGET_BYTES
   int kb_f = 0;                  // NAGP_KB_F (1 .. 16)
+  int ih_kb = 0;                 // NAGP_IH_KB (4, 8 or 16; anything else: not set): depth of the I/O ring of ihgp_adf8_kernel, where it fits
   int filter_dbg = 0;            // NAGP_FILTER_DBG
   int gainm_dbg = 0;             // NAGP_GAINM_DBG
   int stamp_worker = 0;          // NAGP_STAMP_WORKER
@@ -116,6 +117,7 @@ static DevSwitches read_dev_switches() {
   if ((v = env("NAGP_NMF_BUDGET_MB"))) s.nmf_budget_mb = std::max(1, atoi(v));
   if ((v = env("NAGP_PSTFT_BUDGET_MB"))) s.pstft_budget_mb = std::max(1, atoi(v));
   if ((v = env("NAGP_KB_F"))) s.kb_f = std::max(1, std::min(16, atoi(v)));
+  if ((v = env("NAGP_IH_KB"))) { const int kb = atoi(v); s.ih_kb = (kb == 4 || kb == 8 || kb == 16) ? kb : 0; }
   if ((v = env("NAGP_FILTER_DBG"))) s.filter_dbg = atoi(v);
   if ((v = env("NAGP_GAINM_DBG"))) s.gainm_dbg = atoi(v);
   if ((v = env("NAGP_STAMP_WORKER"))) s.stamp_worker = atoi(v);

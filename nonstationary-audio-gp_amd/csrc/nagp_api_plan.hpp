@@ -744,6 +744,13 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
           if (need8() > 156 * 1024) p->hph_sp = 0;
           if (need8() <= 156 * 1024) { p->sp_ih8 = 1; p->lds_sp8 = need8(); }
           else { p->kb_sp = kb0; p->hph_sp = hph0; }
+          // developer switch NAGP_IH_KB: another depth of the role kernel's ring, where it fits (the streamed ring is circular: a slot used
+          // too early or flushed too late changes bits at a different depth, tests/test_ihgp_adf_streamed_ring.py)
+          if (p->sp_ih8 && dev.ih_kb && dev.ih_kb != p->kb_sp) {
+            const int kb1 = p->kb_sp;
+            p->kb_sp = dev.ih_kb;
+            if (need8() <= 156 * 1024) p->lds_sp8 = need8(); else p->kb_sp = kb1;
+          }
         }
         PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SP, o->cub_dim, p->sp_ih8, dev.ih_tables), p->sp_ih8 ? p->lds_sp8 : p->lds_sp));
       }

@@ -826,7 +826,7 @@ extern "C" int nagp_plan_execute(nagp_plan* p) {
     if (hipMemcpy(st, p->d_stamps, sizeof st, hipMemcpyDeviceToHost) == hipSuccess) {
       if (p->opts.kind == NAGP_KIND_IHGP)
         for (int w = 0; w < 2; ++w)
-          fprintf(stderr, "[nagp stamps] %s: wait at B1 %llu | Q/v %llu (both 0 in the three-barrier schedule: Q/v on wave 0) | B2..B3 (direct stage 1b: wait at B2) %llu | weights %llu | wait at B4 %llu | bin sums %llu | - %llu | wait at B5 %llu\n",
+          fprintf(stderr, "[nagp stamps] %s: wait at B1 %llu | Q/v %llu (both 0 in the three-barrier schedule: Q/v on wave 0) | B2..B3 (direct stage 1b: wait at B2) %llu | weights %llu | wait at B4 %llu | bin sums %llu | ring (streamed: its work of every window, inside B5 .. B2; block ring: B5 of a block's last step .. end of the next fill) %llu | wait at B5 %llu\n",
                   w ? "last worker wave " : "first worker wave", st[8 + 8 * w], st[9 + 8 * w], st[10 + 8 * w], st[11 + 8 * w], st[12 + 8 * w], st[13 + 8 * w], st[14 + 8 * w], st[15 + 8 * w]);
     }
     if (p->opts.kind == NAGP_KIND_GF_EP && hipMemcpy(st, p->d_stamps, 64, hipMemcpyDeviceToHost) == hipSuccess)

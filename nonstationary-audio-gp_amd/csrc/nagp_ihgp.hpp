@@ -563,9 +563,25 @@ __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomC
 //   level-2 results (part)     workers, B4 .. B5                    msr_reduce_bins, behind B5                   B2, B4 of step k+1
 //   c0 / c1 / c2, acc          as in the other schedule             (weights B2 .. B4, level 1 B4 .. B5; acc: one wave)
 //   wwt (static products)      wave 0, once                         wave 0                                       same lane
+// The I/O ring of this schedule is circular and streamed: slot k mod KB serves step k (KB = 16, 8 or 4), and four worker waves (2, 3, 6, 7:
+// the SIMDs without a serial wave) move one step's worth per step inside their idle window W(k) = B5(k) .. B2(k+1): they store the inputs
+// of step k+1 (loaded in W(k-1), carried in a register), load those of step k+2 and flush the outputs of step k-1.  The first step is
+// filled ahead of the loop, the last one flushed behind it, one __syncthreads each; no block-level section is left inside the loop.
+//   region                     writer                               last reader                                  ordered by
+//   ring inputs, slot of k+1   I/O lanes, W(k)                      workers' weights (ry), B2(k+1) .. B4(k+1);   B2(k+1)
+//     (y, lZ, ttau, tnu, Z=-1)                                      serial tail of step k+1, behind B5(k+1)
+//     the slot's previous step k+1-KB: flushed in W(k+2-KB), at least two windows earlier (KB >= 4)              B2 .. B5 of the steps between
+//   ring outputs, slot of k    serial tail of step k,               flush by the I/O lanes, W(k+1)               B2(k+1) (.. B5(k+1))
+//     (ttau, tnu, R, fm, MF, Z)  B5(k) .. B2(k+1)
+//     the slot's next writers: the fill of step k+KB in W(k+KB-1) >= W(k+3), the tail of step k+KB                B2 .. B5 of the steps between
+//   one window touches three different slots: k+1 (fill), k (serial tail), k-1 (flush): KB >= 3
+// The global loads of a window are issued ahead of its stores and are not waited for before the next window; the flush's stores are
+// never waited for (nothing in this launch reads them back).  lds_barrier() waits for LDS traffic only, so both stay in flight across
+// the step's barriers.
 // msr_reduce as a whole behind B5 would read l0_j and xg2_j(centre) while wave 1 -- whose tail is the shorter one -- may already be
 // writing the tables of step k+1; hence its split (msr_reduce_tab / msr_reduce_bins).
-// TAB = false, CD = 7 (the 2 x 35 outputs of Q / 2Q / v do not fit the lanes of wave 0) keeps FOUR: B1 | Q / 2Q / v (workers 0..2), link
+// TAB = false, CD = 7 (the 2 x 35 outputs of Q / 2Q / v do not fit the lanes of wave 0) keeps the block ring (fill, KB steps, flush by the
+// whole workgroup round two __syncthreads) and FOUR barriers: B1 | Q / 2Q / v (workers 0..2), link
 // tables (wave 1) | B2 | ... as above with msr_reduce behind B5.  TAB = true (developer switch NAGP_IH_TABLES=1, the form of the
 // four-wave kernel, the in-build cross-check): B1 as for CD = 7; behind B2 the tables e / t1 / ve on wave 1 and q0 / s0 on workers 3 and
 // 4, one more barrier (B3), then the weights from those tables (msp_stage1b).
@@ -610,7 +626,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   const double pEP1 = mom_pEP(mc, sn2, ip.mom_alpha);
   const double rmax = tb.r[NG - 1];
   __syncthreads();
-  // global rows of this problem (both roles fill and flush the ring)
+  // global rows of this problem (the streamed ring: the I/O lanes of the worker role fill and flush it; the block ring: both roles)
   const double* yv = b.y + (size_t)pb * T;
   double* g_tt = b.ttau + (size_t)pb * T * M;
   double* g_tn = b.tnu + (size_t)pb * T * M;
@@ -632,13 +648,8 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     unsigned long long wk_a = 0, wk_b = 0, wk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (wk_stamp) wk_a = __builtin_readcyclecounter();
 #define WK_STAMP(slot) do { if (wk_stamp) { wk_b = __builtin_readcyclecounter(); wk[slot] += wk_b - wk_a; wk_a = wk_b; } } while (0)
-  for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
-    const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
-    // ---- fill the ring for steps k0 .. k0+nb-1
-    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
-    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
-    __syncthreads();
-    for (int kk = 0; kk < nb; ++kk) {
+    // one step between its barriers; kk = the step's ring slot
+    auto wstep = [&](int kk) __attribute__((always_inline)) {
       if constexpr (!NB1) {
         lds_barrier();                 // B1
         WK_STAMP(0);                   // (wait at B1: the serial waves' tail and head)
@@ -662,7 +673,86 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       WK_STAMP(5);
       lds_barrier();                 // B5
       WK_STAMP(7);
-    }
+    };
+    if constexpr (NB1) {
+      // ---- the streamed ring (see the table above): the I/O lanes are the 256 lanes of waves 2, 3, 6, 7 -- the SIMDs that hold no serial
+      // wave.  The lane -> item mapping is static: an LDS address, its stride per slot, a global pointer that advances by one step's row.
+      // Outputs of a step: ttau | tnu | R | fm (M each) | MF (S, through smap), at most two per lane; lZ with its log on lane 0 of wave 7.
+      // Inputs: ttau | tnu | y | lZ, one per lane, carried in a register from the window that loads it to the next one, which stores it.
+      static_assert((IH_KB & (IH_KB - 1)) == 0 && IH_KB >= 4, "the streamed ring masks the step index: the plan's depths are IH_KB, 8 and 4");
+      const int KM = KB - 1;                               // (KB is 4, 8 or 16: at least 3 slots, a power of two)
+      const bool io = (wave & 2) != 0;
+      const int L = io ? ((((wave >> 2) << 1) | (wave & 1)) * 64 + (tid & 63)) : (1 << 20);
+      const int n4 = 4 * M, nout = n4 + S;
+      msp_rp o_l[2]; double* o_g[2]; int o_ls[2], o_gs[2]; bool o_on[2];
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        const int j = L + 256 * t;
+        o_on[t] = j < nout;
+        const int jj = o_on[t] ? j : 0;
+        if (jj < n4) {
+          const int a = jj / M, i = jj - a * M;
+          o_l[t] = (msp_rp)((a == 0 ? rtt : a == 1 ? rtn : a == 2 ? rR : rfm) + i);
+          o_g[t] = (a == 0 ? g_tt : a == 1 ? g_tn : a == 2 ? g_R : g_fm) + (size_t)ip.k_start * M + i;
+          o_ls[t] = M; o_gs[t] = M;
+        } else {
+          const int e = jj - n4;
+          o_l[t] = (msp_rp)(rMF + smap[e]);
+          o_g[t] = g_MF + (size_t)ip.k_start * S + e;
+          o_ls[t] = n4; o_gs[t] = S;
+        }
+      }
+      const bool z_on = io && L == 192;
+      double* z_g = g_lZ + ip.k_start;
+      const msp_rp z_r = (msp_rp)rZ, z_l = (msp_rp)rlZ;
+      const bool i_on = L < 2 * M + 2, i_z = L == 2 * M + 1;
+      msp_wp i_l = (msp_wp)rtt; const double* i_g = g_tt; int i_ls = M, i_gs = M;
+      if (i_on) {
+        if (L < M) { i_l = (msp_wp)(rtt + L); i_g = g_tt + (size_t)ip.k_start * M + L; }
+        else if (L < 2 * M) { i_l = (msp_wp)(rtn + (L - M)); i_g = g_tn + (size_t)ip.k_start * M + (L - M); }
+        else { i_l = (msp_wp)(L == 2 * M ? ry : rlZ); i_g = (L == 2 * M ? yv : g_lZ) + ip.k_start; i_ls = 1; i_gs = 1; }
+      }
+      const msp_wp i_rz = (msp_wp)rZ;
+      auto flush = [&](int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+          if (o_on[t]) { *o_g[t] = o_l[t][s * o_ls[t]]; o_g[t] += o_gs[t]; }
+        if (z_on) { const double z = z_r[s]; *z_g = (z < 0.0) ? z_l[s] : log(z); ++z_g; }
+      };
+      int64_t k = ip.k_start;
+      double carry = 0.0;
+      // prologue: the first step straight into its slot, the second into the register
+      if (i_on && k < T) {
+        const int s0 = (int)(k & KM);
+        i_l[s0 * i_ls] = *i_g; i_g += i_gs;
+        if (i_z) i_rz[s0] = -1.0;
+        if (k + 1 < T) { carry = *i_g; i_g += i_gs; }
+      }
+      __syncthreads();
+      for (; k < T; ++k) {
+        wstep((int)(k & KM));
+        // the window B5(k) .. B2(k+1): store the inputs of step k+1, load those of step k+2 (ahead of the stores below: the wait for a
+        // load then leaves the younger stores alone), flush step k-1
+        if (io) {
+          if (i_on) {
+            if (k + 1 < T) { const int s1 = (int)((k + 1) & KM); i_l[s1 * i_ls] = carry; if (i_z) i_rz[s1] = -1.0; }
+            if (k + 2 < T) { carry = *i_g; i_g += i_gs; }
+          }
+          if (k > ip.k_start) flush((int)((k - 1) & KM));
+        }
+        WK_STAMP(6);                   // (the ring's work of the window)
+      }
+      __syncthreads();
+      if (io && T > ip.k_start) flush((int)((T - 1) & KM));
+    } else {
+  for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
+    const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
+    // ---- fill the ring for steps k0 .. k0+nb-1
+    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
+    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
+    __syncthreads();
+    WK_STAMP(6);                       // (the ring section: from B5 of a block's last step through the flush and the next fill)
+    for (int kk = 0; kk < nb; ++kk) wstep(kk);
     // ---- flush the ring
     __syncthreads();
     for (int i = tid; i < nb; i += NT) g_lZ[k0 + i] = (rZ[i] < 0.0) ? rlZ[i] : log(rZ[i]);
@@ -673,6 +763,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     for (int i = tid; i < nb * S; i += NT) { const int q = i / S, e = i - q * S; g_MF[(size_t)k0 * S + i] = rMF[(size_t)q * M * 4 + smap[e]]; }
     __syncthreads();
   }
+    }
     if (wk_stamp)
       for (int i = 0; i < 8; ++i) mc.stamps[wk_slot + i] += wk[i];
 #undef WK_STAMP
@@ -780,14 +871,8 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }      // link tables of the first step
   if (stamp) st_a = __builtin_readcyclecounter();
 
-  for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
-    const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
-    // ---- fill the ring for steps k0 .. k0+nb-1
-    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
-    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
-    __syncthreads();
-    for (int kk = 0; kk < nb; ++kk) {
-      const int64_t k = k0 + kk;
+  // one step between its barriers; kk = the step's ring slot
+  auto step = [&](const int64_t k, const int kk) __attribute__((always_inline)) {
       if constexpr (!NB1) {
         lds_barrier();                 // B1: fmu, HPH of step k; its link tables (written by wave 1 on its way here)
         IH_STAMP(3);
@@ -852,7 +937,20 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
           else if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }     // fmu / HPH of the modulators just written by this wave
         }
       }
-    }
+  };
+  if constexpr (NB1) {
+    // the streamed ring: the I/O lanes of the worker role fill and flush it; the serial waves only index it by the step's slot
+    __syncthreads();                 // the first step's inputs (prologue of the I/O lanes)
+    for (int64_t k = ip.k_start; k < T; ++k) step(k, (int)(k & (KB - 1)));
+    __syncthreads();                 // the last step's outputs, flushed by the I/O lanes
+  } else {
+  for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
+    const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
+    // ---- fill the ring for steps k0 .. k0+nb-1
+    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
+    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
+    __syncthreads();
+    for (int kk = 0; kk < nb; ++kk) step(k0 + kk, kk);
     // ---- flush the ring
     __syncthreads();
     for (int i = tid; i < nb; i += NT) g_lZ[k0 + i] = (rZ[i] < 0.0) ? rlZ[i] : log(rZ[i]);
@@ -862,6 +960,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     }
     for (int i = tid; i < nb * S; i += NT) { const int q = i / S, e = i - q * S; g_MF[(size_t)k0 * S + i] = rMF[(size_t)q * M * 4 + smap[e]]; }
     __syncthreads();
+  }
   }
 #undef IH_STAMP
   if (act && n_clamped) atomicAdd(&b.counters[(size_t)pb * 4 + 1], (unsigned long long)n_clamped);
