@@ -367,6 +367,40 @@ int nagp_pstft_obj(int32_t n_problems, int32_t kernel, int32_t form /* 0 closed,
 /* Device time of the two kernels of the last nagp_pstft_obj on this thread, in ms (HIP events, summed over its device batches). */
 int nagp_pstft_timings(double* ms /* 1 */);
 
+/* The objective that experiments/toolsGP/trainSEGP_RS.m minimises -- the modulator prior fit of the training drivers
+ * (experiments/train_model.m:132-149, train_GTFNMF.m:91-108): toolsGP/getObjSEGP.m on toolsGP/getGPSESpec.m with its gradient, the
+ * negative log-likelihood of a regularly sampled squared-exponential GP plus white noise in the spectral domain, for a batch of
+ * problems.  With len = exp(param[0]) and the frequency list of getGPSESpec.m:18, [0:ceil(T/2), -floor(T/2)+1:-1],
+ *     f_j = j for j <= ceil(T/2), else j - T   (j = 0 .. T-1),     w_j = 2 pi f_j / T,
+ *     c_j = sqrt(2 pi len^2) exp(-w_j^2 len^2 / 2),   dc_j = c_j (1/len - w_j^2 len),   S_j = varx c_j + vary,
+ *     g_j = 1/(2 S_j) - specy_j / (2 T S_j^2),
+ *     Obj = (1/2 sum_j log S_j + 1/(2T) sum_j specy_j / S_j) / T,
+ *     dObj = [len varx sum_j g_j dc_j,  varx sum_j g_j c_j,  vary sum_j g_j] / T      (the first n_param entries).
+ * The list is kept as the .m writes it: for odd T entry j = (T+1)/2 has f = +(T+1)/2, not -(T-1)/2 (it enters through w^2).
+ * n_param = 3: varx = exp(param[1]), vary = exp(param[2]); 2: varx = exp(param[1]), vary given; 1: varx and vary given -- the three
+ * nargin branches of the .m (specy = abs(fft(y)).^2 there).
+ * param: n_param per problem, problem-major.  specy: T entries shared by the problems (spec_stride = 0) or T per problem
+ * (spec_stride = T).  dObj = NULL: the objective only (the same Obj bits).
+ * Every sum over the frequencies is formed in a fixed order (a butterfly inside a wave, waves and workgroups in ascending order, the
+ * order over the workgroups a function of T alone; no floating-point atomics): a problem's result is the same to the bit alone, in a
+ * batch, with shared or per-problem specy, and however the call is cut into device batches.
+ * All of the following is decided on the host before any device call.
+ * NAGP_EUNSUPPORTED: one problem beyond the device-memory budget of a call, 1 GiB: a call takes 8 T (when specy is shared) + 4096
+ *   bytes and every problem 8 (ceil(T / 256) (2 + n_param, objective only: 2) + 2 n_param + 3 + T when specy is per problem) bytes.
+ *   A batch whose problems do not all fit runs in device batches of as many as do.
+ * NAGP_EINVAL: a NULL param, specy or Obj; a NULL vary (n_param <= 2) or varx (n_param = 1); n_problems < 1; n_param not 1, 2 or 3;
+ *   T < 2; spec_stride not 0 or T; an input that is not finite; specy < 0; a given vary <= 0; a given varx < 0.
+ * A result that is not finite (exp(param) overflowing, or varx and vary both underflowing to 0) is returned as it is: minimize halves
+ * its step on a non-finite objective. */
+int nagp_segp_obj(int32_t n_problems, int32_t n_param /* 1, 2, 3 */, int64_t T,
+                  const double* param /* n_problems x n_param */,
+                  const double* specy, int64_t spec_stride /* 0 = shared, T = per problem */,
+                  const double* vary /* n_problems, read when n_param <= 2 */,
+                  const double* varx /* n_problems, read when n_param == 1 */,
+                  double* Obj, double* dObj /* n_problems x n_param, or NULL */, int32_t device);
+/* Device time of the two kernels of the last nagp_segp_obj on this thread, in ms (HIP events, summed over its device batches). */
+int nagp_segp_timings(double* ms /* 1 */);
+
 /* What the drivers do next with Eft / Varft (demo_toy_modulators_nmf.m:119-158, the same block in the other
  * demos): the reconstructed signal sig = sum_d (W link(g))_d z_d and the modulator amplitudes link(g_n) under the independent
  * posterior marginals z_d ~ N(Eft_d, Varft_d), g_n ~ N(Eft_{D+n}, Varft_{D+n}) of every time step:

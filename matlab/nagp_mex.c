@@ -32,6 +32,10 @@
  *                                    kernel 'exp' | 'matern32' | 'matern52' | 'matern72'; form 0 (get_Obj_pSTFT_<kernel>.m) or 1
  *                                    (get_Obj_pSTFT_all.m); theta 3D x P; specTar N x 1 (shared) or N x P; vary, bet scalars or P entries;
  *                                    minVar D x 1, limOm, limLam D x 2; Obj P x 1, dObj 3D x P (formed only with two outputs)
+ *   [Obj, dObj] = nagp_mex('segp_obj', param, specy, vary, varx [,device])                                     nagp_segp_obj
+ *                                    param n_param x P (n_param = 1, 2, 3: log len [, log varx [, log vary]]); specy T x 1 (shared) or T x P;
+ *                                    vary (read when n_param <= 2), varx (read when n_param = 1): scalars or P entries, [] where not read;
+ *                                    Obj P x 1, dObj n_param x P (formed only with two outputs)
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
  *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
@@ -327,6 +331,33 @@ static void cmd_pstft_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* pr
   for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
 }
 
+static void cmd_segp_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('segp_obj', param, specy, vary, varx [,device]) -> [Obj, dObj]: the objective of experiments/toolsGP/getObjSEGP.m for P problems;
+     vary / varx may be [] where n_param says they are not read; dObj only when asked for */
+  size_t npar, ns, nv, nx, np, P, T, q; const double *param, *spec, *vary, *varx; double *vy = NULL, *vx = NULL; int32_t dev; int i;
+  mxArray* o[2] = {NULL, NULL};
+  if (nrhs < 5 || nrhs > 6 || nlhs > 2) mexErrMsgIdAndTxt("nagp:arg", "usage: [Obj,dObj] = nagp_mex('segp_obj',param,specy,vary,varx[,device])");
+  param = dvec(prhs[1], "param", &npar); np = param ? mxGetM(prhs[1]) : 0;
+  if (!param || np < 1 || np > 3 || npar % np != 0) mexErrMsgIdAndTxt("nagp:arg", "param must be n_param x P with n_param = 1, 2 or 3");
+  P = npar / np;
+  spec = dvec(prhs[2], "specy", &ns);
+  T = (spec && mxGetN(prhs[2]) == 1 && mxGetM(prhs[2]) == ns) ? ns : (spec ? mxGetM(prhs[2]) : 0);
+  if (!T || (ns != T && ns != T * P)) mexErrMsgIdAndTxt("nagp:arg", "specy must be T x 1 or T x P");
+  vary = dvec(prhs[3], "vary", &nv); varx = dvec(prhs[4], "varx", &nx);
+  if (np <= 2 && (!vary || (nv != 1 && nv != P))) mexErrMsgIdAndTxt("nagp:arg", "vary must be a scalar or hold P entries when param has %d rows", (int)np);
+  if (np == 1 && (!varx || (nx != 1 && nx != P))) mexErrMsgIdAndTxt("nagp:arg", "varx must be a scalar or hold P entries when param has one row");
+  dev = nrhs > 5 ? (int32_t)mxGetScalar(prhs[5]) : 0;
+  if (np <= 2) { vy = (double*)mxCalloc(P, sizeof *vy); for (q = 0; q < P; ++q) vy[q] = vary[nv == 1 ? 0 : q]; }
+  if (np == 1) { vx = (double*)mxCalloc(P, sizeof *vx); for (q = 0; q < P; ++q) vx[q] = varx[nx == 1 ? 0 : q]; }
+  o[0] = mxCreateDoubleMatrix((mwSize)P, 1, mxREAL);
+  if (nlhs > 1) o[1] = mxCreateDoubleMatrix((mwSize)np, (mwSize)P, mxREAL);
+  fail_if(nagp_segp_obj((int32_t)P, (int32_t)np, (int64_t)T, param, spec, ns == T ? 0 : (int64_t)T, vy, vx,
+                        mxGetPr(o[0]), o[1] ? mxGetPr(o[1]) : NULL, dev));
+  if (vy) mxFree(vy);
+  if (vx) mxFree(vx);
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
+}
+
 static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])  (demo_toy_modulators_nmf.m:119-158) */
   size_t n, nv, ngx, ngw, D, N, M, T; const double *E, *V, *W, *gx, *gw; int32_t dev; mxArray* o[4]; int i;
@@ -437,6 +468,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "slowfb")) cmd_slowfb(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "nmf_fp")) cmd_nmf_fp(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "pstft_obj")) cmd_pstft_obj(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "segp_obj")) cmd_segp_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);

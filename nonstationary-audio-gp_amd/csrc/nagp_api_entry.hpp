@@ -682,6 +682,89 @@ extern "C" int nagp_pstft_obj(int32_t n_problems, int32_t kernel, int32_t form, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// objective and gradient of the modulator prior fit, toolsGP/getObjSEGP.m on getGPSESpec.m (see include/nagp.h, nagp_segp.hpp)
+constexpr size_t SEGP_BUDGET_BYTES = (size_t)1 << 30;     // device memory of one call: the problems run in device batches under it
+static thread_local double g_segp_ms = 0.0;
+
+typedef void (*SegpFn)(SegpPar);
+static const SegpFn segp_pass_tab[3] = {segp_pass_kernel<1>, segp_pass_kernel<2>, segp_pass_kernel<3>};
+static const SegpFn segp_finish_tab[3] = {segp_finish_kernel<1>, segp_finish_kernel<2>, segp_finish_kernel<3>};
+
+extern "C" int nagp_segp_timings(double* ms) {
+  if (!ms) FAIL(NAGP_EINVAL, "null argument");
+  ms[0] = g_segp_ms;
+  return NAGP_OK;
+}
+
+extern "C" int nagp_segp_obj(int32_t n_problems, int32_t n_param, int64_t T, const double* param, const double* specy, int64_t spec_stride,
+                             const double* vary, const double* varx, double* Obj, double* dObj, int32_t device) {
+  g_segp_ms = 0.0;                                          // a call that is refused or fails reports no time of an earlier one
+  if (!param || !specy || !Obj) FAIL(NAGP_EINVAL, "null argument");
+  if (n_problems < 1) FAIL(NAGP_EINVAL, "bad sizes (n_problems=%d)", n_problems);
+  if (n_param < 1 || n_param > 3) FAIL(NAGP_EINVAL, "n_param = %d: 1 (log len), 2 (and log varx) or 3 (and log vary)", n_param);
+  if (n_param <= 2 && !vary) FAIL(NAGP_EINVAL, "null vary with n_param = %d", n_param);
+  if (n_param == 1 && !varx) FAIL(NAGP_EINVAL, "null varx with n_param = 1");
+  if (T < 2) FAIL(NAGP_EINVAL, "T=%lld: at least 2 frequencies", (long long)T);
+  if (spec_stride != 0 && spec_stride != T) FAIL(NAGP_EINVAL, "spec_stride = %lld: 0 (shared) or T", (long long)spec_stride);
+  for (size_t e = 0, n = (size_t)n_problems * n_param; e < n; ++e)
+    if (!std::isfinite(param[e])) FAIL(NAGP_EINVAL, "param[%zu] = %g", e, param[e]);
+  for (size_t e = 0, n = spec_stride ? (size_t)n_problems * T : (size_t)T; e < n; ++e)
+    if (!std::isfinite(specy[e]) || specy[e] < 0.0) FAIL(NAGP_EINVAL, "specy[%zu] = %g: the spectrum must be finite and >= 0", e, specy[e]);
+  for (int q = 0; q < n_problems; ++q) {
+    if (n_param <= 2 && (!std::isfinite(vary[q]) || !(vary[q] > 0.0))) FAIL(NAGP_EINVAL, "vary[%d] = %g: finite and > 0", q, vary[q]);
+    if (n_param == 1 && (!std::isfinite(varx[q]) || varx[q] < 0.0)) FAIL(NAGP_EINVAL, "varx[%d] = %g: finite and >= 0", q, varx[q]);
+  }
+  const DevSwitches dev_sw = read_dev_switches();
+  const int grad = dObj ? 1 : 0, n_out = grad ? 2 + n_param : 2;
+  const int64_t nwg64 = (T + SEGP_NT - 1) / SEGP_NT;
+  if (nwg64 > 0x7fffffff / SEGP_MAXOUT) FAIL(NAGP_EUNSUPPORTED, "T=%lld: too many frequencies", (long long)T);
+  const int nwg = (int)nwg64;
+  // the budget rule of include/nagp.h
+  const size_t np = (size_t)n_param, Tz = (size_t)T;
+  const size_t fixed = 8 * (spec_stride ? 0 : Tz) + 4096;
+  const size_t per_problem = 8 * ((spec_stride ? Tz : 0) + (size_t)nwg * n_out + 2 * np + 3);
+  const size_t budget = dev_sw.segp_budget_mb ? (size_t)dev_sw.segp_budget_mb << 20 : SEGP_BUDGET_BYTES;
+  if (fixed + per_problem > budget) FAIL(NAGP_EUNSUPPORTED, "one problem takes %zu B of device memory (budget %zu B)", fixed + per_problem, budget);
+  const int nb = (int)std::min<size_t>({(size_t)n_problems, (budget - fixed) / per_problem, (size_t)32768});
+  if (hipSetDevice(device) != hipSuccess) FAIL(NAGP_EHIP, "hipSetDevice(%d)", device);
+  // one device block (doubles): specy (shared) | per batch: param | vary | varx | specy | part | Obj | dObj
+  const size_t nbz = (size_t)nb;
+  const size_t o_ss = 0, o_pa = o_ss + (spec_stride ? 0 : Tz), o_vy = o_pa + nbz * np, o_vx = o_vy + nbz, o_sp = o_vx + nbz,
+               o_pt = o_sp + (spec_stride ? nbz * Tz : 0), o_ob = o_pt + nbz * nwg * n_out, o_dg = o_ob + nbz, total = o_dg + nbz * np + 2;
+  double* dev = nullptr;
+  if (hipMalloc(&dev, total * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", total * sizeof(double)); }
+  int st = NAGP_OK;
+  if (!spec_stride) ENTRY_HIP(nagp_segp_obj, hipMemcpy(dev + o_ss, specy, Tz * 8, hipMemcpyHostToDevice));
+  const SegpFn kp = segp_pass_tab[n_param - 1], kfin = segp_finish_tab[n_param - 1];
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  for (int i = 0; i < 2; ++i) ENTRY_HIP(nagp_segp_obj, hipEventCreate(&ev[i]));
+  for (int i0 = 0; i0 < n_problems && st == NAGP_OK; i0 += nb) {
+    const int nbk = std::min(nb, n_problems - i0);
+    ENTRY_HIP(nagp_segp_obj, hipMemcpy(dev + o_pa, param + (size_t)i0 * np, (size_t)nbk * np * 8, hipMemcpyHostToDevice));
+    if (n_param <= 2) ENTRY_HIP(nagp_segp_obj, hipMemcpy(dev + o_vy, vary + i0, (size_t)nbk * 8, hipMemcpyHostToDevice));
+    if (n_param == 1) ENTRY_HIP(nagp_segp_obj, hipMemcpy(dev + o_vx, varx + i0, (size_t)nbk * 8, hipMemcpyHostToDevice));
+    if (spec_stride) ENTRY_HIP(nagp_segp_obj, hipMemcpy(dev + o_sp, specy + (size_t)i0 * Tz, (size_t)nbk * Tz * 8, hipMemcpyHostToDevice));
+    SegpPar pp{};
+    pp.T = T; pp.nwg = nwg; pp.grad = grad; pp.param = dev + o_pa; pp.specy = spec_stride ? dev + o_sp : dev + o_ss; pp.spec_stride = spec_stride;
+    pp.vary = dev + o_vy; pp.varx = dev + o_vx; pp.part = dev + o_pt; pp.Obj = dev + o_ob; pp.dObj = dev + o_dg;
+    if (st == NAGP_OK) {
+      (void)hipEventRecord(ev[0], 0);
+      hipLaunchKernelGGL(kp, dim3((unsigned)nwg, (unsigned)nbk), dim3(SEGP_NT), 0, 0, pp);
+      hipLaunchKernelGGL(kfin, dim3((unsigned)nbk), dim3(SEGP_FIN_NT), 0, 0, pp);
+      (void)hipEventRecord(ev[1], 0);
+    }
+    ENTRY_HIP(nagp_segp_obj, hipGetLastError());
+    ENTRY_HIP(nagp_segp_obj, hipDeviceSynchronize());
+    if (st == NAGP_OK) { float ms = 0.f; if (hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) g_segp_ms += ms; }
+    ENTRY_HIP(nagp_segp_obj, hipMemcpy(Obj + i0, dev + o_ob, (size_t)nbk * 8, hipMemcpyDeviceToHost));
+    if (grad) ENTRY_HIP(nagp_segp_obj, hipMemcpy(dObj + (size_t)i0 * np, dev + o_dg, (size_t)nbk * np * 8, hipMemcpyDeviceToHost));
+  }
+  for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]);
+  (void)hipFree(dev);
+  return st;
+}
+
+// ---------------------------------------------------------------------------------------------
 // Multi-GPU batched call (see include/nagp.h): problems round robin over the devices, one host thread + plan per device,
 // RCCL all-reduce of the per-sweep nlZ sums.
 extern "C" int nagp_batch_partition(int32_t n_problems, int32_t n_gpus, int32_t* dev_of) {

@@ -1,0 +1,46 @@
+/* mex_segp_driver.c -- drives the 'segp_obj' command of matlab/nagp_mex.c (compiled against the mock mex.h of this directory) with
+ * the argument list matlab/getObjSEGP.m builds, on dumped arrays: output sizes, and Obj / dObj bit for bit against the dumped results
+ * of the Python call; a call with one output and the default device gives the same Obj.  A dumped vary / varx of no entries is passed
+ * as [].
+ *   mex_segp_driver <dump dir>        exit 0 = sizes right and every value bit-equal */
+#include "dump.h"
+#include "mex.h"
+
+static mxArray* dbl(const char* d, const char* name, size_t rows) {
+  size_t n; double* p;
+  mxArray* a;
+  if (!dump_count(d, name)) return mock_numeric(mxDOUBLE_CLASS, 0, 0, NULL);
+  p = (double*)dump_load(d, name, 8, &n);
+  a = mock_numeric(mxDOUBLE_CLASS, rows, n / rows, p);
+  free(p); return a;
+}
+
+int main(int argc, char** argv) {
+  const char* d = argc > 1 ? argv[1] : ".";
+  const size_t NP = (size_t)dump_scalar(d, "n_param"), T = (size_t)dump_scalar(d, "T"), P = (size_t)dump_scalar(d, "P");
+  size_t n; double* e;
+  const mxArray* prhs[6]; mxArray **plhs, **plhs1;
+  prhs[0] = mock_string("segp_obj");
+  prhs[1] = dbl(d, "param", NP);
+  prhs[2] = dbl(d, "specy", T);
+  prhs[3] = dbl(d, "vary", dump_count(d, "vary"));
+  prhs[4] = dbl(d, "varx", dump_count(d, "varx"));
+  prhs[5] = mock_scalar(0);
+  /* plhs has EXACTLY nlhs slots (heap, so that a sanitizer build sees a gateway that writes past them) */
+  plhs = (mxArray**)malloc(2 * sizeof *plhs);
+  mexFunction(2, plhs, 6, prhs);
+  if (mxGetNumberOfElements(plhs[0]) != P || mxGetM(plhs[0]) != P) { printf("Obj: wrong size\n"); return 1; }
+  if (mxGetNumberOfElements(plhs[1]) != NP * P || mxGetM(plhs[1]) != NP) { printf("dObj: wrong size\n"); return 1; }
+  e = (double*)dump_load(d, "Obj", 8, &n);
+  if (n != P || rel_diff(mxGetPr(plhs[0]), e, n, "Obj") != 0.0 || memcmp(mxGetPr(plhs[0]), e, n * sizeof(double))) { printf("Obj: not bit-equal to the Python call\n"); return 1; }
+  free(e);
+  e = (double*)dump_load(d, "dObj", 8, &n);
+  if (n != NP * P || rel_diff(mxGetPr(plhs[1]), e, n, "dObj") != 0.0 || memcmp(mxGetPr(plhs[1]), e, n * sizeof(double))) { printf("dObj: not bit-equal to the Python call\n"); return 1; }
+  free(e);
+  plhs1 = (mxArray**)malloc(1 * sizeof *plhs1);           /* obj = nagp_mex(...), 5 arguments (default device) */
+  mexFunction(1, plhs1, 5, prhs);
+  if (mxGetNumberOfElements(plhs1[0]) != P || memcmp(mxGetPr(plhs1[0]), mxGetPr(plhs[0]), P * sizeof(double))) {
+    printf("nlhs=1 call: Obj differs from the nlhs=2 call\n"); return 1; }
+  printf("n_param %zu T %zu P %zu bit-equal\n", NP, T, P);
+  return 0;
+}
