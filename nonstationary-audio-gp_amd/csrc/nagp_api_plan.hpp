@@ -752,7 +752,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
             if (need8() <= 156 * 1024) p->lds_sp8 = need8(); else p->kb_sp = kb1;
           }
         }
-        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SP, o->cub_dim, p->sp_ih8, dev.ih_tables), p->sp_ih8 ? p->lds_sp8 : p->lds_sp));
+        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SP, o->cub_dim, p->sp_ih8, dev.ih_tables, dev.stamps), p->sp_ih8 ? p->lds_sp8 : p->lds_sp));
       }
     }
     // likModulatorPreCalcwn: the role-specialised sweep of nagp_momsq.hpp
@@ -763,7 +763,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
       if (needq() > 156 * 1024) p->hph_sq = 0;
       if (needq() <= 156 * 1024) {
         p->sq_ih = 1; p->lds_sq = needq();
-        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SQ, o->cub_dim, true, false), p->lds_sq));
+        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SQ, o->cub_dim, true, false, false), p->lds_sq));
       }
     }
     if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);

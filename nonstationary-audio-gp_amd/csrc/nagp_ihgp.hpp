@@ -8,6 +8,7 @@
 #include <type_traits>
 #include "nagp_kernels.hpp"
 #include "nagp_momsq.hpp"
+#include "nagp_lookup.hpp"
 
 namespace nagp {
 
@@ -563,13 +564,19 @@ __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomC
 //   level-2 results (part)     workers, B4 .. B5                    msr_reduce_bins, behind B5                   B2, B4 of step k+1
 //   c0 / c1 / c2, acc          as in the other schedule             (weights B2 .. B4, level 1 B4 .. B5; acc: one wave)
 //   wwt (static products)      wave 0, once                         wave 0                                       same lane
+//   W rows, look-up grid, H PP H' table: written ahead of the loop (one __syncthreads), read-only in it -- wave 0 reads its row of W
+//     between B4 and B5, both serial waves three grid words and three table entries round the seed in the head (one batch of reads)
+// The serial tail waits for none of its ring stores: the head's LDS reads are issued behind them and return in order, and the loop reads
+// no kernel argument (a scalar load in the head would bring an lgkmcnt(0) for the stores with it): the look-up's constants are copied
+// into vector registers ahead of the loop.
 // The I/O ring of this schedule is circular and streamed: slot k mod KB serves step k (KB = 16, 8 or 4), and four worker waves (2, 3, 6, 7:
 // the SIMDs without a serial wave) move one step's worth per step inside their idle window W(k) = B5(k) .. B2(k+1): they store the inputs
 // of step k+1 (loaded in W(k-1), carried in a register), load those of step k+2 and flush the outputs of step k-1.  The first step is
 // filled ahead of the loop, the last one flushed behind it, one __syncthreads each; no block-level section is left inside the loop.
 //   region                     writer                               last reader                                  ordered by
 //   ring inputs, slot of k+1   I/O lanes, W(k)                      workers' weights (ry), B2(k+1) .. B4(k+1);   B2(k+1)
-//     (y, lZ, ttau, tnu, Z=-1)                                      serial tail of step k+1, behind B5(k+1)
+//     (y, lZ, ttau, tnu, Z=-1)                                      serial waves (ttau, tnu), B4(k+1) .. B5(k+1), beside msr_reduce_tab
+//     ttau, tnu of the slot are next written by the lane that read them (its tail of step k+1, behind B5(k+1))    same lane
 //     the slot's previous step k+1-KB: flushed in W(k+2-KB), at least two windows earlier (KB >= 4)              B2 .. B5 of the steps between
 //   ring outputs, slot of k    serial tail of step k,               flush by the I/O lanes, W(k+1)               B2(k+1) (.. B5(k+1))
 //     (ttau, tnu, R, fm, MF, Z)  B5(k) .. B2(k+1)
@@ -585,13 +592,15 @@ __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomC
 // tables (wave 1) | B2 | ... as above with msr_reduce behind B5.  TAB = true (developer switch NAGP_IH_TABLES=1, the form of the
 // four-wave kernel, the in-build cross-check): B1 as for CD = 7; behind B2 the tables e / t1 / ve on wave 1 and q0 / s0 on workers 3 and
 // 4, one more barrier (B3), then the weights from those tables (msp_stage1b).
-template <int CD, bool TAB>
+template <int CD, bool TAB, bool STAMPS = false>
 __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int NT = MSR_NT;
   constexpr bool NB1 = !TAB && CD <= 6;              // the three-barrier schedule (see above)
+  constexpr bool ST_ON = !NB1 || STAMPS;             // NB1: the stamps are a build of their own (STAMPS), IH_STAMP / WK_STAMP expand to nothing otherwise
+  static_assert(NB1 || !STAMPS, "STAMPS selects among the instantiations of the three-barrier schedule only");
   const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG;
   const int64_t T = sh.T;
   const int pb = blockIdx.x;
@@ -644,10 +653,10 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     // developer diagnostics (NAGP_STAMPS): time lines of worker (NAGP_STAMP_WORKER & 7) in stamps[8..15] and of the last worker in
     // stamps[16..23]
     const int wk_slot = (wave == MSR_W0 + (ip.dbg_wave & 7)) ? 8 : ((wave == MSR_W0 + MSR_NWK - 1) ? 16 : -1);
-    const bool wk_stamp = mc.stamps && wk_slot >= 0 && (tid & 63) == 0;
+    const bool wk_stamp = ST_ON && mc.stamps && wk_slot >= 0 && (tid & 63) == 0;
     unsigned long long wk_a = 0, wk_b = 0, wk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (wk_stamp) wk_a = __builtin_readcyclecounter();
-#define WK_STAMP(slot) do { if (wk_stamp) { wk_b = __builtin_readcyclecounter(); wk[slot] += wk_b - wk_a; wk_a = wk_b; } } while (0)
+#define WK_STAMP(slot) do { if constexpr (ST_ON) if (wk_stamp) { wk_b = __builtin_readcyclecounter(); wk[slot] += wk_b - wk_a; wk_a = wk_b; } } while (0)
     // one step between its barriers; kk = the step's ring slot
     auto wstep = [&](int kk) __attribute__((always_inline)) {
       if constexpr (!NB1) {
@@ -826,17 +835,47 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   double Rprev = (act && ip.k_start > 0) ? b.R[((size_t)pb * T + (ip.k_start - 1)) * M + n] : 0.0;
   unsigned int n_clamped = 0;
   unsigned long long st_a = 0, st_b = 0, st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const bool stamp = mc.stamps && tid == ((ip.dbg_wave & 32) ? 64 : 0);      // time line of wave 0 (NAGP_STAMP_WORKER & 32: of wave 1)
-#define IH_STAMP(slot) do { if (stamp) { st_b = __builtin_readcyclecounter(); st[slot] += st_b - st_a; st_a = st_b; } } while (0)
+  const bool stamp = ST_ON && mc.stamps && tid == ((ip.dbg_wave & 32) ? 64 : 0);      // time line of wave 0 (NAGP_STAMP_WORKER & 32: of wave 1)
+#define IH_STAMP(slot) do { if constexpr (ST_ON) if (stamp) { st_b = __builtin_readcyclecounter(); st[slot] += st_b - st_a; st_a = st_b; } } while (0)
 
-  // head of step k: table look-up, A m, the cubature's inputs (wave 0, no barrier)
+  // NB1: the look-up's constants live in vector registers from here on, so that the loop reads no kernel argument again
+  double lk_lr0 = tb.lr0, lk_inv = tb.inv_dlr, lk_rmax = rmax;
+  int lk_ng2 = NG - 2;
+  if constexpr (NB1) asm volatile("" : "+v"(lk_lr0), "+v"(lk_inv), "+v"(lk_rmax), "+v"(lk_ng2));
+  const bool hph_in_lds = ip.hph_lds != 0;
+
+  // head of step k: table look-up, A m, the cubature's inputs (wave 0, no barrier).  IN_LOOP: k > 0 is known (the tables of k = 0 are the
+  // prologue's).  NB1: the straight-line look-up (nagp_lookup.hpp) -- one branch, for finite R beyond the grid; the three grid words and,
+  // with the H PP H' table in LDS, its three entries round the seed in ONE batch of LDS reads, the index selects among them.
   double hph = 0.0, wc[4] = {0, 0, 0, 0}, Am[4] = {0, 0, 0, 0}, fmun = 0.0;
-  auto head = [&](int64_t k) {
+  auto head = [&](int64_t k, auto IN_LOOP) {
     if (act) {
-      if (k > 0) {
-        const int idx = nearest_idx3(p_rg, NG, tb.lr0, tb.inv_dlr, rmax, Rprev);
-        if (stamp) { asm volatile("" :: "v"(idx)); IH_STAMP(6); }
-        hph = ip.hph_lds ? p_hph[idx] : g_hph[idx];
+      if (decltype(IN_LOOP)::value || k > 0) {
+        int idx;
+        if constexpr (NB1) {
+          if (lookup_beyond(lk_rmax, Rprev)) {
+            idx = lookup_tail(p_rg, lk_ng2 + 2, Rprev);
+            hph = hph_in_lds ? p_hph[idx] : g_hph[idx];
+          } else {
+            const int mid = lookup_mid(lk_ng2, lk_lr0, lk_inv, Rprev);
+            double r0 = p_rg[mid - 1], r1 = p_rg[mid], r2 = p_rg[mid + 1];
+            if (hph_in_lds) {
+              double h0 = p_hph[mid - 1], h1 = p_hph[mid], h2 = p_hph[mid + 1];
+              asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(h0), "+v"(h1), "+v"(h2));
+              const int sel = lookup_pick3(r0, r1, r2, Rprev);
+              idx = mid - 1 + sel;
+              hph = (sel == 0) ? h0 : ((sel == 1) ? h1 : h2);
+            } else {
+              idx = mid - 1 + lookup_pick3(r0, r1, r2, Rprev);
+              hph = g_hph[idx];
+            }
+          }
+          if (stamp) { asm volatile("" :: "v"(idx), "v"(hph)); IH_STAMP(6); }
+        } else {
+          idx = nearest_idx3(p_rg, NG, tb.lr0, tb.inv_dlr, rmax, Rprev);
+          if (stamp) { asm volatile("" :: "v"(idx)); IH_STAMP(6); }
+          hph = ip.hph_lds ? p_hph[idx] : g_hph[idx];
+        }
         const double2* w = reinterpret_cast<const double2*>(g_wcol + (size_t)idx * 4);
         const double2 w0 = w[0], w1 = w[1];
         wc[0] = w0.x; wc[1] = w0.y; wc[2] = w1.x; wc[3] = w1.y;
@@ -857,7 +896,8 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       if (stamp) { IH_STAMP(7); }
     }
   };
-  if (wave <= 1) head(ip.k_start);
+  if (stamp) st_a = __builtin_readcyclecounter();      // (the prologue's head stamps slots 6 / 7 as the loop's do)
+  if (wave <= 1) head(ip.k_start, std::false_type{});
   // NB1: the cubature's inputs of a step straight behind its head, each from this wave's own fmu / HPH stores (msp_wave_fence)
   auto qv_or_link = [&]() {
     msp_wave_fence();
@@ -891,21 +931,32 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       lds_barrier();                 // B4
       IH_STAMP(1);
       // (bin sums: worker waves)
-      if constexpr (NB1) msr_reduce_tab<CD>(x, rt);      // the link-table words of the reduction: no reader of the tables is left behind B5
+      // NB1: what the serial tail needs and what exists ahead of B5 is read here, while the workers form the bin sums -- the site's ttau and
+      // tnu of the ring slot (in place since B2, next written by this lane), wave 0's row of W (static), and the link-table words of the
+      // reduction (no reader of the tables is left behind B5).  Every lane reads: the addresses of idle lanes are those of site 0.
+      const int ko = kk * M;
+      double wr[CD], t_old = 0.0, n_old = 0.0;
+      if constexpr (NB1) {
+        t_old = p_tt[ko]; n_old = p_tn[ko];
+#pragma unroll
+        for (int j = 0; j < CD; ++j) wr[j] = (WT == 0) ? p_w[j] : 0.0;      // (2 CD registers of wave 0's copy, free again behind the outputs)
+        msr_reduce_tab<CD>(x, rt);
+      }
       lds_barrier();                 // B5
       IH_STAMP(2);
       {
-        double wr[CD];
+        if constexpr (!NB1) {
 #pragma unroll
-        for (int j = 0; j < CD; ++j) wr[j] = (WT == 0) ? p_w[j] : wrow[j];      // (2 CD registers of wave 0's copy freed for msr_qv_serial)
+          for (int j = 0; j < CD; ++j) wr[j] = wrow[j];
+        }
         if constexpr (NB1) msr_reduce_bins<CD>(x, rt); else msr_reduce<CD>(x);
         msp_wave_fence();
         if (act) {
-          const int ko = kk * M;
           double Z, d1, d2;
-          msp_outputs<CD>(x.accp, sub, n - D, wr, pEP1, mc.jitter, Z, d1, d2);
+          if constexpr (NB1) msp_outputs_b<CD, WT == 0>(x.accp, n - D, wr, pEP1, mc.jitter, Z, d1, d2);
+          else msp_outputs<CD>(x.accp, sub, n - D, wr, pEP1, mc.jitter, Z, d1, d2);
           if (stamp) { asm volatile("" :: "v"(d2)); IH_STAMP(4); }
-          const double t_old = p_tt[ko], n_old = p_tn[ko];
+          if constexpr (!NB1) { t_old = p_tt[ko]; n_old = p_tn[ko]; }
           // site update (:265-266): -d2/(1+d2 HPH), (d1 - fmu d2)/(1+d2 HPH) through one reciprocal
           const double r1 = rcp_nr(fma(d2, hph, 1.0));
           double tnew = fma(ip.w_new, -d2 * r1, ip.w_old * t_old);
@@ -916,8 +967,12 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
           // (for tnew > 0 the reference's R(:,k) = 1./ttau before the clamp is this value; otherwise :287 overwrites it with Inf)
           // R = inf: ttau = 0, or ttau of underflow size (1/ttau overflows while ys = tnu/ttau stays finite): the reference's
           // (ys - fmu)/(HPH + R) is 0 there; the reciprocal form below would multiply inf by 0
-          double g = 0.0;
-          if (Rn < INFINITY) g = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292)
+          double g = 0.0;                                                  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292)
+          if constexpr (NB1) {                                             // by a select: clamped sites are every-step business
+            double gx = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);
+            asm volatile("" : "+v"(gx));
+            g = (Rn < INFINITY) ? gx : 0.0;
+          } else if (Rn < INFINITY) g = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);
           typedef double d2v __attribute__((ext_vector_type(2)));
           d2v m01, m23;
           mreg[0] = fma(wc[0], g, Am[0]); mreg[1] = fma(wc[1], g, Am[1]); mreg[2] = fma(wc[2], g, Am[2]); mreg[3] = fma(wc[3], g, Am[3]);
@@ -932,7 +987,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
           if (stamp) { asm volatile("" :: "v"(Rprev)); IH_STAMP(5); }
         }
         if (k + 1 < T) {
-          head(k + 1);
+          head(k + 1, std::true_type{});
           if constexpr (NB1) { qv_or_link(); IH_STAMP(3); }      // (slot 3: Q / 2Q / v on wave 0, the link tables on wave 1)
           else if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }     // fmu / HPH of the modulators just written by this wave
         }

@@ -574,6 +574,50 @@ __device__ __forceinline__ void msp_outputs(msp_rp acc, bool sub, int jmod, cons
   d2 = fma(-d1, d1, Zinv * s2);
 }
 
+// msp_outputs where the lane's kind is a constant of the caller's copy of the loop (the serial waves of the three-barrier schedule of
+// ihgp_adf8_kernel): Z's sum and the lane's own sums -- 27 words at CD = 6 on a sub-band lane, two on a modulator lane -- leave in ONE batch
+// of LDS reads ahead of any arithmetic.  The arithmetic is msp_outputs', operation for operation.
+template <int CD, bool SUB>
+__device__ __forceinline__ void msp_outputs_b(msp_rp acc, int jmod, const double* wrow, double pEP, double jitter,
+                                              double& Z, double& d1, double& d2) {
+  constexpr int nq = CD * (CD + 1) / 2;
+  constexpr int NR = SUB ? CD + nq : 2;
+  double av[NR];
+  double Zs = acc[3 * CD + nq];
+  if constexpr (SUB) {
+#pragma unroll
+    for (int q = 0; q < NR; ++q) av[q] = acc[q];
+  } else {
+    av[0] = acc[CD + nq + jmod]; av[1] = acc[2 * CD + nq + jmod];
+  }
+  asm volatile("" : "+v"(Zs));
+#pragma unroll
+  for (int q = 0; q < NR; ++q) asm volatile("" : "+v"(av[q]));
+  Z = pEP * ((Zs > jitter) ? Zs : jitter);          // max(NaN, jitter) = jitter
+  const double Zinv = pEP * rcp_nr(Z);              // Z >= pEP*jitter > 0, finite (or inf: Zinv = NaN like inf/inf)
+  double s1, s2;
+  if constexpr (SUB) {
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (int j = 0; j < CD; ++j) { if (j & 1) a1 = fma(wrow[j], av[j], a1); else a0 = fma(wrow[j], av[j], a0); }
+    s1 = a0 + a1;
+    double b0 = 0.0, b1 = 0.0;
+    int q = 0;
+#pragma unroll
+    for (int j = 0; j < CD; ++j) {
+      double t = 0.5 * av[CD + q] * wrow[j]; ++q;
+#pragma unroll
+      for (int j2 = j + 1; j2 < CD; ++j2) { t = fma(av[CD + q], wrow[j2], t); ++q; }
+      if (j & 1) b1 = fma(2.0 * wrow[j], t, b1); else b0 = fma(2.0 * wrow[j], t, b0);
+    }
+    s2 = b0 + b1;
+  } else {
+    s1 = av[0]; s2 = av[1];
+  }
+  d1 = Zinv * s1;
+  d2 = fma(-d1, d1, Zinv * s2);
+}
+
 // =====================================================================================================================
 // Role layout (LAY = 1): 512 threads.  Waves 0 and 1 carry the serial stages of the caller (wave 1 also evaluates the link
 // tables and e -- with t1 / ve in the table form of stage 1b); waves 2 .. 7 carry the parallel ones: Q / 2Q / v on waves 2..4 (three-barrier schedule of ihgp_adf8_kernel: on wave 0, msr_qv_serial),
