@@ -401,6 +401,49 @@ int nagp_segp_obj(int32_t n_problems, int32_t n_param /* 1, 2, 3 */, int64_t T,
 /* Device time of the two kernels of the last nagp_segp_obj on this thread, in ms (HIP events, summed over its device batches). */
 int nagp_segp_timings(double* ms /* 1 */);
 
+/* The objective that experiments/gppad/GPModelFast/MAPGPFast.m minimises -- the envelope inference of GPPAD(real(Z)', fs/10) in the
+ * training drivers (experiments/train_model.m:113): GPModelFast/GetGPObjFast.m with its gradient, for a batch of problems (one
+ * channel at one resolution each).  With a = GetAmp(x_t) (x > 500: x; x < -30: exp(x); else log(1 + exp(x))), s = 1/(1 + exp(-x_t)),
+ * v_t = a^2 varc + vary_t + 1e-5 for t < T, xe = x - mux (length Tx) and c = fftCov (length Tx, real):
+ *     ObjA = sum_t 1/2 log v_t + 1/2 y_t^2 / v_t,      dA_t = s a / v_t (1 - y_t^2 / v_t) varc,
+ *     u = real(ifft(fft(xe) ./ c)),   ObjB = (u' xe) / (2 varx),   Obj = ObjA + ObjB,   dObj = u / varx, dA added to its first T entries.
+ * x: Tx per problem, problem-major; y: T per problem.  vary: one per problem (vary_stride = 0) or T per problem (vary_stride = T, the
+ * drivers' zeros(T, D) and the missing-data use).  The prior spectrum is either given -- fftCov, Tx entries shared by the problems
+ * (cov_stride = 0) or per problem (cov_stride = Tx), len = NULL -- or formed on the device from len, one per problem, by
+ * GetFFTCovFast.m:10-16, sqrt(2 pi len^2) exp(-w^2 len^2 / 2) + 1e-6 on w = 2 pi [0:Tx/2, -Tx/2+1:-1] / Tx (fftCov = NULL).
+ * dObj = NULL: the objective only (the same Obj bits).
+ * The transform is a complex FP64 FFT of the whole sequence with twiddles from a table built in extended precision: in LDS for
+ * Tx <= 4096, as a four-step Tx = (Tx / 4096) x 4096 split of three kernels above.  u' xe and the sum of ObjA are formed in a fixed order
+ * (a thread's samples ascending, a butterfly inside a wave, waves and workgroups in ascending order, all a function of Tx alone; no
+ * floating-point atomics): a problem's result is the same to the bit alone, in a batch, with shared or own fftCov, with or without
+ * dObj, through the one-shot or the resident form, and however the call is cut into device batches.
+ * The resident form keeps y, vary, 1 / (c Tx), the parameters and the twiddles on the device: nagp_gppad_eval moves x in and Obj, dObj
+ * out.  nagp_gppad_obj is create + eval + destroy.
+ * All of the following is decided on the host before any device call.
+ * NAGP_EUNSUPPORTED: Tx not a power of two, or outside 2 .. 2^20; one problem beyond the budget of the per-evaluation buffers, 1 GiB:
+ *   every problem takes 8 (2 Tx (4 Tx when Tx > 4096) + 2 max(1, Tx / 4096) + 1) bytes of them.  A batch whose problems do not all fit is
+ *   evaluated in device batches of as many as do.  (The resident arrays, 8 (T + 1 or T + Tx or 1) + 24 bytes per problem, are outside it.)
+ * NAGP_EINVAL: a NULL handle, x, y, vary, varx, mux, varc or Obj; n_problems < 1; T < 1; T > Tx; vary_stride not 0 or T; cov_stride not
+ *   0 or Tx; both or neither of len and fftCov; y, vary, len, fftCov, varx, mux or varc not finite; vary < 0; varx <= 0; varc <= 0;
+ *   len <= 0; fftCov <= 0.
+ * x is not examined: a result that is not finite is returned as it is (minimize halves its step on one). */
+typedef struct nagp_gppad nagp_gppad; /* opaque */
+int nagp_gppad_obj(int32_t n_problems, int64_t T, int64_t Tx,
+                   const double* x /* n_problems x Tx */, const double* y /* n_problems x T */,
+                   const double* vary, int64_t vary_stride /* 0 = one per problem, T = per sample */,
+                   const double* len /* n_problems, read when fftCov == NULL */,
+                   const double* fftCov, int64_t cov_stride /* NULL, or 0 = shared, Tx = per problem */,
+                   const double* varx, const double* mux, const double* varc /* n_problems each */,
+                   double* Obj /* n_problems */, double* dObj /* n_problems x Tx, or NULL */, int32_t device);
+int nagp_gppad_create(nagp_gppad** handle, int32_t n_problems, int64_t T, int64_t Tx, const double* y,
+                      const double* vary, int64_t vary_stride, const double* len, const double* fftCov, int64_t cov_stride,
+                      const double* varx, const double* mux, const double* varc, int32_t device);
+int nagp_gppad_eval(nagp_gppad* handle, const double* x, double* Obj, double* dObj /* or NULL */);
+void nagp_gppad_destroy(nagp_gppad* handle);
+/* Device time of the kernels of the last nagp_gppad_eval (or nagp_gppad_obj) on this thread, in ms (HIP events, summed over its device
+ * batches). */
+int nagp_gppad_timings(double* ms /* 1 */);
+
 /* What the drivers do next with Eft / Varft (demo_toy_modulators_nmf.m:119-158, the same block in the other
  * demos): the reconstructed signal sig = sum_d (W link(g))_d z_d and the modulator amplitudes link(g_n) under the independent
  * posterior marginals z_d ~ N(Eft_d, Varft_d), g_n ~ N(Eft_{D+n}, Varft_{D+n}) of every time step:

@@ -36,6 +36,9 @@
  *                                    param n_param x P (n_param = 1, 2, 3: log len [, log varx [, log vary]]); specy T x 1 (shared) or T x P;
  *                                    vary (read when n_param <= 2), varx (read when n_param = 1): scalars or P entries, [] where not read;
  *                                    Obj P x 1, dObj n_param x P (formed only with two outputs)
+ *   [Obj, dObj] = nagp_mex('gppad_obj', x, y, fftCov, varx, mux, varc, vary [,device])                         nagp_gppad_obj
+ *                                    x Tx x P; y T x P; fftCov Tx x 1 (shared) or Tx x P; varx, mux, varc: scalars or P entries;
+ *                                    vary a scalar, T x 1 (the same for every problem) or T x P; Obj P x 1, dObj Tx x P (formed only with two outputs)
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
  *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
@@ -358,6 +361,40 @@ static void cmd_segp_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prh
   for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
 }
 
+static void cmd_gppad_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('gppad_obj', x, y, fftCov, varx, mux, varc, vary [,device]) -> [Obj, dObj]: the objective of gppad/GPModelFast/GetGPObjFast.m for P
+     problems; dObj only when asked for */
+  size_t nx, ny, nc, nv, n3[3], P, Tx, T, q, t; const double *x, *y, *cov, *vary, *par[3]; double *sc[3], *vy; int32_t dev; int i, k;
+  mxArray* o[2] = {NULL, NULL};
+  static const char* names[3] = {"varx", "mux", "varc"};
+  if (nrhs < 8 || nrhs > 9 || nlhs > 2) mexErrMsgIdAndTxt("nagp:arg", "usage: [Obj,dObj] = nagp_mex('gppad_obj',x,y,fftCov,varx,mux,varc,vary[,device])");
+  x = dvec(prhs[1], "x", &nx); Tx = x ? mxGetM(prhs[1]) : 0;
+  if (!x || !Tx || nx % Tx != 0) mexErrMsgIdAndTxt("nagp:arg", "x must be Tx x P");
+  P = nx / Tx;
+  y = dvec(prhs[2], "y", &ny); T = y ? mxGetM(prhs[2]) : 0;
+  if (!y || !T || ny != T * P) mexErrMsgIdAndTxt("nagp:arg", "y must be T x P");
+  cov = dvec(prhs[3], "fftCov", &nc);
+  if (!cov || (nc != Tx && nc != Tx * P)) mexErrMsgIdAndTxt("nagp:arg", "fftCov must be Tx x 1 or Tx x P");
+  for (k = 0; k < 3; ++k) {
+    par[k] = dvec(prhs[4 + k], names[k], &n3[k]);
+    if (!par[k] || (n3[k] != 1 && n3[k] != P)) mexErrMsgIdAndTxt("nagp:arg", "%s must be a scalar or hold P entries", names[k]);
+  }
+  vary = dvec(prhs[7], "vary", &nv);
+  if (!vary || (nv != 1 && nv != T && nv != T * P)) mexErrMsgIdAndTxt("nagp:arg", "vary must be a scalar, T x 1 or T x P");
+  dev = nrhs > 8 ? (int32_t)mxGetScalar(prhs[8]) : 0;
+  for (k = 0; k < 3; ++k) { sc[k] = (double*)mxCalloc(P, sizeof(double)); for (q = 0; q < P; ++q) sc[k][q] = par[k][n3[k] == 1 ? 0 : q]; }
+  vy = (double*)mxCalloc(nv == 1 ? P : T * P, sizeof *vy);
+  if (nv == 1) for (q = 0; q < P; ++q) vy[q] = vary[0];
+  else for (q = 0; q < P; ++q) for (t = 0; t < T; ++t) vy[q * T + t] = vary[nv == T ? t : q * T + t];
+  o[0] = mxCreateDoubleMatrix((mwSize)P, 1, mxREAL);
+  if (nlhs > 1) o[1] = mxCreateDoubleMatrix((mwSize)Tx, (mwSize)P, mxREAL);
+  fail_if(nagp_gppad_obj((int32_t)P, (int64_t)T, (int64_t)Tx, x, y, vy, nv == 1 ? 0 : (int64_t)T, NULL, cov, nc == Tx * P && P > 1 ? (int64_t)Tx : 0,
+                         sc[0], sc[1], sc[2], mxGetPr(o[0]), o[1] ? mxGetPr(o[1]) : NULL, dev));
+  for (k = 0; k < 3; ++k) mxFree(sc[k]);
+  mxFree(vy);
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
+}
+
 static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])  (demo_toy_modulators_nmf.m:119-158) */
   size_t n, nv, ngx, ngw, D, N, M, T; const double *E, *V, *W, *gx, *gw; int32_t dev; mxArray* o[4]; int i;
@@ -469,6 +506,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "nmf_fp")) cmd_nmf_fp(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "pstft_obj")) cmd_pstft_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "segp_obj")) cmd_segp_obj(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "gppad_obj")) cmd_gppad_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);

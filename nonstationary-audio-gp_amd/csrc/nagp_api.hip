@@ -10,6 +10,7 @@
 #include "nagp_nmf.hpp"
 #include "nagp_pstft.hpp"
 #include "nagp_segp.hpp"
+#include "nagp_gppad.hpp"
 #include "../../include/nagp.h"
 
 // every templated kernel is instantiated in one of the inst_*.hip translation units
@@ -19,6 +20,7 @@ NAGP_LIST_SLOWFB(extern template __global__)
 NAGP_LIST_NMF(extern template __global__)
 NAGP_LIST_PSTFT(extern template __global__)
 NAGP_LIST_SEGP(extern template __global__)
+NAGP_LIST_GPPAD(extern template __global__)
 
 #include <algorithm>
 #include <cmath>
@@ -30,6 +32,7 @@ NAGP_LIST_SEGP(extern template __global__)
 #include <set>
 #include <string>
 #include <functional>
+#include <map>
 #include <thread>
 #include <vector>
 
@@ -44,7 +47,7 @@ static thread_local std::string g_last_error;
 // and the scripts under tools/ set it; bench.py and the MEX gateway never do).  The switches that make results meaningless (phase-skipping
 // timing probes) and the test hooks that replace devices or fail allocations say so on stderr once when they are active.
 // read_dev_switches() is the only reader of the environment: nagp_plan_create takes one snapshot into the plan (nagp_plan::dev), which
-// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run, nagp_fastfb_sample, nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj and nagp_segp_obj one per call.
+// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run, nagp_fastfb_sample, nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj and nagp_gppad_create one per call.
 struct DevSwitches {
   // presence switches: on when the variable is set to anything
   bool no_wide = false;          // NAGP_NO_WIDE
@@ -77,6 +80,7 @@ struct DevSwitches {
   int nmf_budget_mb = 0;         // NAGP_NMF_BUDGET_MB (>= 1): device-memory budget of nagp_nmf_fp in MiB instead of NMF_BUDGET_BYTES
   int pstft_budget_mb = 0;       // NAGP_PSTFT_BUDGET_MB (>= 1): device-memory budget of nagp_pstft_obj in MiB instead of PSTFT_BUDGET_BYTES
   int segp_budget_mb = 0;        // NAGP_SEGP_BUDGET_MB (>= 1): device-memory budget of nagp_segp_obj in MiB instead of SEGP_BUDGET_BYTES
+  int gppad_budget_mb = 0;       // NAGP_GPPAD_BUDGET_MB (>= 1): device-memory budget of a nagp_gppad handle's per-evaluation buffers in MiB instead of GPPAD_BUDGET_BYTES
   int kb_f = 0;                  // NAGP_KB_F (1 .. 16)
   int ih_kb = 0;                 // NAGP_IH_KB (4, 8 or 16; anything else: not set): depth of the I/O ring of ihgp_adf8_kernel, where it fits
   int filter_dbg = 0;            // NAGP_FILTER_DBG
@@ -120,6 +124,7 @@ static DevSwitches read_dev_switches() {
   if ((v = env("NAGP_NMF_BUDGET_MB"))) s.nmf_budget_mb = std::max(1, atoi(v));
   if ((v = env("NAGP_PSTFT_BUDGET_MB"))) s.pstft_budget_mb = std::max(1, atoi(v));
   if ((v = env("NAGP_SEGP_BUDGET_MB"))) s.segp_budget_mb = std::max(1, atoi(v));
+  if ((v = env("NAGP_GPPAD_BUDGET_MB"))) s.gppad_budget_mb = std::max(1, atoi(v));
   if ((v = env("NAGP_KB_F"))) s.kb_f = std::max(1, std::min(16, atoi(v)));
   if ((v = env("NAGP_IH_KB"))) { const int kb = atoi(v); s.ih_kb = (kb == 4 || kb == 8 || kb == 16) ? kb : 0; }
   if ((v = env("NAGP_FILTER_DBG"))) s.filter_dbg = atoi(v);
@@ -432,7 +437,8 @@ struct Timed {
   }
 };
 
-// ---- the rest of this translation unit, in three parts (one object file: the parts share the plan struct and the static helpers above)
+// ---- the rest of this translation unit, in four parts (one object file: the parts share the plan struct and the static helpers above)
 #include "nagp_api_plan.hpp"
 #include "nagp_api_sweep.hpp"
 #include "nagp_api_entry.hpp"
+#include "nagp_api_gppad.hpp"

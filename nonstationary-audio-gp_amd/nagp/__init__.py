@@ -16,5 +16,8 @@ from .nmf import nmf_run, nmf_fp, nmf_inf_fp, nmf_init, kernel_ss_probFB, getFBL
 from .pstft import (pstft_obj, get_Obj_pSTFT_exp, get_Obj_pSTFT_matern32, get_Obj_pSTFT_matern52, get_Obj_pSTFT_all,  # noqa: F401
                     welchMethod, freq2probSpec, minimize, fit_probSTFT_SD, fit_probSTFT_SD_many)
 from .segp import segp_obj, getObjSEGP, getGPSESpec, trainSEGP_RS, trainSEGP_RS_many, modulator_prior_init  # noqa: F401
+from .gppad import (gppad_obj, GppadHandle, GetGPObjFast, GetFFTCovFast, GetTx, GetDSs, GetAmp, PackParamsGP, InitPADSampleNonStat,  # noqa: F401
+                    LearnMarginalParams, GridMargParams, GetObjNumericalInt, GetObjNumericalInt2, ConjGradMargParams, MAPGPFast,
+                    InferAmplitudeGPMAP, InferAmplitudeGPMAP_many, FBGPMAP, GPPAD, resample2)
 from .train import nlml_batch, fd_value_and_gradient  # noqa: F401
 from .recon import reconstruct_signal, reconstruct_sources  # noqa: F401

@@ -175,11 +175,17 @@ def kernel_ss_probFB(y, A, Q, C_, P0, K, vary, tau, verbose=0, KF=0, slow=0, nou
     return getFBLDSOutput_tau(Xfin, Pfin, tau, nout)
 
 
-def nmf_init(Z, N, restarts=20, numIts=500, seed=0, device=0):
+def nmf_init(Z, N, restarts=20, numIts=500, seed=0, device=0, mods=None):
     """The W of experiments/train_GTFNMF.m:64-89 from the sub-bands Z (D x T complex): A = abs(Z).T, W0 = A[ks, :], H0 = exp(randn)
     (NumPy's stream from `seed`: H0, then ks as in :76-77, then the restart candidates), nmf_fp with `restarts` and `numIts`, and the components
-    ordered by fastness = mean(diff(H)**2) / var(H), descending (:85-89).  Returns WEst (N x D), HEst (T x N), info."""
+    ordered by fastness = mean(diff(H)**2) / var(H), descending (:85-89).  mods (T x D): the demodulated envelopes of GPPAD(real(Z)', fs/10),
+    which the drivers factorise in place of abs(Z)' (:73, :78-83); Z then only gives the shape.  Returns WEst (N x D), HEst (T x N), info."""
     A = np.abs(np.asarray(Z)).T; T = A.shape[0]; N = int(N)
+    if mods is not None:
+        mods = np.asarray(mods, float)
+        if mods.shape != A.shape or not np.all(np.isfinite(mods)) or np.any(mods < 0):
+            raise ValueError('mods must be T x D = %s, finite and >= 0: got %s' % (A.shape, mods.shape))
+        A = mods
     rng = np.random.default_rng(seed)
     H0 = np.exp(rng.standard_normal((T, N)))                                                 # :76
     ks = np.ceil(T * rng.random(N)).astype(int)                                              # :77
