@@ -444,6 +444,61 @@ void nagp_gppad_destroy(nagp_gppad* handle);
  * batches). */
 int nagp_gppad_timings(double* ms /* 1 */);
 
+/* The objectives that experiments/nmf/nmf.m and nmf_inf.m minimise by conjugate gradients -- the NMF with temporal priors on the
+ * activations that the training drivers keep next to their nmf_fp call (train_model.m:123), and its inference-only form for missing
+ * data and denoising: getObj_nmf_temp.m (learning form, W = NULL: x = [log H(:); log W(:)], T K + K D entries per problem) and
+ * getObj_nmf_temp_inf.m (inference form, W given, K x D per problem: x = log H(:), T K entries), with their gradients, for a batch of
+ * problems (restarts) that share A and vary.  All matrices column-major: A, vary T x D, H T x K, W K x D.  Kept literally (:45-66):
+ *     H = exp(logH);   learning form: W = exp(logW), W = diag(1 ./ sum(W,2)) W;   inference form: W as given, NOT renormalised
+ *     Ahat = H W + vary,   obj1 = sum(A ./ Ahat + log(Ahat)),   dA = (Ahat - A) ./ Ahat.^2,   dlogh = (dA W') .* H,
+ *     learning form: dW = H' dA, dWW = dW .* W, dlogw = dWW - diag(sum(dWW,2)) W.
+ * The prior stands for the .m's nargin branches:
+ *   NAGP_NMFT_NONE: obj = obj1 / T.
+ *   NAGP_NMFT_TG (:109-131), truncated-Gaussian AR(1) chain with varinf, lam (K each):
+ *     obj2 = sum_k (1+lam^2)/(2 varinf) sum_{t=2..T-1} H^2 + 1/(2 varinf) H(T)^2 + lam^2/(2 varinf) H(1)^2 - lam/varinf sum_{t=2..T} H(t) H(t-1),
+ *     dobj2dH: t = 1: lam^2/varinf H(1) - lam/varinf H(2);   1 < t < T: (1+lam^2)/varinf H(t) - lam/varinf (H(t+1) + H(t-1));
+ *              t = T: 1/varinf H(T) - lam/varinf H(T-1)      -- three different row forms, as the .m has them.
+ *   NAGP_NMFT_IG (:69-107), inverse-gamma Markov chain with muinf, varinf, lam: alp1 = muinf^2/varinf + 2, bet1 = (alp1 - 1) muinf,
+ *     alp = 2 + lam^2 + muinf^2/varinf, a = (alp - 1) lam, b = (alp - 1)(1 - lam) muinf, ahtpb(t) = a H(t) + b (t < T),
+ *     obj2 = sum_k bet1/H(1) + (alp1+1) logH(1) - alp sum_{t<T} log ahtpb(t) + (alp+1) sum_{t>1} logH(t) + sum_{t>1} ahtpb(t-1)/H(t),
+ *     dobj2dH: t = 1: a/H(2) - bet1/H(1)^2 + (alp1+1)/H(1) - alp a/ahtpb(1);
+ *              1 < t < T: a/H(t+1) - ahtpb(t-1)/H(t)^2 + (alp+1)/H(t) - alp a/ahtpb(t);   t = T: -ahtpb(T-1)/H(T)^2 + (1+alp)/H(T).
+ *   With a prior obj = (obj1 + obj2) / T and dlogh += dobj2dH .* H; the whole gradient is divided by T.
+ * muinf, varinf, lam: K each, shared by the problems; NULL where the prior does not read them.  vary = NULL: zeros.  dObj = NULL: the
+ * objective only (the same Obj bits).  Every sum over t is formed in an order that depends on the shape alone (a butterfly inside a
+ * wave, the waves of a workgroup and the workgroups in a fixed order; the K x D products H' dA on the matrix cores per workgroup; no
+ * floating-point atomics): a problem's result is the same to the bit alone, in a batch, with or without dObj, through the one-shot or
+ * the resident form, and however the call is cut into device batches.
+ * The resident form keeps A, vary, a given W, the prior parameters and the partial-sum buffers on the device: nagp_nmf_temp_eval moves x
+ * in and Obj, dObj out.  nagp_nmf_temp_obj is create + eval + destroy.
+ * All of the following is decided on the host before any device call.
+ * NAGP_EINVAL: a NULL handle, x, A or Obj; n_problems, D or K < 1; T < 1, or T < 2 with a prior (the .m indexes H(2,:)); an unknown
+ *   prior; a prior parameter array NULL where it is read; A, vary, W or a prior parameter not finite; a negative A or vary; a negative
+ *   entry or an all-zero row of a given W; varinf <= 0; for NAGP_NMFT_IG muinf <= 0 or lam outside [0, 1] (beyond that ahtpb can be
+ *   negative and its log fails).
+ * NAGP_EUNSUPPORTED: D > 64 or K > 16 (W lives in the LDS, H(t,:) in registers, K is padded to one MFMA tile); one problem beyond the
+ *   budget of the per-evaluation buffers, 1 GiB: with nx = T K (+ K D in the learning form) and nq = 0, 4, 5 for NONE, TG, IG every
+ *   problem takes 8 (2 nx + ceil(T / 256) ((K D in the learning form) + 1 + nq K) + 1) bytes of them.  A batch whose problems do not all
+ *   fit is evaluated in device batches of as many as do.  (The resident arrays, 8 T D (twice with vary) + 8 K D per problem of a given
+ *   W + 24 K bytes, are outside it.)
+ * x is not examined: a result that is not finite is returned as it is (minimize halves its step on one). */
+enum { NAGP_NMFT_NONE = 0, NAGP_NMFT_TG = 1, NAGP_NMFT_IG = 2 };
+typedef struct nagp_nmf_temp nagp_nmf_temp; /* opaque */
+int nagp_nmf_temp_obj(int32_t n_problems, int64_t T, int32_t D, int32_t K, int32_t prior,
+                      const double* x /* n_problems x (T K + K D), or x (T K) with W */,
+                      const double* A /* T x D, shared */, const double* vary /* T x D shared, or NULL = zeros */,
+                      const double* W /* NULL: learning form; else K x D per problem: inference form */,
+                      const double* muinf, const double* varinf, const double* lam /* K each, shared; NULL where not read */,
+                      double* Obj /* n_problems */, double* dObj /* as x, or NULL = objective only */, int32_t device);
+int nagp_nmf_temp_create(nagp_nmf_temp** handle, int32_t n_problems, int64_t T, int32_t D, int32_t K, int32_t prior,
+                         const double* A, const double* vary, const double* W,
+                         const double* muinf, const double* varinf, const double* lam, int32_t device);
+int nagp_nmf_temp_eval(nagp_nmf_temp* handle, const double* x, double* Obj, double* dObj /* or NULL */);
+void nagp_nmf_temp_destroy(nagp_nmf_temp* handle);
+/* Device time of the two kernels of the last nagp_nmf_temp_eval (or nagp_nmf_temp_obj) on this thread, in ms (HIP events, summed over
+ * its device batches). */
+int nagp_nmf_temp_timings(double* ms /* 1 */);
+
 /* What the drivers do next with Eft / Varft (demo_toy_modulators_nmf.m:119-158, the same block in the other
  * demos): the reconstructed signal sig = sum_d (W link(g))_d z_d and the modulator amplitudes link(g_n) under the independent
  * posterior marginals z_d ~ N(Eft_d, Varft_d), g_n ~ N(Eft_{D+n}, Varft_{D+n}) of every time step:

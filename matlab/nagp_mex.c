@@ -39,6 +39,11 @@
  *   [Obj, dObj] = nagp_mex('gppad_obj', x, y, fftCov, varx, mux, varc, vary [,device])                         nagp_gppad_obj
  *                                    x Tx x P; y T x P; fftCov Tx x 1 (shared) or Tx x P; varx, mux, varc: scalars or P entries;
  *                                    vary a scalar, T x 1 (the same for every problem) or T x P; Obj P x 1, dObj Tx x P (formed only with two outputs)
+ *   [Obj, dObj] = nagp_mex('nmf_temp_obj', x, A, vary, W, muinf, varinf, lam [,device])                        nagp_nmf_temp_obj
+ *                                    A T x D; vary T x D or [] (zeros); W [] -- the learning form, x (T K + K D) x P -- or K x D (shared) or
+ *                                    K x D x P -- the inference form, x (T K) x P; muinf, varinf, lam: K entries or []: varinf empty = no prior,
+ *                                    muinf empty = the truncated-Gaussian chain, none empty = the inverse-gamma chain (nmf.m:119-131);
+ *                                    Obj P x 1, dObj as x (formed only with two outputs)
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
  *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
@@ -395,6 +400,49 @@ static void cmd_gppad_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* pr
   for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
 }
 
+static void cmd_nmf_temp_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('nmf_temp_obj', x, A, vary, W, muinf, varinf, lam [,device]) -> [Obj, dObj]: the objectives of experiments/nmf/getObj_nmf_temp.m (W = [])
+     and getObj_nmf_temp_inf.m for P problems; dObj only when asked for */
+  size_t nx, na, nv, nw, n3[3], P, T, D, K, X, q; const double *x, *A, *vary, *W, *par[3]; double* wp = NULL; int32_t dev, prior; int i, k;
+  mxArray* o[2] = {NULL, NULL};
+  static const char* names[3] = {"muinf", "varinf", "lam"};
+  if (nrhs < 8 || nrhs > 9 || nlhs > 2) mexErrMsgIdAndTxt("nagp:arg", "usage: [Obj,dObj] = nagp_mex('nmf_temp_obj',x,A,vary,W,muinf,varinf,lam[,device])");
+  A = dvec(prhs[2], "A", &na); T = A ? mxGetM(prhs[2]) : 0;
+  if (!A || !T || na % T != 0) mexErrMsgIdAndTxt("nagp:arg", "A must be T x D");
+  D = na / T;
+  vary = dvec(prhs[3], "vary", &nv);
+  if (vary && nv != na) mexErrMsgIdAndTxt("nagp:arg", "vary must be T x D or []");
+  x = dvec(prhs[1], "x", &nx); X = x ? mxGetM(prhs[1]) : 0;
+  if (!x || !X || nx % X != 0) mexErrMsgIdAndTxt("nagp:arg", "x must hold one column per problem");
+  P = nx / X;
+  W = dvec(prhs[4], "W", &nw);
+  if (W) {
+    K = mxGetM(prhs[4]);
+    if (!K || (nw != K * D && nw != K * D * P)) mexErrMsgIdAndTxt("nagp:arg", "W must be K x D or K x D x P");
+    if (X != T * K) mexErrMsgIdAndTxt("nagp:arg", "x must be (T K) x P with a given W");
+  } else {
+    K = X / (T + D);
+    if (!K || K * (T + D) != X) mexErrMsgIdAndTxt("nagp:arg", "x must be (T K + K D) x P without W");
+  }
+  for (k = 0; k < 3; ++k) {
+    par[k] = dvec(prhs[5 + k], names[k], &n3[k]);
+    if (par[k] && n3[k] != K) mexErrMsgIdAndTxt("nagp:arg", "%s must hold K entries or be []", names[k]);
+  }
+  prior = !par[1] ? NAGP_NMFT_NONE : (!par[0] ? NAGP_NMFT_TG : NAGP_NMFT_IG);
+  if (prior != NAGP_NMFT_NONE && !par[2]) mexErrMsgIdAndTxt("nagp:arg", "lam is empty but varinf is not");
+  dev = nrhs > 8 ? (int32_t)mxGetScalar(prhs[8]) : 0;
+  if (W && nw == K * D && P > 1) {                         /* a shared W: one copy per problem */
+    wp = (double*)mxCalloc(K * D * P, sizeof *wp);
+    for (q = 0; q < P; ++q) memcpy(wp + q * K * D, W, K * D * sizeof *wp);
+  }
+  o[0] = mxCreateDoubleMatrix((mwSize)P, 1, mxREAL);
+  if (nlhs > 1) o[1] = mxCreateDoubleMatrix((mwSize)X, (mwSize)P, mxREAL);
+  fail_if(nagp_nmf_temp_obj((int32_t)P, (int64_t)T, (int32_t)D, (int32_t)K, prior, x, A, vary, wp ? wp : W, prior == NAGP_NMFT_IG ? par[0] : NULL,
+                            prior != NAGP_NMFT_NONE ? par[1] : NULL, prior != NAGP_NMFT_NONE ? par[2] : NULL, mxGetPr(o[0]), o[1] ? mxGetPr(o[1]) : NULL, dev));
+  if (wp) mxFree(wp);
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
+}
+
 static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])  (demo_toy_modulators_nmf.m:119-158) */
   size_t n, nv, ngx, ngw, D, N, M, T; const double *E, *V, *W, *gx, *gw; int32_t dev; mxArray* o[4]; int i;
@@ -507,6 +555,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "pstft_obj")) cmd_pstft_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "segp_obj")) cmd_segp_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "gppad_obj")) cmd_gppad_obj(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "nmf_temp_obj")) cmd_nmf_temp_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);

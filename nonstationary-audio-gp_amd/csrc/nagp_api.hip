@@ -11,6 +11,7 @@
 #include "nagp_pstft.hpp"
 #include "nagp_segp.hpp"
 #include "nagp_gppad.hpp"
+#include "nagp_nmf_temp.hpp"
 #include "../../include/nagp.h"
 
 // every templated kernel is instantiated in one of the inst_*.hip translation units
@@ -21,6 +22,7 @@ NAGP_LIST_NMF(extern template __global__)
 NAGP_LIST_PSTFT(extern template __global__)
 NAGP_LIST_SEGP(extern template __global__)
 NAGP_LIST_GPPAD(extern template __global__)
+NAGP_LIST_NMFT(extern template __global__)
 
 #include <algorithm>
 #include <cmath>
@@ -47,7 +49,7 @@ static thread_local std::string g_last_error;
 // and the scripts under tools/ set it; bench.py and the MEX gateway never do).  The switches that make results meaningless (phase-skipping
 // timing probes) and the test hooks that replace devices or fail allocations say so on stderr once when they are active.
 // read_dev_switches() is the only reader of the environment: nagp_plan_create takes one snapshot into the plan (nagp_plan::dev), which
-// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run, nagp_fastfb_sample, nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj and nagp_gppad_create one per call.
+// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run, nagp_fastfb_sample, nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj, nagp_gppad_create and nagp_nmf_temp_create one per call.
 struct DevSwitches {
   // presence switches: on when the variable is set to anything
   bool no_wide = false;          // NAGP_NO_WIDE
@@ -68,6 +70,7 @@ struct DevSwitches {
   bool fb_sequential = false;    // NAGP_FB_SEQUENTIAL
   bool force_rccl = false;       // NAGP_FORCE_RCCL
   bool stamps = false;           // NAGP_STAMPS
+  bool nmft_valu = false;        // NAGP_NMFT_VALU: the H' dA partial products of nmft_pass_kernel on the VALU instead of the matrix cores
   bool ih_roles = true;          // NAGP_IH_ROLES: off when the value starts with '0'
   bool ih_tables = false;        // NAGP_IH_TABLES: on when the value starts with '1' (table form of stage 1b in ihgp_adf8_kernel)
   int gain_form = 0;             // NAGP_GAIN_FORM: 0 = the plan's rule, 1 = solve, 2 = inv
@@ -81,6 +84,7 @@ struct DevSwitches {
   int pstft_budget_mb = 0;       // NAGP_PSTFT_BUDGET_MB (>= 1): device-memory budget of nagp_pstft_obj in MiB instead of PSTFT_BUDGET_BYTES
   int segp_budget_mb = 0;        // NAGP_SEGP_BUDGET_MB (>= 1): device-memory budget of nagp_segp_obj in MiB instead of SEGP_BUDGET_BYTES
   int gppad_budget_mb = 0;       // NAGP_GPPAD_BUDGET_MB (>= 1): device-memory budget of a nagp_gppad handle's per-evaluation buffers in MiB instead of GPPAD_BUDGET_BYTES
+  int nmft_budget_mb = 0;        // NAGP_NMFT_BUDGET_MB (>= 1): device-memory budget of a nagp_nmf_temp handle's per-evaluation buffers in MiB instead of NMFT_BUDGET_BYTES
   int kb_f = 0;                  // NAGP_KB_F (1 .. 16)
   int ih_kb = 0;                 // NAGP_IH_KB (4, 8 or 16; anything else: not set): depth of the I/O ring of ihgp_adf8_kernel, where it fits
   int filter_dbg = 0;            // NAGP_FILTER_DBG
@@ -111,7 +115,7 @@ static DevSwitches read_dev_switches() {
   s.no_pipeline = env("NAGP_NO_PIPELINE"); s.no_recycle = env("NAGP_NO_RECYCLE"); s.no_xsweep = env("NAGP_NO_XSWEEP");
   s.no_cache_tabs = env("NAGP_NO_CACHE_TABS"); s.no_gf_roles = env("NAGP_NO_GF_ROLES"); s.no_gain768 = env("NAGP_NO_GAIN768");
   s.no_gain_mfma = env("NAGP_NO_GAIN_MFMA"); s.ih_seq = env("NAGP_IH_SEQ"); s.fb_sequential = env("NAGP_FB_SEQUENTIAL");
-  s.force_rccl = env("NAGP_FORCE_RCCL"); s.stamps = env("NAGP_STAMPS");
+  s.force_rccl = env("NAGP_FORCE_RCCL"); s.stamps = env("NAGP_STAMPS"); s.nmft_valu = env("NAGP_NMFT_VALU");
   const char* v;
   if ((v = env("NAGP_IH_ROLES"))) s.ih_roles = v[0] != '0';
   if ((v = env("NAGP_IH_TABLES"))) s.ih_tables = v[0] == '1';
@@ -125,6 +129,7 @@ static DevSwitches read_dev_switches() {
   if ((v = env("NAGP_PSTFT_BUDGET_MB"))) s.pstft_budget_mb = std::max(1, atoi(v));
   if ((v = env("NAGP_SEGP_BUDGET_MB"))) s.segp_budget_mb = std::max(1, atoi(v));
   if ((v = env("NAGP_GPPAD_BUDGET_MB"))) s.gppad_budget_mb = std::max(1, atoi(v));
+  if ((v = env("NAGP_NMFT_BUDGET_MB"))) s.nmft_budget_mb = std::max(1, atoi(v));
   if ((v = env("NAGP_KB_F"))) s.kb_f = std::max(1, std::min(16, atoi(v)));
   if ((v = env("NAGP_IH_KB"))) { const int kb = atoi(v); s.ih_kb = (kb == 4 || kb == 8 || kb == 16) ? kb : 0; }
   if ((v = env("NAGP_FILTER_DBG"))) s.filter_dbg = atoi(v);
@@ -442,3 +447,4 @@ struct Timed {
 #include "nagp_api_sweep.hpp"
 #include "nagp_api_entry.hpp"
 #include "nagp_api_gppad.hpp"
+#include "nagp_api_nmf_temp.hpp"

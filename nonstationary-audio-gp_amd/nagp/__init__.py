@@ -19,5 +19,7 @@ from .segp import segp_obj, getObjSEGP, getGPSESpec, trainSEGP_RS, trainSEGP_RS_
 from .gppad import (gppad_obj, GppadHandle, GetGPObjFast, GetFFTCovFast, GetTx, GetDSs, GetAmp, PackParamsGP, InitPADSampleNonStat,  # noqa: F401
                     LearnMarginalParams, GridMargParams, GetObjNumericalInt, GetObjNumericalInt2, ConjGradMargParams, MAPGPFast,
                     InferAmplitudeGPMAP, InferAmplitudeGPMAP_many, FBGPMAP, GPPAD, resample2)
+from . import nmf_temp  # noqa: F401  (its driver `nmf` is reached as nagp.nmf_temp.nmf: nagp.nmf is the module of the fixed-point NMF)
+from .nmf_temp import nmf_temp_obj, NmfTempHandle, getObj_nmf_temp, getObj_nmf_temp_inf, nmf_inf, nmf_inf_many  # noqa: F401
 from .train import nlml_batch, fd_value_and_gradient  # noqa: F401
 from .recon import reconstruct_signal, reconstruct_sources  # noqa: F401

@@ -81,7 +81,9 @@ EXPORTS = ['nagp_version', 'nagp_device_count', 'nagp_strerror', 'nagp_last_erro
            'nagp_batch_partition', 'nagp_batch_run', 'nagp_shutdown', 'nagp_reconstruct', 'nagp_mom_eval', 'nagp_iekf_update1', 'nagp_fastfb_run',
            'nagp_giekf_nlml_grad', 'nagp_plan_set_windows', 'nagp_plan_window_stats', 'nagp_window_partition', 'nagp_reconstruct_sources', 'nagp_fastfb_sample',
            'nagp_slowfb_run', 'nagp_slowfb_timings', 'nagp_nmf_fp', 'nagp_nmf_timings', 'nagp_pstft_obj', 'nagp_pstft_timings',
-           'nagp_segp_obj', 'nagp_segp_timings', 'nagp_gppad_obj', 'nagp_gppad_create', 'nagp_gppad_eval', 'nagp_gppad_destroy', 'nagp_gppad_timings']
+           'nagp_segp_obj', 'nagp_segp_timings', 'nagp_gppad_obj', 'nagp_gppad_create', 'nagp_gppad_eval', 'nagp_gppad_destroy', 'nagp_gppad_timings',
+           'nagp_nmf_temp_obj', 'nagp_nmf_temp_create', 'nagp_nmf_temp_eval', 'nagp_nmf_temp_destroy', 'nagp_nmf_temp_timings']
+NMFT_NONE, NMFT_TG, NMFT_IG = 0, 1, 2
 
 
 class NagpError(RuntimeError):
@@ -237,6 +239,14 @@ def lib():
     L.nagp_gppad_eval.argtypes = [C.c_void_p, c_dp, c_dp, c_dp]; L.nagp_gppad_eval.restype = C.c_int
     L.nagp_gppad_destroy.argtypes = [C.c_void_p]; L.nagp_gppad_destroy.restype = None
     L.nagp_gppad_timings.argtypes = [c_dp]; L.nagp_gppad_timings.restype = C.c_int
+    nmft_data = [c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]                                   # A, vary, W, muinf, varinf, lam
+    L.nagp_nmf_temp_obj.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_dp] + nmft_data + [c_dp, c_dp, C.c_int32]
+    L.nagp_nmf_temp_obj.restype = C.c_int
+    L.nagp_nmf_temp_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32] + nmft_data + [C.c_int32]
+    L.nagp_nmf_temp_create.restype = C.c_int
+    L.nagp_nmf_temp_eval.argtypes = [C.c_void_p, c_dp, c_dp, c_dp]; L.nagp_nmf_temp_eval.restype = C.c_int
+    L.nagp_nmf_temp_destroy.argtypes = [C.c_void_p]; L.nagp_nmf_temp_destroy.restype = None
+    L.nagp_nmf_temp_timings.argtypes = [c_dp]; L.nagp_nmf_temp_timings.restype = C.c_int
     L.nagp_giekf_nlml_grad.argtypes = [C.c_int32, C.POINTER(Model), C.POINTER(c_dp), C.c_int64, C.c_int32, C.POINTER(c_dp), C.POINTER(c_dp), C.POINTER(c_dp),
                                        c_dp, c_ip, c_ip, c_ip, c_dp, c_dp, C.c_int32]
     L.nagp_giekf_nlml_grad.restype = C.c_int
