@@ -162,7 +162,7 @@ extern "C" int nagp_fastfb_run(int32_t S, const double* A, const double* AKHA, c
   const size_t lds = fb_lds_doubles(S, mat_global) * sizeof(double);
   if (S > 256) FAIL(NAGP_EUNSUPPORTED, "S=%d: the stationary filterbank runs a thread per state (S <= 256)", S);
   if (hipSetDevice(device) != hipSuccess) FAIL(NAGP_EHIP, "hipSetDevice(%d)", device);
-  // spans of the parallel-in-time form (needs two more S x S work matrices in LDS: S <= 64); short series run as one span
+  // spans of the parallel-in-time form (needs two more (S+4) x (S+4) work matrices in LDS: fb_compose_lds_doubles fits 160 KiB up to S = 69); short series run as one span
   const size_t lds_c = fb_compose_lds_doubles(S) * sizeof(double);
   int ns = 1;
   if (lds_c <= 160 * 1024 && T >= 2048 && !read_dev_switches().fb_sequential) ns = (int)std::min<int64_t>(512, T / 128);

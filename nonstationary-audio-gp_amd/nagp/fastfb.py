@@ -3,9 +3,9 @@
     [A,Q,H,Pinf,K,tau1] = get_disc_model(lamx,varx,omega,D,kernel,se_approx_order)     unifying_prob_tf/get_disc_model.m
     [lik,Xfin,Pfin]     = kernel_ss_kalmanFastFB(A,Q,C,P0,K,vary,y,verbose,KF)         unifying_prob_tf/kernel_ss_kalmanFastFB.m
 
-The set-up (`dare`, stationary gain, smoother gain) stays on the host exactly where the .m has it -- SciPy's
-solve_discrete_are / solve_discrete_lyapunov stand for the Control-System-Toolbox `dare` -- and the two O(T) loops run on
-the GPU (nagp_fastfb_run).  There is no CPU fallback.
+The set-up (`dare`, stationary gain, smoother gain) stays on the host where the .m has it -- float64 doubling iterations stand
+for the Control-System-Toolbox `dare` (_steady_state; pinned to a 60-digit solution in tests/test_fastfb_host.py) -- and the two
+O(T) loops run on the GPU (nagp_fastfb_run).  There is no CPU fallback.
 `kernel_ss_sampleFastFB` draws whole posterior trajectories on the same model (nagp_fastfb_sample).
 """
 import ctypes as C
@@ -36,25 +36,73 @@ def get_disc_model(lamx, varx, omega, D, kernel, se_approx_order=6):
     return sla.block_diag(*Ab), sla.block_diag(*Qb), np.hstack(Hb), sla.block_diag(*Pb), D * tau1, tau1
 
 
+def _dare_doubling(A, H, Q, R, iters=60, tol=1e-15):
+    """PP = dare(A', H', Q, R) by the structure-preserving doubling iteration of ihgp_tables._dare_batch, one equation:
+    W = I + G H ; A+ = A W^-1 A ; G+ = G + A W^-1 G A' ; H+ = H + A' H W^-1 A  ->  H_k -> PP.  None unless it converges
+    (and for R = 0, where G_0 = H' R^-1 H does not exist)."""
+    if not R > 0:
+        return None
+    S = A.shape[0]; eye = np.eye(S)
+    Ak = np.array(A.T); Gk = H.T @ H / R; Hk = (Q + Q.T) / 2
+    with np.errstate(all='ignore'):
+        for _ in range(iters):
+            W = eye + Gk @ Hk
+            WiA = np.linalg.solve(W, Ak); WiG = np.linalg.solve(W, Gk)
+            Hn = Hk + Ak.T @ Hk @ WiA
+            d = np.max(np.abs(Hn - Hk)) / max(np.max(np.abs(Hn)), 1e-300)
+            Ak, Gk, Hk = Ak @ WiA, Gk + Ak @ WiG @ Ak.T, (Hn + Hn.T) / 2
+            if d < tol:
+                break
+    return Hk if np.all(np.isfinite(Hk)) and d < tol else None
+
+
+def _stein_doubling(G, QQ, iters=60, tol=1e-15):
+    """X = G X G' + QQ (dare(G', 0, QQ)) by doubling: X <- X + G_k X G_k', G_k <- G_k^2."""
+    X = QQ; Gk = G
+    for _ in range(iters):
+        Xn = X + Gk @ X @ Gk.T
+        d = np.max(np.abs(Xn - X)) / max(np.max(np.abs(Xn)), 1e-300)
+        X = (Xn + Xn.T) / 2; Gk = Gk @ Gk
+        if d < tol:
+            break
+    return X
+
+
 def _steady_state(A, Q, C_, vary, KF=0):
     """The set-up lines of kernel_ss_kalmanFastFB.m (:46-77, :127-132): DARE, stationary gain, smoother gain and covariance.
-    Returns A (Fortran order), H (1 x S), R, Sinn, Kg, HA, AKHA, PF2, G and Psm (both None when KF == 1)."""
+    Returns A (Fortran order), H (1 x S), R, Sinn, Kg, HA, AKHA, PF2, G and Psm (both None when KF == 1).
+    The steady-state covariances of Matern-5/2 filterbanks are conditioned 1e8 and worse, so the equations of the .m are solved in
+    forms that hold PF2 and Psm to 1e-12 of a 60-digit solution (tests/test_fastfb_host.py) where the QZ / Bartels-Stewart route
+    is 1e-9 .. 1e-7 away: the DARE by doubling; G = PF2*A'/PP by a Cholesky solve against PP = A*PF2*A' + Q formed from the
+    symmetrised PF2 (the same matrix in exact arithmetic; its rounding is then consistent with the right-hand side, which
+    cond(PP) would otherwise amplify); QQ = PF2 - G*PP*G' as the equal sum (I-GA)*PF2*(I-GA)' + G*Q*G' of positive
+    semi-definite terms; the Stein equation by doubling.  A DARE the doubling iteration does not serve -- vary = 0 (kernel_ss_probFB
+    calls with it), or no convergence -- goes to SciPy's QZ solver, as in ihgp_tables; when that fails too the error of the .m is raised."""
     A = L.f64(A)
-    H = np.asarray(C_, float).reshape(1, -1); R = float(np.ravel(vary)[0])
+    H = np.asarray(C_, float).reshape(1, -1); R = float(np.ravel(vary)[0]); Q = np.asarray(Q, float)
     try:
-        PP = sla.solve_discrete_are(A.T, H.T, np.asarray(Q, float), np.array([[R]]))      # :46
+        PP = _dare_doubling(A, H, Q, R)                                                    # :46
+        if PP is None:
+            PP = sla.solve_discrete_are(A.T, H.T, Q, np.array([[R]]))
+        Sinn = float((H @ PP @ H.T)[0, 0]) + R
+        if not Sinn > 0:
+            raise ArithmeticError('innovation variance %g' % Sinn)
     except Exception as e:                                                                 # :51-53
         raise L.NagpError('Unstable DARE solution!') from e
-    Sinn = float((H @ PP @ H.T)[0, 0]) + R
     Kg = (PP @ H.T / Sinn).ravel()                                                         # :56
     HA = (H @ A).ravel()
     AKHA = L.f64(A - np.outer(Kg, HA))                                                     # :59
-    PF2 = PP - np.outer(Kg, (H @ PP).ravel())                                              # :73
+    PF2 = PP - np.outer(Kg, (H @ PP).ravel()); PF2 = (PF2 + PF2.T) / 2                     # :73
     G = None; Psm = None
     if KF != 1:
-        G = np.linalg.solve(PP.T, (PF2 @ A.T).T).T                                         # :127  PF2*A'/PP
-        QQ = PF2 - G @ PP @ G.T; QQ = (QQ + QQ.T) / 2                                      # :130-131
-        Psm = sla.solve_discrete_lyapunov(G, QQ)                                           # :132  dare(G',0,QQ)
+        PPc = A @ PF2 @ A.T + (Q + Q.T) / 2; PPc = (PPc + PPc.T) / 2
+        try:
+            G = sla.cho_solve(sla.cho_factor(PPc), A @ PF2).T                              # :127  PF2*A'/PP
+        except np.linalg.LinAlgError:                                                      # PP not numerically positive definite
+            G = sla.solve(PPc, A @ PF2, assume_a='sym').T
+        IGA = np.eye(A.shape[0]) - G @ A
+        QQ = IGA @ PF2 @ IGA.T + G @ Q @ G.T; QQ = (QQ + QQ.T) / 2                         # :130-131
+        Psm = _stein_doubling(G, QQ)                                                       # :132  dare(G',0,QQ)
         G = L.f64(G)
     return A, H, R, Sinn, Kg, HA, AKHA, PF2, G, Psm
 
