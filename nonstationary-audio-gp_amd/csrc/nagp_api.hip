@@ -35,6 +35,7 @@ NAGP_LIST_NMFT(extern template __global__)
 #include <string>
 #include <functional>
 #include <map>
+#include <memory>
 #include <thread>
 #include <vector>
 
@@ -78,13 +79,10 @@ struct DevSwitches {
   int chunks = 12;               // NAGP_CHUNKS (>= 1): smoother chunks per sweep
   int pipeline_slots = 0;        // NAGP_PIPELINE_SLOTS (>= 1; at most nc - 1 at the use)
   int mom_chunk = 0;             // NAGP_MOM_CHUNK (>= 64)
-  int fbs_budget_mb = 0;         // NAGP_FBS_BUDGET_MB (>= 1): device-memory budget of nagp_fastfb_sample in MiB instead of FBS_BUDGET_BYTES
-  int sfb_budget_mb = 0;         // NAGP_SFB_BUDGET_MB (>= 1): device-memory budget of nagp_slowfb_run in MiB instead of SFB_BUDGET_BYTES
-  int nmf_budget_mb = 0;         // NAGP_NMF_BUDGET_MB (>= 1): device-memory budget of nagp_nmf_fp in MiB instead of NMF_BUDGET_BYTES
-  int pstft_budget_mb = 0;       // NAGP_PSTFT_BUDGET_MB (>= 1): device-memory budget of nagp_pstft_obj in MiB instead of PSTFT_BUDGET_BYTES
-  int segp_budget_mb = 0;        // NAGP_SEGP_BUDGET_MB (>= 1): device-memory budget of nagp_segp_obj in MiB instead of SEGP_BUDGET_BYTES
-  int gppad_budget_mb = 0;       // NAGP_GPPAD_BUDGET_MB (>= 1): device-memory budget of a nagp_gppad handle's per-evaluation buffers in MiB instead of GPPAD_BUDGET_BYTES
-  int nmft_budget_mb = 0;        // NAGP_NMFT_BUDGET_MB (>= 1): device-memory budget of a nagp_nmf_temp handle's per-evaluation buffers in MiB instead of NMFT_BUDGET_BYTES
+  // NAGP_<FBS|SFB|NMF|PSTFT|SEGP|GPPAD|NMFT>_BUDGET_MB (>= 1): the device-memory budget in MiB, instead of the <...>_BUDGET_BYTES of its file, of nagp_fastfb_sample,
+  // nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj and of the per-evaluation buffers of a nagp_gppad / nagp_nmf_temp handle (budget_bytes, nagp_api_layout.hpp)
+  enum Budget { FBS, SFB, NMF, PSTFT, SEGP, GPPAD, NMFT, N_BUDGETS };
+  int budget_mb[N_BUDGETS] = {0, 0, 0, 0, 0, 0, 0};
   int kb_f = 0;                  // NAGP_KB_F (1 .. 16)
   int ih_kb = 0;                 // NAGP_IH_KB (4, 8 or 16; anything else: not set): depth of the I/O ring of ihgp_adf8_kernel, where it fits
   int filter_dbg = 0;            // NAGP_FILTER_DBG
@@ -123,13 +121,8 @@ static DevSwitches read_dev_switches() {
   if ((v = env("NAGP_CHUNKS"))) s.chunks = std::max(1, atoi(v));
   if ((v = env("NAGP_PIPELINE_SLOTS"))) s.pipeline_slots = std::max(1, atoi(v));
   if ((v = env("NAGP_MOM_CHUNK"))) s.mom_chunk = std::max(64, atoi(v));
-  if ((v = env("NAGP_FBS_BUDGET_MB"))) s.fbs_budget_mb = std::max(1, atoi(v));
-  if ((v = env("NAGP_SFB_BUDGET_MB"))) s.sfb_budget_mb = std::max(1, atoi(v));
-  if ((v = env("NAGP_NMF_BUDGET_MB"))) s.nmf_budget_mb = std::max(1, atoi(v));
-  if ((v = env("NAGP_PSTFT_BUDGET_MB"))) s.pstft_budget_mb = std::max(1, atoi(v));
-  if ((v = env("NAGP_SEGP_BUDGET_MB"))) s.segp_budget_mb = std::max(1, atoi(v));
-  if ((v = env("NAGP_GPPAD_BUDGET_MB"))) s.gppad_budget_mb = std::max(1, atoi(v));
-  if ((v = env("NAGP_NMFT_BUDGET_MB"))) s.nmft_budget_mb = std::max(1, atoi(v));
+  static const char* const budget_env[DevSwitches::N_BUDGETS] = {"NAGP_FBS_BUDGET_MB", "NAGP_SFB_BUDGET_MB", "NAGP_NMF_BUDGET_MB", "NAGP_PSTFT_BUDGET_MB", "NAGP_SEGP_BUDGET_MB", "NAGP_GPPAD_BUDGET_MB", "NAGP_NMFT_BUDGET_MB"};
+  for (int i = 0; i < DevSwitches::N_BUDGETS; ++i) if ((v = env(budget_env[i]))) s.budget_mb[i] = std::max(1, atoi(v));
   if ((v = env("NAGP_KB_F"))) s.kb_f = std::max(1, std::min(16, atoi(v)));
   if ((v = env("NAGP_IH_KB"))) { const int kb = atoi(v); s.ih_kb = (kb == 4 || kb == 8 || kb == 16) ? kb : 0; }
   if ((v = env("NAGP_FILTER_DBG"))) s.filter_dbg = atoi(v);
@@ -442,9 +435,15 @@ struct Timed {
   }
 };
 
-// ---- the rest of this translation unit, in four parts (one object file: the parts share the plan struct and the static helpers above)
+// ---- the rest of this translation unit, in parts (one object file: the parts share the plan struct and the static helpers above)
 #include "nagp_api_plan.hpp"
 #include "nagp_api_sweep.hpp"
+#include "nagp_api_batch.hpp"
 #include "nagp_api_entry.hpp"
+#include "nagp_api_fastfb.hpp"
+#include "nagp_api_slowfb.hpp"
+#include "nagp_api_nmf.hpp"
+#include "nagp_api_pstft.hpp"
+#include "nagp_api_segp.hpp"
 #include "nagp_api_gppad.hpp"
 #include "nagp_api_nmf_temp.hpp"

@@ -2,17 +2,14 @@
 // nagp_gppad.hpp): the resident handle, the one-shot call on top of it, the twiddle tables.
 constexpr size_t GPPAD_BUDGET_BYTES = (size_t)1 << 30;    // device memory of the per-evaluation buffers: the problems run in device batches under it
 static thread_local double g_gppad_ms = 0.0;
-#define GPPAD_HIP(fn, x) do { if (st == NAGP_OK) { hipError_t _e = (x); if (_e != hipSuccess) { g_last_error = std::string(#fn ": " #x " -> ") + hipGetErrorString(_e); (void)hipGetLastError(); st = NAGP_EHIP; } } } while (0)
 
 struct nagp_gppad {
   int device = 0, n = 0, nb = 0, N1 = 1, N2 = 1, lcb = 0, nwg = 1, nt = 64;
   int64_t T = 0, Tx = 0, vary_stride = 0, ic_stride = 0;
   size_t lds = 0;
-  double* res = nullptr;      // resident: y | vary | ic | varx | mux | varc
-  double* bat = nullptr;      // per device batch: x | dObj | work | part | Obj
-  size_t o_vy = 0, o_ic = 0, o_vx = 0, o_mu = 0, o_vc = 0, o_dg = 0, o_wk = 0, o_pt = 0, o_ob = 0;
+  DevBlock res, bat;          // resident / per device batch (with the two events), laid out by r / b
+  GppadRes r{}; GppadBat b{};
   const double2* tw = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
 };
 
 // exp(-2 pi i m / Tx), m < Tx, in long double through the octant of m (the argument of sinl / cosl stays inside [0, pi/4]); one table
@@ -50,20 +47,8 @@ static int gppad_twiddles(int device, int64_t Tx, const double2** out) {
   return NAGP_OK;
 }
 
-extern "C" int nagp_gppad_timings(double* ms) {
-  if (!ms) FAIL(NAGP_EINVAL, "null argument");
-  ms[0] = g_gppad_ms;
-  return NAGP_OK;
-}
-
-extern "C" void nagp_gppad_destroy(nagp_gppad* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  for (int i = 0; i < 2; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
-  if (h->res) (void)hipFree(h->res);
-  if (h->bat) (void)hipFree(h->bat);
-  delete h;
-}
+extern "C" int nagp_gppad_timings(double* ms) { return timings_out(ms, &g_gppad_ms, 1); }
+extern "C" void nagp_gppad_destroy(nagp_gppad* h) { delete h; }
 
 static GppadPar gppad_par(const nagp_gppad* h) {
   GppadPar pp{};
@@ -97,7 +82,7 @@ extern "C" int nagp_gppad_create(nagp_gppad** handle, int32_t n_problems, int64_
     for (size_t e = 0, m = cov_stride ? nz * Txz : Txz; e < m; ++e)
       if (!std::isfinite(fftCov[e]) || !(fftCov[e] > 0.0)) FAIL(NAGP_EINVAL, "fftCov[%zu] = %g: finite and > 0", e, fftCov[e]);
   const DevSwitches dev_sw = read_dev_switches();
-  nagp_gppad* h = new nagp_gppad();
+  std::unique_ptr<nagp_gppad> h(new nagp_gppad());      // released to the caller at the end; every return before that frees it
   h->device = device; h->n = n_problems; h->T = T; h->Tx = Tx; h->vary_stride = vary_stride;
   h->ic_stride = (fftCov && cov_stride == 0) ? 0 : Tx;
   if (Tx > GPPAD_TILE) { h->N2 = GPPAD_TILE; h->N1 = (int)(Tx / GPPAD_TILE); h->lcb = GPPAD_LOG_TILE - gp_log2(h->N1); h->nwg = h->N1; }
@@ -106,48 +91,45 @@ extern "C" int nagp_gppad_create(nagp_gppad** handle, int32_t n_problems, int64_
   // the budget rule of include/nagp.h
   const bool four = h->N1 > 1;
   const size_t per_problem = 8 * (2 * Txz + (four ? 2 * Txz : 0) + 2 * (size_t)h->nwg + 1);
-  const size_t budget = dev_sw.gppad_budget_mb ? (size_t)dev_sw.gppad_budget_mb << 20 : GPPAD_BUDGET_BYTES;
-  if (per_problem > budget) { delete h; FAIL(NAGP_EUNSUPPORTED, "one problem takes %zu B of device memory per evaluation (budget %zu B)", per_problem, budget); }
-  h->nb = (int)std::min<size_t>({nz, budget / per_problem, (size_t)32768});
-  if (hipSetDevice(device) != hipSuccess) { delete h; FAIL(NAGP_EHIP, "hipSetDevice(%d)", device); }
-  const size_t nbz = (size_t)h->nb, n_vy = vary_stride ? nz * Tz : nz, n_ic = h->ic_stride ? nz * Txz : Txz;
-  h->o_vy = nz * Tz; h->o_ic = h->o_vy + n_vy; h->o_vx = h->o_ic + n_ic; h->o_mu = h->o_vx + nz; h->o_vc = h->o_mu + nz;
-  const size_t res_total = h->o_vc + nz + 2;
-  h->o_dg = nbz * Txz; h->o_wk = h->o_dg + nbz * Txz; h->o_pt = h->o_wk + (four ? 2 * nbz * Txz : 0); h->o_ob = h->o_pt + 2 * nbz * h->nwg;
-  const size_t bat_total = h->o_ob + nbz + 2;
-  if (hipMalloc(&h->res, res_total * 8) != hipSuccess) { (void)hipGetLastError(); delete h; FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", res_total * 8); }
-  if (hipMalloc(&h->bat, bat_total * 8) != hipSuccess) { (void)hipGetLastError(); nagp_gppad_destroy(h); FAIL(NAGP_ENOMEM, "hipMalloc(%zu)", bat_total * 8); }
+  const size_t budget = budget_bytes(dev_sw.budget_mb[DevSwitches::GPPAD], GPPAD_BUDGET_BYTES);
+  const BatchPlan bp = batch_plan(nz, budget, 0, per_problem);
+  if (!bp.ok) FAIL(NAGP_EUNSUPPORTED, "one problem takes %zu B of device memory per evaluation (budget %zu B)", per_problem, budget);
+  h->nb = (int)bp.nb;
+  if (hipSetDevice(device) != hipSuccess) FAIL(NAGP_EHIP, "hipSetDevice(%d)", device);
+  const size_t n_vy = vary_stride ? nz * Tz : nz, n_ic = h->ic_stride ? nz * Txz : Txz;
+  h->r = gppad_res(nz, Tz, Txz, vary_stride != 0, h->ic_stride != 0);
+  h->b = gppad_bat(Txz, four, (size_t)h->nwg, bp.nb);
+  API_ALLOC(h->res, device, h->r.total);
+  API_ALLOC(h->bat, device, h->b.total);
+  double* const res = h->res.p; double* const bat = h->bat.p;
   int st = gppad_twiddles(device, Tx, &h->tw);
   if (st == NAGP_OK) st = set_lds(gppad_lds_kernel<0>, h->lds);
   if (st == NAGP_OK) st = set_lds(gppad_colf_kernel<0>, h->lds);
   if (st == NAGP_OK) st = set_lds(gppad_row_kernel<0>, h->lds);
   if (st == NAGP_OK) st = set_lds(gppad_coli_kernel<0>, h->lds);
-  for (int i = 0; i < 2; ++i) GPPAD_HIP(nagp_gppad_create, hipEventCreate(&h->ev[i]));
-  GPPAD_HIP(nagp_gppad_create, hipMemcpy(h->res, y, nz * Tz * 8, hipMemcpyHostToDevice));
-  GPPAD_HIP(nagp_gppad_create, hipMemcpy(h->res + h->o_vy, vary, n_vy * 8, hipMemcpyHostToDevice));
-  GPPAD_HIP(nagp_gppad_create, hipMemcpy(h->res + h->o_vx, varx, nz * 8, hipMemcpyHostToDevice));
-  GPPAD_HIP(nagp_gppad_create, hipMemcpy(h->res + h->o_mu, mux, nz * 8, hipMemcpyHostToDevice));
-  GPPAD_HIP(nagp_gppad_create, hipMemcpy(h->res + h->o_vc, varc, nz * 8, hipMemcpyHostToDevice));
+  API_HIP(nagp_gppad_create, h->bat.events(2));
+  API_HIP(nagp_gppad_create, hipMemcpy(res + h->r.y, y, nz * Tz * 8, hipMemcpyHostToDevice));
+  API_HIP(nagp_gppad_create, hipMemcpy(res + h->r.vy, vary, n_vy * 8, hipMemcpyHostToDevice));
+  API_HIP(nagp_gppad_create, hipMemcpy(res + h->r.vx, varx, nz * 8, hipMemcpyHostToDevice));
+  API_HIP(nagp_gppad_create, hipMemcpy(res + h->r.mu, mux, nz * 8, hipMemcpyHostToDevice));
+  API_HIP(nagp_gppad_create, hipMemcpy(res + h->r.vc, varc, nz * 8, hipMemcpyHostToDevice));
   if (fftCov) {                                            // 1 / (c Tx) in the order the forward transform leaves
     std::vector<double> ic(n_ic);
     const double invT = 1.0 / (double)Tx;
     for (size_t q = 0, nq = cov_stride ? nz : 1; q < nq; ++q)
       for (size_t e = 0; e < Txz; ++e) ic[q * Txz + e] = (1.0 / fftCov[q * Txz + (size_t)gppad_freq_at((int64_t)e, h->N1, h->N2)]) * invT;
-    GPPAD_HIP(nagp_gppad_create, hipMemcpy(h->res + h->o_ic, ic.data(), n_ic * 8, hipMemcpyHostToDevice));
+    API_HIP(nagp_gppad_create, hipMemcpy(res + h->r.ic, ic.data(), n_ic * 8, hipMemcpyHostToDevice));
   } else {                                                 // GetFFTCovFast.m:10-16 on the device (len goes through the head of the batch block)
-    for (int i0 = 0; i0 < n_problems && st == NAGP_OK; i0 += h->nb) {
-      const int nbk = std::min(h->nb, n_problems - i0);
-      GPPAD_HIP(nagp_gppad_create, hipMemcpy(h->bat, len + i0, (size_t)nbk * 8, hipMemcpyHostToDevice));
-      GppadPar pp = gppad_par(h);
-      pp.len = h->bat; pp.ic_out = h->res + h->o_ic + (size_t)i0 * Txz;
-      if (st == NAGP_OK) hipLaunchKernelGGL(gppad_cov_kernel<0>, dim3((unsigned)((Tx + 255) / 256), (unsigned)nbk), dim3(256), 0, 0, pp);
-      GPPAD_HIP(nagp_gppad_create, hipGetLastError());
-      GPPAD_HIP(nagp_gppad_create, hipDeviceSynchronize());
-    }
+    run_batches("nagp_gppad_create", st, n_problems, h->nb, nullptr, 0, nullptr,
+      [&](int i0, int nbk) { API_HIP(nagp_gppad_create, hipMemcpy(bat, len + i0, (size_t)nbk * 8, hipMemcpyHostToDevice)); },
+      [&](int i0, int nbk, int) {
+        GppadPar pp = gppad_par(h.get());
+        pp.len = bat; pp.ic_out = res + h->r.ic + (size_t)i0 * Txz;
+        hipLaunchKernelGGL(gppad_cov_kernel<0>, dim3((unsigned)((Tx + 255) / 256), (unsigned)nbk), dim3(256), 0, 0, pp);
+      }, [](int, int) {});
   }
-  if (st != NAGP_OK) { nagp_gppad_destroy(h); return st; }
-  *handle = h;
-  return NAGP_OK;
+  if (st == NAGP_OK) *handle = h.release();
+  return st;
 }
 
 extern "C" int nagp_gppad_eval(nagp_gppad* h, const double* x, double* Obj, double* dObj) {
@@ -155,18 +137,18 @@ extern "C" int nagp_gppad_eval(nagp_gppad* h, const double* x, double* Obj, doub
   if (!h || !x || !Obj) FAIL(NAGP_EINVAL, "null argument");
   if (hipSetDevice(h->device) != hipSuccess) FAIL(NAGP_EHIP, "hipSetDevice(%d)", h->device);
   const size_t Txz = (size_t)h->Tx, Tz = (size_t)h->T;
+  double* const res = h->res.p; double* const bat = h->bat.p;
+  const GppadRes& r = h->r; const GppadBat& b = h->b;
   int st = NAGP_OK;
-  for (int i0 = 0; i0 < h->n && st == NAGP_OK; i0 += h->nb) {
-    const int nbk = std::min(h->nb, h->n - i0);
-    GPPAD_HIP(nagp_gppad_eval, hipMemcpy(h->bat, x + (size_t)i0 * Txz, (size_t)nbk * Txz * 8, hipMemcpyHostToDevice));
-    GppadPar pp = gppad_par(h);
-    pp.grad = dObj ? 1 : 0;
-    pp.x = h->bat; pp.dObj = h->bat + h->o_dg; pp.work = reinterpret_cast<double2*>(h->bat + h->o_wk); pp.part = h->bat + h->o_pt; pp.Obj = h->bat + h->o_ob;
-    pp.y = h->res + (size_t)i0 * Tz; pp.vary = h->res + h->o_vy + (h->vary_stride ? (size_t)i0 * Tz : (size_t)i0);
-    pp.ic = h->res + h->o_ic + (h->ic_stride ? (size_t)i0 * Txz : 0);
-    pp.varx = h->res + h->o_vx + i0; pp.mux = h->res + h->o_mu + i0; pp.varc = h->res + h->o_vc + i0;
-    if (st == NAGP_OK) {
-      (void)hipEventRecord(h->ev[0], 0);
+  run_batches("nagp_gppad_eval", st, h->n, h->nb, h->bat.ev, 2, &g_gppad_ms,
+    [&](int i0, int nbk) { API_HIP(nagp_gppad_eval, hipMemcpy(bat + b.x, x + (size_t)i0 * Txz, (size_t)nbk * Txz * 8, hipMemcpyHostToDevice)); },
+    [&](int i0, int nbk, int) {
+      GppadPar pp = gppad_par(h);
+      pp.grad = dObj ? 1 : 0;
+      pp.x = bat + b.x; pp.dObj = bat + b.dg; pp.work = reinterpret_cast<double2*>(bat + b.wk); pp.part = bat + b.pt; pp.Obj = bat + b.ob;
+      pp.y = res + r.y + (size_t)i0 * Tz; pp.vary = res + r.vy + (h->vary_stride ? (size_t)i0 * Tz : (size_t)i0);
+      pp.ic = res + r.ic + (h->ic_stride ? (size_t)i0 * Txz : 0);
+      pp.varx = res + r.vx + i0; pp.mux = res + r.mu + i0; pp.varc = res + r.vc + i0;
       if (h->N1 == 1) hipLaunchKernelGGL(gppad_lds_kernel<0>, dim3((unsigned)nbk), dim3(h->nt), h->lds, 0, pp);
       else {
         const dim3 grid((unsigned)h->N1, (unsigned)nbk);
@@ -175,14 +157,10 @@ extern "C" int nagp_gppad_eval(nagp_gppad* h, const double* x, double* Obj, doub
         hipLaunchKernelGGL(gppad_coli_kernel<0>, grid, dim3(h->nt), h->lds, 0, pp);
       }
       hipLaunchKernelGGL(gppad_finish_kernel<0>, dim3((unsigned)((nbk + 63) / 64)), dim3(64), 0, 0, pp, nbk);
-      (void)hipEventRecord(h->ev[1], 0);
-    }
-    GPPAD_HIP(nagp_gppad_eval, hipGetLastError());
-    GPPAD_HIP(nagp_gppad_eval, hipDeviceSynchronize());
-    if (st == NAGP_OK) { float ms = 0.f; if (hipEventElapsedTime(&ms, h->ev[0], h->ev[1]) == hipSuccess) g_gppad_ms += ms; }
-    GPPAD_HIP(nagp_gppad_eval, hipMemcpy(Obj + i0, h->bat + h->o_ob, (size_t)nbk * 8, hipMemcpyDeviceToHost));
-    if (dObj) GPPAD_HIP(nagp_gppad_eval, hipMemcpy(dObj + (size_t)i0 * Txz, h->bat + h->o_dg, (size_t)nbk * Txz * 8, hipMemcpyDeviceToHost));
-  }
+    }, [&](int i0, int nbk) {
+      API_HIP(nagp_gppad_eval, hipMemcpy(Obj + i0, bat + b.ob, (size_t)nbk * 8, hipMemcpyDeviceToHost));
+      if (dObj) API_HIP(nagp_gppad_eval, hipMemcpy(dObj + (size_t)i0 * Txz, bat + b.dg, (size_t)nbk * Txz * 8, hipMemcpyDeviceToHost));
+    });
   return st;
 }
 
@@ -192,10 +170,7 @@ extern "C" int nagp_gppad_obj(int32_t n_problems, int64_t T, int64_t Tx, const d
   g_gppad_ms = 0.0;
   if (!x || !Obj) FAIL(NAGP_EINVAL, "null argument");
   nagp_gppad* h = nullptr;
-  int st = nagp_gppad_create(&h, n_problems, T, Tx, y, vary, vary_stride, len, fftCov, cov_stride, varx, mux, varc, device);
-  if (st != NAGP_OK) return st;
-  st = nagp_gppad_eval(h, x, Obj, dObj);
-  nagp_gppad_destroy(h);
-  return st;
+  const int st = nagp_gppad_create(&h, n_problems, T, Tx, y, vary, vary_stride, len, fftCov, cov_stride, varx, mux, varc, device);
+  const std::unique_ptr<nagp_gppad> owner(h);
+  return st != NAGP_OK ? st : nagp_gppad_eval(h, x, Obj, dObj);
 }
-#undef GPPAD_HIP

@@ -1,0 +1,79 @@
+// nagp_api_layout.hpp -- part of the host translation unit nagp_api.hip: the arithmetic of the batched entry points ("Batched
+// entry points") -- the budget, the size of a device batch and the offsets inside "one device block of doubles" of every entry point.
+// Plain C++ without the HIP runtime, so that tests/c/batch_layout_check.cpp can run all of it under the host sanitizers.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+
+namespace nagp {
+constexpr size_t BATCH_MAX = 32768;      // items of one device batch at the most (the y extent of a grid stays far below 65535)
+// the device-memory budget of one call: the developer switch in MiB when it is set, the entry point's constant otherwise
+inline size_t budget_bytes(int switch_mb, size_t default_bytes) { return switch_mb ? (size_t)switch_mb << 20 : default_bytes; }
+
+// n items in device batches of nb under `budget` bytes: `fixed` bytes once, `per_item` bytes for every item of a batch.  !ok: one item
+// does not fit (the caller refuses with its own status and text)
+struct BatchPlan { bool ok; size_t nb; };
+inline BatchPlan batch_plan(size_t n, size_t budget, size_t fixed, size_t per_item) {
+  return fixed + per_item > budget ? BatchPlan{false, 0} : BatchPlan{true, std::min({n, (budget - fixed) / per_item, BATCH_MAX})};
+}
+
+// one device block of doubles, stated as a sequence of parts: take(n) gives the offset of the next n doubles, total(pad) closes the block
+struct Layout {
+  size_t at = 0;
+  size_t take(size_t n_doubles) { const size_t o = at; at += n_doubles; return o; }
+  size_t total(size_t pad) const { return at + pad; }
+};
+
+// ---- the blocks of the entry points, nb items per device batch (a braced list is evaluated left to right: the parts lie in the order written)
+// nagp_fastfb_sample: A | AKHA | G | Lq | Lp | K | H | HA | y | span matrices: filter, A^L, G^L, G^last (+ 8) | per batch: x* | ms | d | yd | c | starts
+struct FbsBlock { size_t A, B, G, lq, lp, k, h, ha, y, phf, pha, phg, phl, xs, ms, d, yd, c, st, total; };
+inline FbsBlock fbs_block(size_t S, size_t T, size_t ns, size_t nb) {
+  const size_t SS = S * S, SSP = S * (S + 4), TS = T * S;
+  Layout l; return {l.take(SS), l.take(SS), l.take(SS), l.take(SS), l.take(SS), l.take(S), l.take(S), l.take(S), l.take(T), l.take(ns * SSP), l.take(SSP), l.take(SSP),
+          l.take(SSP + 8), l.take(nb * TS), l.take(nb * TS), l.take(nb * T), l.take(nb * T), l.take(nb * ns * S), l.take(nb * ns * S), l.total(0)};
+}
+// nagp_slowfb_run: Ab | Qb | P0 | H | sub (int) | per batch: y | vary | lik | flag (int) | pm | pP | v | 1/s | K | r | N | MS | Pdiag | Psub
+// (v .. N only for the smoother, Pdiag when asked for; n ints lie in n / 2 + 1 doubles)
+struct SfbBlock { size_t ab, qb, p0, h, sub, y, vr, lik, fl, pm, pP, v, si, K, r, N, ms, pd, ps, total; };
+inline SfbBlock sfb_block(size_t S, size_t block, size_t T, size_t n_sub, bool filter_only, bool pdiag, size_t nb) {
+  const size_t SS = S * S, TS = T * S, TSS = T * SS, sm = filter_only ? 0 : nb;
+  Layout l; return {l.take(S * block), l.take(S * block), l.take(SS), l.take(S), l.take(n_sub / 2 + 1), l.take(nb * T), l.take(nb * T), l.take(nb), l.take(nb / 2 + 1),
+          l.take(nb * TS), l.take(nb * TSS), l.take(sm * T), l.take(sm * T), l.take(sm * TS), l.take(sm * TS), l.take(sm * TSS), l.take(nb * TS),
+          l.take(pdiag ? nb * TS : 0), l.take(nb * n_sub * n_sub * T), l.total(2)};
+}
+// nagp_nmf_fp: A | vary | per batch: W | H | pw | po | Obj
+struct NmfBlock { size_t a, v, w, h, pw, po, ob, total; };
+inline NmfBlock nmf_block(size_t T, size_t D, size_t K, size_t nwg, size_t n_obj, bool vary, size_t nb) {
+  Layout l; return {l.take(T * D), l.take(vary ? T * D : 0), l.take(nb * K * D), l.take(nb * T * K), l.take(nb * nwg * 2 * K * D), l.take(nb * nwg * 2), l.take(nb * n_obj), l.total(2)};
+}
+// nagp_pstft_obj: minVar | limOm | limLam | specTar (shared) | per batch: theta | vary | bet | specTar | part | Obj | dObj
+struct PstftBlock { size_t mv, lo, ll, ss, th, vy, bt, sp, pt, ob, dg, total; };
+inline PstftBlock pstft_block(size_t D, size_t N, bool per_problem_spec, size_t nwg, size_t n_out, size_t nb) {
+  Layout l; return {l.take(D), l.take(2 * D), l.take(2 * D), l.take(per_problem_spec ? 0 : N), l.take(nb * 3 * D), l.take(nb), l.take(nb), l.take(per_problem_spec ? nb * N : 0),
+          l.take(nb * nwg * n_out), l.take(nb), l.take(nb * 3 * D), l.total(2)};
+}
+// nagp_segp_obj: specy (shared) | per batch: param | vary | varx | specy | part | Obj | dObj
+struct SegpBlock { size_t ss, pa, vy, vx, sp, pt, ob, dg, total; };
+inline SegpBlock segp_block(size_t n_param, size_t T, bool per_problem_spec, size_t nwg, size_t n_out, size_t nb) {
+  Layout l; return {l.take(per_problem_spec ? 0 : T), l.take(nb * n_param), l.take(nb), l.take(nb), l.take(per_problem_spec ? nb * T : 0), l.take(nb * nwg * n_out), l.take(nb),
+          l.take(nb * n_param), l.total(2)};
+}
+// nagp_gppad handle, resident: y | vary | ic | varx | mux | varc;  per device batch: x | dObj | work (four-step form) | part | Obj
+struct GppadRes { size_t y, vy, ic, vx, mu, vc, total; };
+inline GppadRes gppad_res(size_t n, size_t T, size_t Tx, bool vary_per_sample, bool ic_per_problem) {
+  Layout l; return {l.take(n * T), l.take(vary_per_sample ? n * T : n), l.take(ic_per_problem ? n * Tx : Tx), l.take(n), l.take(n), l.take(n), l.total(2)};
+}
+struct GppadBat { size_t x, dg, wk, pt, ob, total; };
+inline GppadBat gppad_bat(size_t Tx, bool four_step, size_t nwg, size_t nb) {
+  Layout l; return {l.take(nb * Tx), l.take(nb * Tx), l.take(four_step ? 2 * nb * Tx : 0), l.take(2 * nb * nwg), l.take(nb), l.total(2)};
+}
+// nagp_nmf_temp handle, resident: A | vary | W (inference form) | muinf, varinf, lam;  per device batch: x | dObj | pw (learning form) | po | Obj
+struct NmftRes { size_t a, vy, w, pr, total; };
+inline NmftRes nmft_res(size_t n, size_t T, size_t D, size_t K, bool vary, bool given_W) {
+  Layout l; return {l.take(T * D), l.take(vary ? T * D : 0), l.take(given_W ? n * K * D : 0), l.take(3 * K), l.total(2)};
+}
+struct NmftBat { size_t x, dg, pw, po, ob, total; };
+inline NmftBat nmft_bat(size_t nx, size_t D, size_t K, bool learn, size_t nwg, size_t n_po, size_t nb) {
+  Layout l; return {l.take(nb * nx), l.take(nb * nx), l.take(learn ? nb * nwg * K * D : 0), l.take(nb * nwg * n_po), l.take(nb), l.total(2)};
+}
+}  // namespace nagp

@@ -12,7 +12,7 @@ GPPAD(Y, Params), both through FBGPMAP:
 The objective and its gradient -- an FFT, a division by the prior spectrum, an inverse FFT and the likelihood pass, Tx = 131072 for
 speech_74 -- run on the GPU (nagp_gppad_obj and the resident nagp_gppad_create / _eval / _destroy, include/nagp.h).  The marginal
 parameters (500 samples x 250 grid points), the first-level initialisation, resample(x, 2, 1) between the levels and the
-conjugate-gradient line search (pstft.minimize_steps) stay on the host.  There is no CPU fallback: the `evaluator` argument exists so
+conjugate-gradient line search (minimize.minimize_steps) stay on the host.  There is no CPU fallback: the `evaluator` argument exists so
 that the tests can put the float64 restatement through the same driver.
 
 Not built, and refused with the name of the reference file that would serve them: length-scale learning (LrnLen = 1, 2:
@@ -24,7 +24,8 @@ import math
 import numpy as np
 
 from . import _lib as L
-from .pstft import minimize, minimize_steps
+from ._drive import ResidentHandle, close, forward, lock_step_rows, run
+from .minimize import minimize, minimize_steps
 
 
 # ---------------------------------------------------------------------------------------------------------------- small helpers
@@ -96,73 +97,12 @@ def _per_problem(v, P, name):
     return L.f64(a, 'C')
 
 
-class GppadHandle:
-    """The resident form (nagp_gppad_create): y (P, T), vary (P,) or (P, T), 1 / c, the parameters and the twiddles stay on the
-    device; eval(x) moves x (P, Tx) in and Obj (P,), dObj (P, Tx) out.  The prior spectrum is fftCov ((Tx,) shared or (P, Tx)) or
-    is formed on the device from len."""
-
-    def __init__(self, y, Tx, vary, varx, mux, varc, len=None, fftCov=None, device=0):
-        import ctypes as C
-        y = L.f64(np.atleast_2d(np.asarray(y, float)), 'C')
-        self.P, self.T = y.shape; self.Tx = int(Tx)
-        P = self.P
-        vy = np.asarray(vary, float)
-        if vy.ndim == 0:
-            vy = np.full(P, float(vy))
-        if vy.shape not in ((P,), (P, self.T)):
-            raise ValueError('vary must be a scalar, (P,) or (P, T): got %s' % (vy.shape,))
-        vy = L.f64(vy, 'C')
-        if (len is None) == (fftCov is None):
-            raise ValueError('exactly one of len and fftCov is given')
-        ln = _per_problem(len, P, 'len') if len is not None else None
-        cov = None
-        if fftCov is not None:
-            cov = L.f64(np.asarray(fftCov, float), 'C')
-            if cov.shape not in ((self.Tx,), (P, self.Tx)):
-                raise ValueError('fftCov must be (Tx,) or (P, Tx): got %s' % (cov.shape,))
-        self._h = C.c_void_p()
-        L.check(L.lib().nagp_gppad_create(C.byref(self._h), P, self.T, self.Tx, L.dptr(y), L.dptr(vy), self.T if vy.ndim == 2 else 0,
-                                          L.dptr(ln), L.dptr(cov), (self.Tx if cov.ndim == 2 else 0) if cov is not None else 0,
-                                          L.dptr(_per_problem(varx, P, 'varx')), L.dptr(_per_problem(mux, P, 'mux')),
-                                          L.dptr(_per_problem(varc, P, 'varc')), int(device)))
-
-    def eval(self, x, grad=True):
-        x = L.f64(np.asarray(x, float).reshape(self.P, self.Tx), 'C')
-        Obj = np.zeros(self.P); dObj = np.zeros((self.P, self.Tx)) if grad else None
-        if not self._h:
-            raise L.NagpError('the handle is closed')
-        L.check(L.lib().nagp_gppad_eval(self._h, L.dptr(x), L.dptr(Obj), L.dptr(dObj)))
-        return (Obj, dObj) if grad else Obj
-
-    def close(self):
-        if self._h:
-            L.lib().nagp_gppad_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def gppad_obj(x, y, vary, varx, mux, varc, len=None, fftCov=None, grad=True, device=0):
-    """nagp_gppad_obj with NumPy arrays.  x (Tx,) or (P, Tx); y (T,) or (P, T); vary a scalar, (P,) or (P, T) (for one problem also
-    (T,)); varx, mux, varc scalars or (P,); the prior spectrum as fftCov ((Tx,) shared or (P, Tx)) or formed on the device from len
-    (a scalar or (P,)).  Returns Obj and, with grad, dObj, with the leading problem axis of x."""
-    x = np.asarray(x, float); single = x.ndim <= 1
-    xx = L.f64(np.atleast_2d(x), 'C'); yy = L.f64(np.atleast_2d(np.asarray(y, float)), 'C')
-    if xx.ndim != 2 or yy.ndim != 2 or yy.shape[0] != xx.shape[0]:
-        raise ValueError('x must be (Tx,) or (P, Tx) and y (T,) or (P, T): got %s, %s' % (x.shape, np.shape(y)))
-    P, Tx = xx.shape; T = yy.shape[1]
+def _shaped(y, Tx, vary, varx, mux, varc, len, fftCov, one=False):
+    """the data arguments of nagp_gppad_create / nagp_gppad_obj from NumPy arrays, in the order of the C signatures: y (P, T), vary,
+    vary_stride, len, fftCov, cov_stride, varx, mux, varc.  one: a (T,) vary is the per-sample vary of the one problem."""
+    P, T = y.shape
     vy = np.asarray(vary, float)
-    if single and vy.ndim == 1 and vy.shape == (T,) and T != 1:
+    if one and vy.shape == (T,) and T != 1:
         vy = vy[None, :]
     if vy.ndim == 0:
         vy = np.full(P, float(vy))
@@ -177,10 +117,36 @@ def gppad_obj(x, y, vary, varx, mux, varc, len=None, fftCov=None, grad=True, dev
         cov = L.f64(np.asarray(fftCov, float), 'C')
         if cov.shape not in ((Tx,), (P, Tx)):
             raise ValueError('fftCov must be (Tx,) or (P, Tx): got %s' % (cov.shape,))
+    return [L.dptr(y), L.dptr(vy), T if vy.ndim == 2 else 0, L.dptr(ln), L.dptr(cov), Tx if cov is not None and cov.ndim == 2 else 0,
+            L.dptr(_per_problem(varx, P, 'varx')), L.dptr(_per_problem(mux, P, 'mux')), L.dptr(_per_problem(varc, P, 'varc'))]
+
+
+class GppadHandle(ResidentHandle):
+    """The resident form (nagp_gppad_create): y (P, T), vary (P,) or (P, T), 1 / c, the parameters and the twiddles stay on the
+    device; eval(x) moves x (P, Tx) in and Obj (P,), dObj (P, Tx) out.  The prior spectrum is fftCov ((Tx,) shared or (P, Tx)) or
+    is formed on the device from len."""
+    _eval, _destroy = 'nagp_gppad_eval', 'nagp_gppad_destroy'
+
+    def __init__(self, y, Tx, vary, varx, mux, varc, len=None, fftCov=None, device=0):
+        import ctypes as C
+        y = L.f64(np.atleast_2d(np.asarray(y, float)), 'C')
+        self.P, self.T = y.shape; self.Tx = self.nx = int(Tx)
+        h = C.c_void_p()
+        L.check(L.lib().nagp_gppad_create(C.byref(h), self.P, self.T, self.Tx, *_shaped(y, self.Tx, vary, varx, mux, varc, len, fftCov), int(device)))
+        self._h = h
+
+
+def gppad_obj(x, y, vary, varx, mux, varc, len=None, fftCov=None, grad=True, device=0):
+    """nagp_gppad_obj with NumPy arrays.  x (Tx,) or (P, Tx); y (T,) or (P, T); vary a scalar, (P,) or (P, T) (for one problem also
+    (T,)); varx, mux, varc scalars or (P,); the prior spectrum as fftCov ((Tx,) shared or (P, Tx)) or formed on the device from len
+    (a scalar or (P,)).  Returns Obj and, with grad, dObj, with the leading problem axis of x."""
+    x = np.asarray(x, float); single = x.ndim <= 1
+    xx = L.f64(np.atleast_2d(x), 'C'); yy = L.f64(np.atleast_2d(np.asarray(y, float)), 'C')
+    if xx.ndim != 2 or yy.ndim != 2 or yy.shape[0] != xx.shape[0]:
+        raise ValueError('x must be (Tx,) or (P, Tx) and y (T,) or (P, T): got %s, %s' % (x.shape, np.shape(y)))
+    P, Tx = xx.shape; T = yy.shape[1]
     Obj = np.zeros(P); dObj = np.zeros((P, Tx)) if grad else None
-    L.check(L.lib().nagp_gppad_obj(P, T, Tx, L.dptr(xx), L.dptr(yy), L.dptr(vy), T if vy.ndim == 2 else 0, L.dptr(ln), L.dptr(cov),
-                                   (Tx if cov.ndim == 2 else 0) if cov is not None else 0, L.dptr(_per_problem(varx, P, 'varx')),
-                                   L.dptr(_per_problem(mux, P, 'mux')), L.dptr(_per_problem(varc, P, 'varc')), L.dptr(Obj), L.dptr(dObj),
+    L.check(L.lib().nagp_gppad_obj(P, T, Tx, L.dptr(xx), *_shaped(yy, Tx, vary, varx, mux, varc, len, fftCov, one=single), L.dptr(Obj), L.dptr(dObj),
                                    int(device)))
     if single:
         return (Obj[0], dObj[0]) if grad else Obj[0]
@@ -350,15 +316,6 @@ def _device_evaluator(device):
     return open_level
 
 
-def _run_level(f, steps):
-    try:
-        x = next(steps)
-        while True:
-            x = steps.send(f(x))
-    except StopIteration as e:
-        return e.value
-
-
 def MAPGPFast(x, y, Params, Dims, NumIts, evaluator=None, device=0):
     """[x,Obj] = MAPGPFast(x,y,Params,Dims,NumIts) (MAPGPFast.m): NumIts line searches of minimize on GetGPObjFast with the spectrum
     GetFFTCovFast(Params.len, Dims.Tx), formed on the device.  evaluator(y, Params, Dims) returns the objective f(x) -> (Obj, dObj)
@@ -366,10 +323,9 @@ def MAPGPFast(x, y, Params, Dims, NumIts, evaluator=None, device=0):
     y = np.asarray(y, float).reshape(-1)
     f = (evaluator or _device_evaluator(device))(y, Params, Dims)
     try:
-        x, Obj, _ = _run_level(f, minimize_steps(np.asarray(x, float).reshape(-1), int(NumIts)))
+        x, Obj, _ = run(minimize_steps(np.asarray(x, float).reshape(-1), int(NumIts)), f)
     finally:
-        if hasattr(f, 'close'):
-            f.close()
+        close(f)
     return x, Obj
 
 
@@ -406,13 +362,7 @@ def infer_steps(y, Params, Opts):
             xDS, _, _ = InitPADSampleNonStat(yDS, ParamsCur, WinSz)
             xDS = np.concatenate([xDS, mux * np.ones(TxCur - TCur)])
         yield ('level', yDS, ParamsCur, PackDimsGPFast(TCur, TxCur))
-        steps = minimize_steps(xDS, int(NumIts[n]))
-        try:
-            x = next(steps)
-            while True:
-                x = steps.send((yield ('x', x)))
-        except StopIteration as e:
-            xDS, Obj, _ = e.value
+        xDS, Obj, _ = yield from forward(minimize_steps(xDS, int(NumIts[n])), lambda x: ('x', x))
         if n < NumDSs - 1:
             xDS = resample2(xDS)                                                                 # :128-130
         Info['Obj'].append(Obj / Tx)                                                             # :133
@@ -432,23 +382,17 @@ def InferAmplitudeGPMAP(y, Params, Opts=None, evaluator=None, device=0):
     evaluator(y, Params, Dims) -> f(x) -> (Obj, dObj): the objective of one resolution, by default a resident nagp_gppad handle on
     `device` (f.close(), when there, is called at the end of the resolution)."""
     ev = evaluator or _device_evaluator(device)
-    g = infer_steps(y, Params, Opts)
-    f = None
+    level = [None]                                           # the objective of the resolution the generator stands at
+
+    def answer(req):
+        if req[0] == 'x':
+            return level[0](req[1])
+        close(level[0])
+        level[0] = ev(req[1], req[2], req[3])
     try:
-        req = next(g)
-        while True:
-            if req[0] == 'level':
-                if f is not None and hasattr(f, 'close'):
-                    f.close()
-                f = ev(req[1], req[2], req[3])
-                req = g.send(None)
-            else:
-                req = g.send(f(req[1]))
-    except StopIteration as e:
-        return e.value
+        return run(infer_steps(y, Params, Opts), answer)
     finally:
-        if f is not None and hasattr(f, 'close'):
-            f.close()
+        close(level[0])
 
 
 def InferAmplitudeGPMAP_many(ys, Params, Opts=None, device=0):
@@ -478,26 +422,15 @@ def InferAmplitudeGPMAP_many(ys, Params, Opts=None, device=0):
             h = GppadHandle(np.stack([pending[k][1] for k in ks]), Tx, vary, np.array([float(pending[k][2]['varx']) for k in ks]),
                             np.array([float(pending[k][2]['mux']) for k in ks]), np.array([float(pending[k][2]['varc']) for k in ks]),
                             len=np.array([float(pending[k][2]['len']) for k in ks]), device=device)
-            try:
-                X = np.zeros((len(ks), Tx)); live = {}
-                for j, k in enumerate(ks):
-                    live[j] = gens[k].send(None)             # the first ('x', x) of the resolution
-                    X[j] = live[j][1]
-                while live:
-                    Obj, dObj = h.eval(X)
-                    for j in list(live):
-                        k = ks[j]
-                        try:
-                            r = gens[k].send((Obj[j], dObj[j]))
-                        except StopIteration as e:
-                            out[k] = e.value; del live[j]
-                            continue
-                        if r[0] == 'level':
-                            nxt[k] = r; del live[j]
-                        else:
-                            live[j] = r; X[j] = r[1]
+            try:                                             # a channel leaves with the ('level', ...) of its next resolution
+                done, left = lock_step_rows(h.eval, [gens[k] for k in ks], Tx, lambda r: r[1] if r[0] == 'x' else None)
             finally:
                 h.close()
+            for j, k in enumerate(ks):
+                if j in left:
+                    nxt[k] = left[j]
+                else:
+                    out[k] = done[j]
         pending = nxt
     return out
 

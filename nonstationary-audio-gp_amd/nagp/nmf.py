@@ -13,6 +13,7 @@ kernel_ss_kalmanFastFB / kernel_ss_kalmanSlowFB return.  There is no CPU fallbac
 import numpy as np
 
 from . import _lib as L
+from ._drive import opt as _opt
 from .fastfb import kernel_ss_kalmanFastFB
 from .slowfb import kernel_ss_kalmanSlowFB
 
@@ -46,10 +47,6 @@ def _row_normalise(W):
     """diag(1 ./ sum(W,2)) * W"""
     W = np.asarray(W, float)
     return (1.0 / W.sum(axis=-1))[..., None] * W
-
-
-def _opt(opts, name, default):
-    return default if not opts or name not in opts else opts[name]
 
 
 def inf_normalise(W):

@@ -7,7 +7,7 @@ drivers keep next to their nmf_fp call (train_model.m:123) and the only form of 
     [W,H,info] = nmf(A,W,H,muinf,varinf,lam,vary,Opts)                         experiments/nmf/nmf.m
 
 The objective and its gradient run on the GPU (nagp_nmf_temp_obj and the resident nagp_nmf_temp_create / _eval / _destroy,
-include/nagp.h); the Polak-Ribiere line search (pstft.minimize_steps) stays on the host.  The restarts of a driver run as one lock-step
+include/nagp.h); the Polak-Ribiere line search (minimize.minimize_steps) stays on the host.  The restarts of a driver run as one lock-step
 batch on one resident handle, a generator per restart.  There is no CPU fallback: the `evaluator` argument exists so that the tests can
 put the float64 restatement through the same drivers.
 
@@ -22,7 +22,8 @@ import math
 import numpy as np
 
 from . import _lib as L
-from .pstft import minimize_steps
+from ._drive import ResidentHandle, close, lock_step_rows, opt as _opt
+from .minimize import minimize_steps
 
 PRIORS = {'none': L.NMFT_NONE, 'tg': L.NMFT_TG, 'ig': L.NMFT_IG}
 
@@ -86,61 +87,45 @@ def _weights(W, P, D):
     return L.f64(np.ascontiguousarray(np.transpose(W, (0, 2, 1))), 'C'), W.shape[1]
 
 
-class NmfTempHandle:
+def _shaped(A, vary, W, P, prior, muinf, varinf, lam, pick_K):
+    """the arguments of nagp_nmf_temp_create / nagp_nmf_temp_obj from NumPy arrays: (T, D, K, [A, vary, W, muinf, varinf, lam]).
+    pick_K(T, D, k) settles K, k being the rows of a given W (None in the learning form)."""
+    if prior not in PRIORS:
+        raise ValueError('prior is one of %s: got %r' % (sorted(PRIORS), prior))
+    A, vary = _data(A, vary)
+    T, D = A.shape
+    w, k = _weights(W, P, D) if W is not None else (None, None)
+    K = int(pick_K(T, D, k))
+    need = {'none': (), 'tg': ('varinf', 'lam'), 'ig': ('muinf', 'varinf', 'lam')}[prior]
+    given = dict(muinf=muinf, varinf=varinf, lam=lam)
+    for name in need:
+        if _empty(given[name]):
+            raise ValueError('the %s prior reads %s' % (prior, name))
+    return T, D, K, [A, vary, w] + [_vec(given[name], K, name) if name in need else None for name in ('muinf', 'varinf', 'lam')]
+
+
+class NmfTempHandle(ResidentHandle):
     """The resident form (nagp_nmf_temp_create): A, vary, a given W, the prior parameters and the partial-sum buffers stay on the
     device; eval(x) moves x (P, nx) in and Obj (P,), dObj (P, nx) out.  W = None: the learning form, nx = T K + K D (K is then
     required); W (K, D) or (P, K, D): the inference form, nx = T K."""
+    _eval, _destroy = 'nagp_nmf_temp_eval', 'nagp_nmf_temp_destroy'
 
     def __init__(self, A, vary, W=None, prior='none', muinf=None, varinf=None, lam=None, K=None, n_problems=1, device=0):
         import ctypes as C
-        if prior not in PRIORS:
-            raise ValueError('prior is one of %s: got %r' % (sorted(PRIORS), prior))
-        A, vary = _data(A, vary)
-        self.T, self.D = A.shape; self.P = int(n_problems)
-        w = None
-        if W is not None:
-            w, k = _weights(W, self.P, self.D)
-            if K is not None and int(K) != k:
+
+        def pick_K(T, D, k):
+            if k is not None and K is not None and int(K) != k:
                 raise ValueError('K = %d but W has %d rows' % (K, k))
-            K = k
-        if K is None:
-            raise ValueError('the learning form needs K')
-        self.K = int(K); self.learn = W is None
+            if k is None and K is None:
+                raise ValueError('the learning form needs K')
+            return K if k is None else k
+        self.P = int(n_problems)
+        self.T, self.D, self.K, arrays = _shaped(A, vary, W, self.P, prior, muinf, varinf, lam, pick_K)
+        self.learn = W is None
         self.nx = self.T * self.K + (self.K * self.D if self.learn else 0)
-        need = {'none': (), 'tg': ('varinf', 'lam'), 'ig': ('muinf', 'varinf', 'lam')}[prior]
-        given = dict(muinf=muinf, varinf=varinf, lam=lam)
-        for name in need:
-            if _empty(given[name]):
-                raise ValueError('the %s prior reads %s' % (prior, name))
-        pr = [_vec(given[name], self.K, name) if name in need else None for name in ('muinf', 'varinf', 'lam')]
-        self._h = C.c_void_p()
-        L.check(L.lib().nagp_nmf_temp_create(C.byref(self._h), self.P, self.T, self.D, self.K, PRIORS[prior], L.dptr(A), L.dptr(vary), L.dptr(w),
-                                             L.dptr(pr[0]), L.dptr(pr[1]), L.dptr(pr[2]), int(device)))
-
-    def eval(self, x, grad=True):
-        x = L.f64(np.asarray(x, float).reshape(self.P, self.nx), 'C')
-        Obj = np.zeros(self.P); dObj = np.zeros((self.P, self.nx)) if grad else None
-        if not self._h:
-            raise L.NagpError('the handle is closed')
-        L.check(L.lib().nagp_nmf_temp_eval(self._h, L.dptr(x), L.dptr(Obj), L.dptr(dObj)))
-        return (Obj, dObj) if grad else Obj
-
-    def close(self):
-        if self._h:
-            L.lib().nagp_nmf_temp_destroy(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        h = C.c_void_p()
+        L.check(L.lib().nagp_nmf_temp_create(C.byref(h), self.P, self.T, self.D, self.K, PRIORS[prior], *map(L.dptr, arrays), int(device)))
+        self._h = h
 
 
 def nmf_temp_obj(x, A, vary, W=None, prior='none', muinf=None, varinf=None, lam=None, grad=True, device=0):
@@ -148,32 +133,23 @@ def nmf_temp_obj(x, A, vary, W=None, prior='none', muinf=None, varinf=None, lam=
     (T K + K D,) or (P, T K + K D) = [log H(:); log W(:)] per problem, K = numel / (T + D) as the .m; W (K, D) or (P, K, D): the inference
     form, x (T K,) or (P, T K).  muinf, varinf, lam: K each, as the prior reads them.  Returns Obj and, with grad, dObj, with the leading
     problem axis of x."""
-    if prior not in PRIORS:
-        raise ValueError('prior is one of %s: got %r' % (sorted(PRIORS), prior))
     x = np.asarray(x, float); single = x.ndim <= 1
     xx = L.f64(np.atleast_2d(x), 'C')
     if xx.ndim != 2:
         raise ValueError('x must be (nx,) or (P, nx): got %s' % (x.shape,))
-    A, vary = _data(A, vary)
-    T, D = A.shape; P, nx = xx.shape
-    w = None
-    if W is None:
-        K = nx // (T + D)
-        if K < 1 or K * (T + D) != nx:
-            raise ValueError('x holds T K + K D entries per problem (T = %d, D = %d): got %d' % (T, D, nx))
-    else:
-        w, K = _weights(W, P, D)
-        if nx != T * K:
-            raise ValueError('x holds T K = %d entries per problem: got %d' % (T * K, nx))
-    need = {'none': (), 'tg': ('varinf', 'lam'), 'ig': ('muinf', 'varinf', 'lam')}[prior]
-    given = dict(muinf=muinf, varinf=varinf, lam=lam)
-    for name in need:
-        if _empty(given[name]):
-            raise ValueError('the %s prior reads %s' % (prior, name))
-    pr = [_vec(given[name], K, name) if name in need else None for name in ('muinf', 'varinf', 'lam')]
+    P, nx = xx.shape
+
+    def pick_K(T, D, k):
+        if k is None:
+            k = nx // (T + D)
+            if k < 1 or k * (T + D) != nx:
+                raise ValueError('x holds T K + K D entries per problem (T = %d, D = %d): got %d' % (T, D, nx))
+        elif nx != T * k:
+            raise ValueError('x holds T K = %d entries per problem: got %d' % (T * k, nx))
+        return k
+    T, D, K, arrays = _shaped(A, vary, W, P, prior, muinf, varinf, lam, pick_K)
     Obj = np.zeros(P); dObj = np.zeros((P, nx)) if grad else None
-    L.check(L.lib().nagp_nmf_temp_obj(P, T, D, K, PRIORS[prior], L.dptr(xx), L.dptr(A), L.dptr(vary), L.dptr(w), L.dptr(pr[0]), L.dptr(pr[1]),
-                                      L.dptr(pr[2]), L.dptr(Obj), L.dptr(dObj), int(device)))
+    L.check(L.lib().nagp_nmf_temp_obj(P, T, D, K, PRIORS[prior], L.dptr(xx), *map(L.dptr, arrays), L.dptr(Obj), L.dptr(dObj), int(device)))
     if single:
         return (Obj[0], dObj[0]) if grad else Obj[0]
     return (Obj, dObj) if grad else Obj
@@ -212,10 +188,6 @@ class _Closing:
         return self.f(X)
 
 
-def _opt(opts, name, default):
-    return default if not opts or name not in opts else opts[name]
-
-
 def chunked_steps(x0, numIts, progress_chunk):
     """the loop of nmf.m:111-169 / nmf_inf.m:99-152 as a generator: ceil(numIts / progress_chunk) chunks, each a fresh minimize of
     progress_chunk line searches from the result of the one before.  It yields a point and is sent (f, df) there; its return value is
@@ -224,35 +196,9 @@ def chunked_steps(x0, numIts, progress_chunk):
     x = np.asarray(x0, float).reshape(-1)
     Obj = []; it = []
     for _ in range(Lc):
-        steps = minimize_steps(x, int(progress_chunk))
-        try:
-            pt = next(steps)
-            while True:
-                pt = steps.send((yield pt))
-        except StopIteration as e:
-            x, fX, i = e.value
+        x, fX, i = yield from minimize_steps(x, int(progress_chunk))
         Obj.append(fX); it.append(i)
     return x, (np.concatenate(Obj) if Obj else np.zeros(0)), np.array(it, int)
-
-
-def _lock_step(f, gens, nx):
-    """the generators in lock-step on one batched evaluator: a round is one f(X); a generator that has finished drops out (its row rides
-    along with its last point).  A problem's bits do not depend on its batch mates, so the results equal the one-at-a-time runs."""
-    n = len(gens)
-    X = np.zeros((n, nx)); out = [None] * n; live = {}
-    for j, g in enumerate(gens):
-        try:
-            X[j] = next(g); live[j] = g
-        except StopIteration as e:                          # numIts = 0
-            out[j] = e.value
-    while live:
-        Obj, dObj = f(X)
-        for j in list(live):
-            try:
-                X[j] = live[j].send((Obj[j], dObj[j]))
-            except StopIteration as e:
-                out[j] = e.value; del live[j]
-    return out
 
 
 def _check_WH(A, W, H):
@@ -272,10 +218,9 @@ def nmf_inf_many(A, Ws, Hs, muinf, varinf, lam, vary, numIts=1000, progress_chun
         gens = [chunked_steps(np.log(np.asarray(H, float)).reshape(-1, order='F'), numIts, progress_chunk) for H in Hs]
     f = (evaluator or _device_evaluator(device))(A, vary, np.stack([np.asarray(W, float) for W in Ws]), K, prior, mu, vi, la, n)
     try:
-        res = _lock_step(f, gens, T * K)
+        res, _ = lock_step_rows(f, gens, T * K)
     finally:
-        if hasattr(f, 'close'):
-            f.close()
+        close(f)
     return [(np.exp(x.reshape(T, K, order='F')), {'Obj': Obj, 'it': it}) for x, Obj, it in res]
 
 
@@ -341,10 +286,9 @@ def nmf(A, W, H, muinf, varinf, lam, vary, opts=None, inits=None, seed=None, eva
         x0 = np.concatenate([np.log(H).reshape(-1, order='F'), np.log(W).reshape(-1, order='F')])
     f = (evaluator or _device_evaluator(device))(A, vary, None, K, prior, mu, vi, la, 1)
     try:
-        (x, Obj, it), = _lock_step(f, [chunked_steps(x0, numIts, chunk)], T * K + K * D)
+        ((x, Obj, it),), _ = lock_step_rows(f, [chunked_steps(x0, numIts, chunk)], T * K + K * D)
     finally:
-        if hasattr(f, 'close'):
-            f.close()
+        close(f)
     H = np.exp(x[:T * K].reshape(T, K, order='F'))
     W = np.exp(x[T * K:].reshape(K, D, order='F'))
     W = (1.0 / np.sum(W, axis=1))[:, None] * W                                                    # :138

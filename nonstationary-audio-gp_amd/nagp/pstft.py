@@ -16,12 +16,11 @@ import math
 import numpy as np
 
 from . import _lib as L
+from ._drive import forward, lock_step, opt as _opt, run
+from .minimize import minimize, minimize_steps, INT, EXT, MAX, RATIO, SIG, RHO, REALMIN  # noqa: F401  (their home is minimize.py)
 
 KERNEL_ID = {'exp': 0, 'matern32': 1, 'matern52': 2, 'matern72': 3}
 CLOSED = ('exp', 'matern32', 'matern52')                     # the kernels with a get_Obj_pSTFT_<kernel>.m (fit_probSTFT_SD.m:285-289)
-INT, EXT, MAX, RATIO, SIG = 0.1, 3.0, 20, 10.0, 0.1         # minimize.m:42-46
-RHO = SIG / 2
-REALMIN = np.finfo(float).tiny
 
 
 def _kernel_id(kernel):
@@ -111,112 +110,6 @@ def freq2probSpec(fmax, df, varMa):
     return om, lamx, np.asarray(varMa, float) * (1 - lamx ** 2)
 
 
-def minimize_steps(X, length):
-    """The algorithm of minimize.m -- Polak-Ribiere conjugate gradients, a line search by cubic extrapolation and quadratic / cubic
-    interpolation under the Wolfe-Powell conditions, the slope-ratio guess of the first step -- as a generator: it yields a point and
-    is sent (f, df) there; its return value (StopIteration.value) is (X, fX, i).  length > 0: at most that many line searches,
-    < 0: at most that many evaluations; a pair (length, red) sets the reduction expected of the first line search.  A non-finite
-    f or df during extrapolation halves the step, as the .m's catch does.  An interpolation whose square root is of a negative number
-    bisects (the .m would carry a complex step into max / min)."""
-    red = 1.0
-    if np.ndim(length) > 0:
-        length, red = length[0], length[1]
-    X = np.array(X, float).reshape(-1)
-    with np.errstate(all='ignore'):
-        i = 0; ls_failed = False
-        f0, df0 = yield X.copy()
-        f0 = np.float64(f0); df0 = np.asarray(df0, float).reshape(-1)
-        fX = [f0]
-        i += length < 0
-        s = -df0; d0 = -s @ s
-        x3 = np.float64(red) / (1 - d0)
-        while i < abs(length):
-            i += length > 0
-            X0, F0, dF0 = X.copy(), f0, df0
-            M = MAX if length > 0 else min(MAX, -length - i)
-            while True:                                      # extrapolate
-                x2, f2, d2, f3, df3 = np.float64(0), f0, d0, f0, df0
-                success = False
-                while not success and M > 0:
-                    M -= 1; i += length < 0
-                    f3, df3 = yield X + x3 * s
-                    f3 = np.float64(f3); df3 = np.asarray(df3, float).reshape(-1)
-                    if not np.isfinite(f3) or not np.all(np.isfinite(df3)):
-                        x3 = (x2 + x3) / 2                   # bisect and try again
-                        continue
-                    success = True
-                if f3 < F0:
-                    X0, F0, dF0 = X + x3 * s, f3, df3
-                d3 = df3 @ s
-                if d3 > SIG * d0 or f3 > f0 + x3 * RHO * d0 or M == 0:
-                    break
-                x1, f1, d1 = x2, f2, d2
-                x2, f2, d2 = x3, f3, d3
-                A = 6 * (f1 - f2) + 3 * (d2 + d1) * (x2 - x1)
-                B = 3 * (f2 - f1) - (2 * d1 + d2) * (x2 - x1)
-                disc = B * B - A * d1 * (x2 - x1)
-                x3 = x1 - d1 * (x2 - x1) ** 2 / (B + np.sqrt(disc)) if disc >= 0 else np.float64(np.nan)
-                if not np.isfinite(x3) or x3 < 0 or x3 > x2 * EXT:
-                    x3 = x2 * EXT
-                elif x3 < x2 + INT * (x2 - x1):
-                    x3 = x2 + INT * (x2 - x1)
-            while (abs(d3) > -SIG * d0 or f3 > f0 + x3 * RHO * d0) and M > 0:      # interpolate
-                if d3 > 0 or f3 > f0 + x3 * RHO * d0:
-                    x4, f4, d4 = x3, f3, d3
-                else:
-                    x2, f2, d2 = x3, f3, d3
-                if f4 > f0:
-                    x3 = x2 - (0.5 * d2 * (x4 - x2) ** 2) / (f4 - f2 - d2 * (x4 - x2))
-                else:
-                    A = 6 * (f2 - f4) / (x4 - x2) + 3 * (d4 + d2)
-                    B = 3 * (f4 - f2) - (2 * d2 + d4) * (x4 - x2)
-                    disc = B * B - A * d2 * (x4 - x2) ** 2
-                    x3 = x2 + (np.sqrt(disc) - B) / A if disc >= 0 else np.float64(np.nan)
-                if not np.isfinite(x3):
-                    x3 = (x2 + x4) / 2
-                x3 = max(min(x3, x4 - INT * (x4 - x2)), x2 + INT * (x4 - x2))
-                f3, df3 = yield X + x3 * s
-                f3 = np.float64(f3); df3 = np.asarray(df3, float).reshape(-1)
-                if f3 < F0:
-                    X0, F0, dF0 = X + x3 * s, f3, df3
-                M -= 1; i += length < 0
-                d3 = df3 @ s
-            if abs(d3) < -SIG * d0 and f3 < f0 + x3 * RHO * d0:                    # the line search succeeded
-                X = X + x3 * s; f0 = f3; fX.append(f0)
-                s = (df3 @ df3 - df0 @ df3) / (df0 @ df0) * s - df3                # Polak-Ribiere
-                df0 = df3
-                d3 = d0; d0 = df0 @ s
-                if d0 > 0:
-                    s = -df0; d0 = -s @ s
-                x3 = x3 * min(RATIO, d3 / (d0 - REALMIN))
-                ls_failed = False
-            else:
-                X, f0, df0 = X0, F0, dF0
-                if ls_failed or i > abs(length):
-                    break
-                s = -df0; d0 = -s @ s
-                x3 = 1 / (1 - d0)
-                ls_failed = True
-    return X, np.array(fX, float), int(i)
-
-
-def minimize(X, f, length, *args):
-    """[X, fX, i] = minimize(X, f, length, P1, P2, ...) (minimize.m:1): f(X, P1, ...) returns (value, gradient)."""
-    shape = np.shape(X)
-    g = minimize_steps(X, length)
-    try:
-        x = next(g)
-        while True:
-            x = g.send(f(x.reshape(shape), *args))
-    except StopIteration as e:
-        X, fX, i = e.value
-    return X.reshape(shape), fX, i
-
-
-def _opt(opts, name, default):
-    return default if not opts or name not in opts else opts[name]
-
-
 def _mirror(pg, T):
     """fit_probSTFT_SD.m:265-271: the two-sided spectrum, its length chosen by the parity of the SIGNAL length T"""
     return np.concatenate([pg, pg[-2:0:-1]]) if T % 2 == 0 else np.concatenate([pg, pg[:0:-1]])
@@ -283,13 +176,7 @@ def fit_steps(y, D, kernel, opts=None):
                                 np.log(lam_c - lamLim[:, 0]) - np.log(lamLim[:, 1] - lam_c)])
         vary = np.max(specTar) * vary_an[c2f]
         b = bet[c2f] * numFreq[c2f] / numFreq[c2f]                                # :299
-        steps = minimize_steps(theta, numIts)
-        try:
-            x = next(steps)
-            while True:
-                x = steps.send((yield (x, vary, specTar, minVar, omLim, lamLim, b, True)))
-        except StopIteration as e:
-            theta, ObjCur, inCur = e.value
+        theta, ObjCur, inCur = yield from forward(minimize_steps(theta, numIts), lambda x: (x, vary, specTar, minVar, omLim, lamLim, b, True))
         if yHO is not None:
             likeHO[c2f] = yield (theta, 0.0, specHO, minVar, omLim, lamLim, 0.0, False)
         likeUnReg[c2f] = yield (theta, 0.0, specUR, minVar, omLim, lamLim, 0.0, False)
@@ -321,43 +208,16 @@ def fit_probSTFT_SD(y, D, kernel, opts=None, evaluator=None, device=0):
     log of a negative number), opts['reassign'] = 1 (NotImplementedError); verbose plotting is ignored.
     evaluator(theta, vary, specTar, minVar, limOm, limLam, bet, grad): the objective, by default nagp_pstft_obj on `device`."""
     ev = evaluator or _device_evaluator(kernel, device)
-    g = fit_steps(y, D, kernel, opts)
-    try:
-        req = next(g)
-        while True:
-            req = g.send(ev(*req))
-    except StopIteration as e:
-        return e.value
+    return run(fit_steps(y, D, kernel, opts), lambda req: ev(*req))
 
 
 def fit_probSTFT_SD_many(ys, D, kernel, opts=None, device=0):
     """fit_probSTFT_SD on several signals in lock-step: one generator per signal, the pending evaluation requests of a round gathered
     and issued as one nagp_pstft_obj call per group of equal N (and equal shared arguments).  A problem's bits do not depend on its
     batch mates, so the results equal the one-at-a-time fits to the bit.  Returns a list of (varx, lamx, om, Info)."""
-    gens = [fit_steps(y, D, kernel, opts) for y in ys]
-    out = [None] * len(gens); pending = {}
-    for k, g in enumerate(gens):
-        try:
-            pending[k] = next(g)
-        except StopIteration as e:
-            out[k] = e.value
-    while pending:
-        groups = {}
-        for k, r in pending.items():
-            key = (r[2].size, r[7], r[3].tobytes(), r[4].tobytes(), r[5].tobytes())
-            groups.setdefault(key, []).append(k)
-        answers = {}
-        for ks in groups.values():
-            r0 = pending[ks[0]]
-            res = pstft_obj(np.stack([pending[k][0] for k in ks]), np.array([pending[k][1] for k in ks]), np.stack([pending[k][2] for k in ks]),
-                            r0[3], r0[4], r0[5], np.array([pending[k][6] for k in ks]), kernel, grad=r0[7], device=device)
-            for j, k in enumerate(ks):
-                answers[k] = (res[0][j], res[1][j]) if r0[7] else res[j]
-        nxt = {}
-        for k, a in answers.items():
-            try:
-                nxt[k] = gens[k].send(a)
-            except StopIteration as e:
-                out[k] = e.value
-        pending = nxt
-    return out
+    def issue(rs):
+        grad = rs[0][7]
+        res = pstft_obj(np.stack([r[0] for r in rs]), np.array([r[1] for r in rs]), np.stack([r[2] for r in rs]),
+                        rs[0][3], rs[0][4], rs[0][5], np.array([r[6] for r in rs]), kernel, grad=grad, device=device)
+        return list(zip(*res)) if grad else res
+    return lock_step([fit_steps(y, D, kernel, opts) for y in ys], lambda r: (r[2].size, r[7], r[3].tobytes(), r[4].tobytes(), r[5].tobytes()), issue)

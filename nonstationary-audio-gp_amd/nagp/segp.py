@@ -6,7 +6,7 @@ vector (experiments/train_model.m:132-149, train_GTFNMF.m:91-108, train_GTFNMF_g
     [fftCov,dfftCov] = getGPSESpec(len,T)                                      experiments/toolsGP/getGPSESpec.m
 
 The objective and its gradient -- every sum over the T frequencies of the periodogram -- run on the GPU (nagp_segp_obj, include/nagp.h);
-the FFT of the signal (arbitrary length), the conjugate-gradient line search (pstft.minimize_steps) and the 201-tap smoothing of
+the FFT of the signal (arbitrary length), the conjugate-gradient line search (minimize.minimize_steps) and the 201-tap smoothing of
 modulator_prior_init stay on the host.  There is no CPU fallback: the `evaluator` argument of the fit exists so that the tests can
 put the float64 restatement through the same driver.
 """
@@ -16,7 +16,8 @@ import warnings
 import numpy as np
 
 from . import _lib as L
-from .pstft import minimize_steps
+from ._drive import forward, lock_step, opt as _opt, run
+from .minimize import minimize_steps
 
 
 def segp_obj(param, specy, vary=None, varx=None, grad=True, device=0):
@@ -73,10 +74,6 @@ def getGPSESpec(len, T, nout=1):
     return fftCov, fftCov * (1.0 / ell[None, :] - omega ** 2 * ell[None, :])
 
 
-def _opt(opts, name, default):
-    return default if not opts or name not in opts else opts[name]
-
-
 def train_steps(x, opts=None, lenx=None, varx=None, vary=None):
     """trainSEGP_RS as a generator: it yields a request (param, specx, vary, varx) and is sent (obj, dobj); its return value is
     (lenx, varx, info)."""
@@ -104,13 +101,7 @@ def train_steps(x, opts=None, lenx=None, varx=None, vary=None):
     Obj, it = [], []
     params = np.array([np.log(lenx)])                                                                # :82: log(lenx) alone is optimised
     for _ in range(n_chunks):
-        steps = minimize_steps(params, progress_chunk)
-        try:
-            p = next(steps)
-            while True:
-                p = steps.send((yield (p, specx, vary, varx)))
-        except StopIteration as e:
-            params, ObjCur, itCur = e.value
+        params, ObjCur, itCur = yield from forward(minimize_steps(params, progress_chunk), lambda p: (p, specx, vary, varx))
         lenx = float(np.exp(params[0]))
         Obj.append(ObjCur); it.append(itCur)
     info = {'Obj': np.concatenate(Obj) if Obj else np.zeros(0), 'it': np.array(it, int)}
@@ -136,13 +127,7 @@ def trainSEGP_RS(x, opts=None, lenx=None, varx=None, vary=None, evaluator=None, 
     one nagp_segp_obj call.
     evaluator(param, specy, vary, varx) -> (obj, dobj): the objective, by default nagp_segp_obj on `device`."""
     ev = evaluator or _device_evaluator(device)
-    g = train_steps(x, opts, lenx, varx, vary)
-    try:
-        req = next(g)
-        while True:
-            req = g.send(ev(*req))
-    except StopIteration as e:
-        return e.value
+    return run(train_steps(x, opts, lenx, varx, vary), lambda req: ev(*req))
 
 
 def _per_signal(v, n, name):
@@ -162,31 +147,10 @@ def trainSEGP_RS_many(xs, opts=None, lenx=None, varx=None, vary=None, device=0):
     one-at-a-time fits to the bit.  lenx, varx, vary: scalars or one entry per signal.  Returns a list of (lenx, varx, info)."""
     n = len(xs)
     ls, vxs, vys = _per_signal(lenx, n, 'lenx'), _per_signal(varx, n, 'varx'), _per_signal(vary, n, 'vary')
-    gens = [train_steps(x, opts, ls[k], vxs[k], vys[k]) for k, x in enumerate(xs)]
-    out = [None] * n; pending = {}
-    for k, g in enumerate(gens):
-        try:
-            pending[k] = next(g)
-        except StopIteration as e:
-            out[k] = e.value
-    while pending:
-        groups = {}
-        for k, r in pending.items():
-            groups.setdefault(r[1].size, []).append(k)
-        answers = {}
-        for ks in groups.values():
-            Obj, dObj = segp_obj(np.stack([pending[k][0] for k in ks]), np.stack([pending[k][1] for k in ks]),
-                                 vary=np.array([pending[k][2] for k in ks]), varx=np.array([pending[k][3] for k in ks]), device=device)
-            for j, k in enumerate(ks):
-                answers[k] = (Obj[j], dObj[j])
-        nxt = {}
-        for k, a in answers.items():
-            try:
-                nxt[k] = gens[k].send(a)
-            except StopIteration as e:
-                out[k] = e.value
-        pending = nxt
-    return out
+    def issue(rs):
+        return list(zip(*segp_obj(np.stack([r[0] for r in rs]), np.stack([r[1] for r in rs]), vary=np.array([r[2] for r in rs]),
+                                  varx=np.array([r[3] for r in rs]), device=device)))
+    return lock_step([train_steps(x, opts, ls[k], vxs[k], vys[k]) for k, x in enumerate(xs)], lambda r: r[1].size, issue)
 
 
 def conv_same(u, v):

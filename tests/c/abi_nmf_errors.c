@@ -50,6 +50,10 @@ int main(void) {
   if (memcmp(W, W0, P * K * D * sizeof *W) || memcmp(H, H0, P * T * K * sizeof *H)) { fprintf(stderr, "n_its = 0 did not copy the inputs\n"); ++bad; }
   EXPECT(nagp_nmf_fp(P, T, D, K, A, vary, W0, H0, 0, 1, NULL, NULL, NULL, 0), NAGP_OK);
   EXPECT(nagp_nmf_timings(NULL), NAGP_EINVAL);
+  { double ms = -1.0;                                                                                              /* a refused call reports no time */
+    EXPECT(CALL(P, T, 65, K, A, vary, W0, H0, ITS), NAGP_EUNSUPPORTED);
+    EXPECT(nagp_nmf_timings(&ms), NAGP_OK);
+    if (ms != 0.0) { fprintf(stderr, "nagp_nmf_timings after a refused call: %g, expected 0\n", ms); ++bad; } }
   free(A); free(vary); free(W0); free(H0); free(W); free(H); free(Obj);
   if (bad) { fprintf(stderr, "%d unexpected statuses\n", bad); return 1; }
   printf("all error paths returned their status\n");

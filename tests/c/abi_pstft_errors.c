@@ -63,6 +63,10 @@ int main(void) {
   vary[P - 1] = 1e-4;
   EXPECT(nagp_pstft_timings(NULL), NAGP_EINVAL);
   EXPECT(nagp_pstft_timings(&ms), NAGP_OK);
+  ms = -1.0;                                                             /* a refused call reports no time */
+  EXPECT(STD(4, 1, D, N, N), NAGP_EUNSUPPORTED);
+  EXPECT(nagp_pstft_timings(&ms), NAGP_OK);
+  if (ms != 0.0) { fprintf(stderr, "nagp_pstft_timings after a refused call: %g, expected 0\n", ms); ++bad; }
   free(theta); free(spec); free(vary); free(bet); free(minVar); free(limOm); free(limLam); free(Obj); free(dObj); free(big);
   if (bad) { fprintf(stderr, "%d unexpected statuses\n", bad); return 1; }
   printf("all error paths returned their status\n");

@@ -70,6 +70,13 @@ def call(A, Q, H, P0, y, vary, block, filter_only=0, sub=None, psub=True, output
                                    L.dptr(MS) if outputs else L.c_dp(), L.c_dp(), L.dptr(Ps) if (n_sub and psub) else L.c_dp(), 0)
 
 
+def refused_time():
+    """nagp_slowfb_timings after a refused call: no time of an earlier call on this thread"""
+    ms = np.full(3, -1.0)
+    assert L.lib().nagp_slowfb_timings(L.dptr(ms)) == 0
+    return ms.tolist()
+
+
 @pytest.fixture(scope='module')
 def m32():
     nagp.build()
@@ -94,6 +101,7 @@ def test_einval_cases(m32):
     assert call(A, Q, H, P0, y, v, 4, sub=[0, 4], psub=False) == EINVAL               # n_sub without Psub
     assert call(A, Q, H, P0, y, v, 4, outputs=False) == EINVAL                        # nothing asked for
     assert b'no output' in L.lib().nagp_last_error()
+    assert refused_time() == [0.0, 0.0, 0.0]
 
 
 def test_eunsupported_cases(m32):
@@ -108,6 +116,7 @@ def test_eunsupported_cases(m32):
     Qd = Q.copy(); Qd[0, 7] = 1e-3
     assert call(A, Qd, H, P0, y, v, 4) == EUNSUPPORTED
     assert call(A, Q, H, P0, y, v, 2) == EUNSUPPORTED                                  # blocks of 4 declared as blocks of 2
+    assert refused_time() == [0.0, 0.0, 0.0]
     with pytest.raises(L.NagpError, match='outside the blocks'):                       # the mirror detects no block and the library refuses
         nagp.kernel_ss_kalmanSlowFB(np.ones((12, 12)), np.eye(12), np.ones(12), np.eye(12), 12, 0.1, y)
 
@@ -120,6 +129,7 @@ def test_enomem_under_the_budget_switch(m32, monkeypatch):
     assert call(A, Q, H, P0, np.zeros(T), np.full(T, 1e-2), 4) == ENOMEM
     assert b'budget 1048576 B' in L.lib().nagp_last_error()
     assert call(A, Q, H, P0, np.zeros(T), np.full(T, 1e-2), 4, filter_only=1) == ENOMEM           # 8 T (S^2 + S + 2 + S) = 656 T
+    assert refused_time() == [0.0, 0.0, 0.0]
     assert call(A, Q, H, P0, np.zeros(1200), np.full(1200, 1e-2), 4, filter_only=1) != ENOMEM        # fits: refused later, for want of a device, or runs
 
 
