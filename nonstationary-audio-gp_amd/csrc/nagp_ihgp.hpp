@@ -545,6 +545,27 @@ __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomC
     for (int i = 0; i < 8; ++i) mc.stamps[i] += st[i];
 }
 
+// The look-up of the three-barrier schedule of ihgp_adf8_kernel in its two halves (nagp_lookup.hpp).  ih_window_reads: the three grid
+// words and three H PP H' entries round the seed mid = 1 .. NG - 2 (entries 0 .. NG - 1), one batch of LDS reads (the table's only
+// when it is in LDS).  Both halves are functions of scalars: as lambdas capturing by reference they put the captured state into scratch.
+// ih_window_pick, behind R: the index of the step's table entries and H PP H'; the two side paths -- finite R beyond the grid, the
+// table in global memory -- overwrite what the straight line selected.
+__device__ __forceinline__ void ih_window_reads(msp_rp p_rg, msp_rp p_hph, bool hph_in_lds, int mid, double& r0, double& r1, double& r2, double& h0, double& h1,
+                                                double& h2) {
+  r0 = p_rg[mid - 1]; r1 = p_rg[mid]; r2 = p_rg[mid + 1];
+  if (hph_in_lds) { h0 = p_hph[mid - 1]; h1 = p_hph[mid]; h2 = p_hph[mid + 1]; }      // (table in global memory: the grid words only)
+}
+__device__ __forceinline__ void ih_window_pick(int mid, double r0, double r1, double r2, double h0, double h1, double h2, msp_rp p_rg, msp_rp p_hph,
+                                               const double* g_hph, bool hph_in_lds, double rmax, int NG, double R, int& idx, double& hph) {
+  const int sel = lookup_pick3(r0, r1, r2, R);
+  idx = mid - 1 + sel;
+  hph = (sel == 0) ? h0 : ((sel == 1) ? h1 : h2);
+  if (lookup_beyond(rmax, R)) {
+    idx = lookup_tail(p_rg, NG, R);
+    hph = hph_in_lds ? p_hph[idx] : g_hph[idx];
+  } else if (!hph_in_lds) hph = g_hph[idx];      // (issued ahead of the ring stores; first used, and so waited for, where the head stores HPH)
+}
+
 // The same sweep with role-specialised waves (nagp_momsp.hpp, role layout): 512 threads, waves 0 / 1 as above, waves 2..7 run the
 // parallel stages of the cubature in their own loop.  A wave holds the registers of its role only, which is what lets two
 // waves share a SIMD.
@@ -565,10 +586,13 @@ __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomC
 //   c0 / c1 / c2, acc          as in the other schedule             (weights B2 .. B4, level 1 B4 .. B5; acc: one wave)
 //   wwt (static products)      wave 0, once                         wave 0                                       same lane
 //   W rows, look-up grid, H PP H' table: written ahead of the loop (one __syncthreads), read-only in it -- wave 0 reads its row of W
-//     between B4 and B5, both serial waves three grid words and three table entries round the seed in the head (one batch of reads)
-// The serial tail waits for none of its ring stores: the head's LDS reads are issued behind them and return in order, and the loop reads
-// no kernel argument (a scalar load in the head would bring an lgkmcnt(0) for the stores with it): the look-up's constants are copied
-// into vector registers ahead of the loop.
+//     between B4 and B5, both serial waves three grid words and three table entries round the seed in the site update (one batch of reads)
+// The look-up of step k+1 is seeded from ttau (lookup_mid_ttau_c, nagp_lookup.hpp) straight behind the clamp of the site update: the seed,
+// the address and the six reads run beside the exact division R = 1 / ttau and are waited for where R arrives, ahead of the ring stores;
+// behind R only the branch beyond the grid (finite R > rmax: lookup_tail), the pick among the three and the selects are left.
+// The serial tail waits for none of its ring stores: no LDS read of the straight path is issued behind them, and the loop reads
+// no kernel argument in the head or the site update (a scalar load there would bring an lgkmcnt(0) for the stores with it): the look-up's
+// constants are copied into vector registers ahead of the loop.
 // The I/O ring of this schedule is circular and streamed: slot k mod KB serves step k (KB = 16, 8 or 4), and four worker waves (2, 3, 6, 7:
 // the SIMDs without a serial wave) move one step's worth per step inside their idle window W(k) = B5(k) .. B2(k+1): they store the inputs
 // of step k+1 (loaded in W(k-1), carried in a register), load those of step k+2 and flush the outputs of step k-1.  The first step is
@@ -842,34 +866,33 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   double lk_lr0 = tb.lr0, lk_inv = tb.inv_dlr, lk_rmax = rmax;
   int lk_ng2 = NG - 2;
   if constexpr (NB1) asm volatile("" : "+v"(lk_lr0), "+v"(lk_inv), "+v"(lk_rmax), "+v"(lk_ng2));
+  double lk_c1, lk_c0;                               // the seed from ttau: its two folded constants
+  lookup_seed_consts(tb.lr0, tb.inv_dlr, lk_c1, lk_c0);
+  if constexpr (NB1) asm volatile("" : "+v"(lk_c1), "+v"(lk_c0));
   const bool hph_in_lds = ip.hph_lds != 0;
 
   // head of step k: table look-up, A m, the cubature's inputs (wave 0, no barrier).  IN_LOOP: k > 0 is known (the tables of k = 0 are the
   // prologue's).  NB1: the straight-line look-up (nagp_lookup.hpp) -- one branch, for finite R beyond the grid; the three grid words and,
   // with the H PP H' table in LDS, its three entries round the seed in ONE batch of LDS reads, the index selects among them.
+  // The window of the look-up is seeded from ttau (lookup_mid_ttau_c) in the site update, beside the division R = 1 / ttau: the seed, the
+  // address and the reads of the three grid words and, with the H PP H' table in LDS, its three entries are under way when R arrives;
+  // behind R only the branch beyond the grid, the pick among the three and the selects are left.  The prologue's head (k_start > 0:
+  // R of step k_start - 1 from memory) seeds from R as before -- the same window or one that holds the same minimiser.
   double hph = 0.0, wc[4] = {0, 0, 0, 0}, Am[4] = {0, 0, 0, 0}, fmun = 0.0;
-  auto head = [&](int64_t k, auto IN_LOOP) {
+  int w_mid = 1;
+  double w_r0 = 0.0, w_r1 = 0.0, w_r2 = 0.0, w_h0 = 0.0, w_h1 = 0.0, w_h2 = 0.0;
+  int w_idx = 0;
+  auto head = [&](int64_t k, auto IN_LOOP) __attribute__((always_inline)) {
     if (act) {
       if (decltype(IN_LOOP)::value || k > 0) {
         int idx;
         if constexpr (NB1) {
-          if (lookup_beyond(lk_rmax, Rprev)) {
-            idx = lookup_tail(p_rg, lk_ng2 + 2, Rprev);
-            hph = hph_in_lds ? p_hph[idx] : g_hph[idx];
-          } else {
-            const int mid = lookup_mid(lk_ng2, lk_lr0, lk_inv, Rprev);
-            double r0 = p_rg[mid - 1], r1 = p_rg[mid], r2 = p_rg[mid + 1];
-            if (hph_in_lds) {
-              double h0 = p_hph[mid - 1], h1 = p_hph[mid], h2 = p_hph[mid + 1];
-              asm volatile("" : "+v"(r0), "+v"(r1), "+v"(r2), "+v"(h0), "+v"(h1), "+v"(h2));
-              const int sel = lookup_pick3(r0, r1, r2, Rprev);
-              idx = mid - 1 + sel;
-              hph = (sel == 0) ? h0 : ((sel == 1) ? h1 : h2);
-            } else {
-              idx = mid - 1 + lookup_pick3(r0, r1, r2, Rprev);
-              hph = g_hph[idx];
-            }
+          if constexpr (!decltype(IN_LOOP)::value) {
+            w_mid = lookup_mid(lk_ng2, lk_lr0, lk_inv, Rprev);
+            ih_window_reads(p_rg, p_hph, hph_in_lds, w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2);
+            ih_window_pick(w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2, p_rg, p_hph, g_hph, hph_in_lds, lk_rmax, lk_ng2 + 2, Rprev, w_idx, hph);
           }
+          idx = w_idx;      // (IN_LOOP: picked in the site update of the step before)
           if (stamp) { asm volatile("" :: "v"(idx), "v"(hph)); IH_STAMP(6); }
         } else {
           idx = nearest_idx3(p_rg, NG, tb.lr0, tb.inv_dlr, rmax, Rprev);
@@ -899,7 +922,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   if (stamp) st_a = __builtin_readcyclecounter();      // (the prologue's head stamps slots 6 / 7 as the loop's do)
   if (wave <= 1) head(ip.k_start, std::false_type{});
   // NB1: the cubature's inputs of a step straight behind its head, each from this wave's own fmu / HPH stores (msp_wave_fence)
-  auto qv_or_link = [&]() {
+  auto qv_or_link = [&]() __attribute__((always_inline)) {
     msp_wave_fence();
     if (wave == 0) msr_qv_serial<CD>(xq, mc); else msp_link<CD>(x, mc);
   };
@@ -963,6 +986,10 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
           const double nnew = fma(ip.w_new, fma(-fmun, d2, d1) * r1, ip.w_old * n_old);
           if (!(tnew > 0.0)) ++n_clamped;
           tnew = max0(tnew);                                               // :274 (NaN -> 0, C-3)
+          if constexpr (NB1) {                                             // beside the division; ahead of the ring stores
+            w_mid = lookup_mid_ttau_c(lk_ng2, lk_c1, lk_c0, tnew);
+            ih_window_reads(p_rg, p_hph, hph_in_lds, w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2);
+          }
           double Rn = 1.0 / tnew;                                          // R = 1/ttau: the look-up key and an output, exact division
           // (for tnew > 0 the reference's R(:,k) = 1./ttau before the clamp is this value; otherwise :287 overwrites it with Inf)
           // R = inf: ttau = 0, or ttau of underflow size (1/ttau overflows while ys = tnu/ttau stays finite): the reference's
@@ -977,6 +1004,9 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
           d2v m01, m23;
           mreg[0] = fma(wc[0], g, Am[0]); mreg[1] = fma(wc[1], g, Am[1]); mreg[2] = fma(wc[2], g, Am[2]); mreg[3] = fma(wc[3], g, Am[3]);
           m01.x = mreg[0]; m01.y = mreg[1]; m23.x = mreg[2]; m23.y = mreg[3];
+          // the look-up of step k+1 from the window read above: ahead of the ring stores, so that the wait for the window takes no store
+          // with it, and behind the gain in program order, so that the window's reads have the division and the gain's chain to return in
+          if constexpr (NB1) ih_window_pick(w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2, p_rg, p_hph, g_hph, hph_in_lds, lk_rmax, lk_ng2 + 2, Rn, w_idx, hph);
           p_tt[ko] = tnew; p_tn[ko] = nnew; p_R[ko] = Rn;
           typedef d2v __attribute__((address_space(3))) * lds_d2p;
           lds_d2p mf = (lds_d2p)(p_MF + 4 * ko);

@@ -45,6 +45,37 @@ NAGP_LK_HD int lookup_mid(int ng2, double lr0, double inv_dlr, double R) {
   const int est = (int)(f + 0.5);
   return est < 1 ? 1 : (est > ng2 ? ng2 : est);
 }
+// The same centre from ttau = 1 / R, so that the window can be read beside the division that forms R: the coarse log10 of ttau with its
+// sign flipped.  The two estimates differ by at most twice the error of lookup_log10 (0.006 against a grid spacing of 0.030), and the
+// first minimiser lies within 0.51 spacings of log10 R, so it stays inside mid - 1 .. mid + 1.  ttau below DBL_MIN (zero, the denormals, -0):
+// 1.  There R is Inf (ttau <= 2^-1024: the window must hold index 0, while -log10 of a tiny ttau alone points at the other end of the
+// grid) or finite and beyond the grid (lookup_beyond: the caller leaves through lookup_tail and does not use the window).  ttau = +Inf
+// (R = 0): the estimate is below the grid, 1 as in lookup_mid.  The caller's ttau is never negative or NaN (max0).
+// The chain is part of every step of the serial waves, so it is written in as few operations as it takes: lookup_log10's polynomial
+// e + t + 0.3466 t (1 - t) as two fma, and -log10(2) inv_dlr and 0.5 - lr0 inv_dlr folded into one more (lookup_seed_consts, once per
+// launch); fma everywhere, so that host and device round alike.  No clamp ahead of the conversion: |est| < 4e4 for every normal ttau.
+NAGP_LK_HD void lookup_seed_consts(double lr0, double inv_dlr, double& c1, double& c0) {
+  c1 = -0.30102999566398120 * inv_dlr; c0 = 0.5 - lr0 * inv_dlr;
+}
+NAGP_LK_HD int lookup_mid_ttau_c(int ng2, double c1, double c0, double ttau) {
+  unsigned long long u;
+  __builtin_memcpy(&u, &ttau, 8);
+  const int e = (int)((u >> 52) & 0x7ff) - 1023;
+  const unsigned long long mu = (u & 0x000fffffffffffffull) | 0x3ff0000000000000ull;
+  double t;
+  __builtin_memcpy(&t, &mu, 8);
+  t -= 1.0;
+  const double l2 = fma(t, fma(t, -0.3466, 1.3466), (double)e);      // log2 ttau to ~0.01
+  double g = fma(l2, c1, c0);                                        // (-log10 ttau - lr0) inv_dlr + 0.5
+  g = (ttau >= 2.2250738585072014e-308) ? g : 0.5;
+  const int est = (int)g;
+  return est < 1 ? 1 : (est > ng2 ? ng2 : est);
+}
+NAGP_LK_HD int lookup_mid_ttau(int ng2, double lr0, double inv_dlr, double ttau) {
+  double c1, c0;
+  lookup_seed_consts(lr0, inv_dlr, c1, c0);
+  return lookup_mid_ttau_c(ng2, c1, c0, ttau);
+}
 // 0, 1 or 2: the first minimiser of |r[mid - 1 + s] - R|
 NAGP_LK_HD int lookup_pick3(double r0, double r1, double r2, double R) {
   const double d0 = fabs(r0 - R), d1 = fabs(r1 - R), d2 = fabs(r2 - R);
@@ -59,6 +90,16 @@ NAGP_LK_HD int nearest_idx3_sl(P r, int NG, double lr0, double inv_dlr, double r
   if (lookup_beyond(rmax, R)) return lookup_tail(r, NG, R);
   const int mid = lookup_mid(NG - 2, lr0, inv_dlr, R);
   return mid - 1 + lookup_pick3(r[mid - 1], r[mid], r[mid + 1], R);
+}
+// the seeded order of ihgp_adf8_kernel's site update: window from ttau, then R = 1 / ttau decides the branch and picks.  Same index as
+// nearest_idx3_sl(..., 1.0 / ttau) for every ttau >= 0 (tests/test_ihgp_lookup_seeded_host.py).
+template <class P>
+NAGP_LK_HD int nearest_idx3_seeded(P r, int NG, double lr0, double inv_dlr, double rmax, double ttau) {
+  const int mid = lookup_mid_ttau(NG - 2, lr0, inv_dlr, ttau);
+  const double r0 = r[mid - 1], r1 = r[mid], r2 = r[mid + 1];
+  const double R = 1.0 / ttau;
+  if (lookup_beyond(rmax, R)) return lookup_tail(r, NG, R);
+  return mid - 1 + lookup_pick3(r0, r1, r2, R);
 }
 
 }  // namespace nagp
