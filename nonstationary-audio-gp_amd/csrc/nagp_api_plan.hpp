@@ -724,7 +724,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
     if (ihgp_filter_lds_doubles(sh, t, p->tb.NG, p->hph_lds, p->kb_ih) * sizeof(double) > 156 * 1024) t.cache_tabs = 0;
     p->cache_f = t.cache_tabs; p->sta_f = t.store_a;
     p->lds_ih = ihgp_filter_lds_doubles(sh, t, p->tb.NG, p->hph_lds, p->kb_ih) * sizeof(double);
-    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp filter: LDS %zu B, hph table in LDS %d, cubature tables in LDS %d, block-structured mom %d, mom LDS %zu B\n", p->lds_ih, p->hph_lds, p->cache_f, p->src_f, mom_lds_doubles(t) * sizeof(double));
+    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp filter: LDS %zu B, hph table in LDS %d, cubature tables in LDS %d, block-structured mom %d, mom LDS %zu B, block stride %d\n", p->lds_ih, p->hph_lds, p->cache_f, p->src_f, mom_lds_doubles(t) * sizeof(double), (int)sh.BS);
     // the ADF sweep in the sparse-point form (ihgp_adf_kernel): plain NMF likelihood, <= 320 sigma points, unstructured Wnmf
     // (plans with a block of 5 .. 8 states, BS = 8: the general ADF kernel ihgp_filter_kernel at block stride 8; the affine scans are instantiated for both strides)
     if (sh.BS == 4 && p->sp.enabled && !p->src_f && sh.M <= 64 && sh.D <= 4 * MSP_DT && o->n_pts <= MSP_NT + 64 && (o->n_pts + 3) / 4 <= MSP_NW * MSP_NST) {
@@ -766,8 +766,9 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
         PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SQ, o->cub_dim, true, false, false), p->lds_sq));
       }
     }
+    p->seq_ih = dev.ih_seq && !p->sq_ih && !p->sp_ih && !p->src_f;
     if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);
-    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B)\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B), table form of stage 1b %d, sequential kernels in every sweep %d\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8, (int)(p->sp_ih8 && dev.ih_tables), p->seq_ih);
     PLAN_TRY(set_kernel(p->k.ih_filter, pick_ih_filter(mom_variant(mc), p->src_f, sh.BS == 8), p->lds_ih));
     for (int mode = 0; mode < 2; ++mode) {      // the affine scans and the sequential scan use no dynamic LDS
       PLAN_TRY(set_kernel(p->k.aff_compose[mode], pick_aff_compose(mode, sh.BS), 0));
@@ -803,7 +804,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
     // pipelined plans: the filter's workgroup asks for the whole LDS of its CU, so that no workgroup of the smoother kernels running
     // beside it on the second stream is placed on the same CU (the filter is the critical path; its time is latency, not occupancy)
     if (p->pipeline && B <= 128 && p->lds_filter < 160 * 1024) p->lds_filter = 160 * 1024;     // (never BELOW what the kernel needs: set_lds refuses > 160 KiB)
-    if (dev.stamps) fprintf(stderr, "[nagp plan] gf filter: LDS %zu B, ring %d steps, cubature tables in LDS %d, mom LDS %zu B, sparse-point ADF %d\n", p->lds_filter, p->kb_f, p->cache_f, ekf ? (size_t)0 : mom_lds_doubles(t) * sizeof(double), p->sp_gf);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] gf filter: LDS %zu B, ring %d steps, cubature tables in LDS %d, mom LDS %zu B, sparse-point ADF %d, split blocks %d, likelihood %d, MFMA span passes at Sp %d\n", p->lds_filter, p->kb_f, p->cache_f, ekf ? (size_t)0 : mom_lds_doubles(t) * sizeof(double), p->sp_gf, (int)split, (int)o->lik_kind, (int)p->mfma_sp);
     // ADF sweep with role-specialised waves (nagp_gfadf8.hpp): 512 threads, <= 2 lower tiles per thread, the role layout's limits
     // (one sigma point per worker lane; the cubature sums from bin sums as in the IHGP sweep)
     if (p->sp_gf && sh.M * (sh.M + 1) / 2 <= 2 * MSR_NT && sh.S <= MSR_NT && p->sp.bdesc &&
@@ -919,6 +920,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
     if (p->sq_ep) PLAN_TRY(set_kernel(p->k.site, pick_ep_site(FORM_SQ, o->cub_dim), p->lds_ep_sq));
     else if (p->sp_ep) PLAN_TRY(set_kernel(p->k.site, pick_ep_site(FORM_SP, o->cub_dim), p->lds_ep_sp));
     else PLAN_TRY(set_kernel(p->k.site, pick_ep_site(FORM_GENERAL, mom_variant(mc)), p->lds_ep));
+    if (dev.stamps) fprintf(stderr, "[nagp plan] site refresh: sparse-point form %d, staged square-root form %d\n", p->sp_ep, p->sq_ep);
   }
   p->nlZ.assign((size_t)B * o->ep_itts, 0.0);
   p->mdM.assign((size_t)B * o->ep_itts, 0.0);

@@ -724,7 +724,7 @@ static int exec_ihgp(nagp_plan* p) {
   for (int itt = 1; itt <= I; ++itt) {
     // forward: sweep 1 is the sequential ADF filter; later sweeps have fixed sites for k < T-1 (an affine
     // recursion, run parallel in time) and one ADF step at k = T-1
-    const bool seq = p->dev.ih_seq && !p->sq_ih && !p->sp_ih && !p->src_f;      // developer switch: the sequential kernels (general ADF filter, ihgp_scan_kernel) for every sweep instead of the affine scans
+    const bool seq = p->seq_ih;      // developer switch (decided at plan creation): the sequential kernels (general ADF filter, ihgp_scan_kernel) for every sweep instead of the affine scans
     if (itt > 1 && !seq) RUN(affine(0, sh.T - 1, itt));
     IhgpPar ip{itt, p->damping[itt - 1], itt == 1 ? 1 : 0, (itt == 1 || seq) ? (int64_t)0 : (int64_t)(sh.T - 1)};
     ip.hph_lds = p->hph_lds; ip.kb = p->kb_ih;

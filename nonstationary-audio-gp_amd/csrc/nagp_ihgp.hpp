@@ -1590,6 +1590,7 @@ __global__ void __launch_bounds__(256) ihgp_aff_apply_kernel(Shape sh, Bufs b, I
   const int64_t T = sh.T;
   const int gid = blockIdx.x * blockDim.x + threadIdx.x;
   double mxM = 0.0, mxP = 0.0;
+  unsigned long long n_clamped = 0;      // (MODE == 0) sites the stored clamp acts on, counted as the sequential kernels count them
   if (gid < ap.ns * M) {
     const int j = gid / M, n = gid - j * M;
     const double* mdl = b.model + (size_t)pb * mdl_size(sh);
@@ -1625,6 +1626,7 @@ __global__ void __launch_bounds__(256) ihgp_aff_apply_kernel(Shape sh, Bufs b, I
         for (int i = 0; i < BS; ++i)
           if (i < bs) mfp[i] = x[i];
         b.fm[ix] = hn * x[0];
+        if (!(b.ttau[ix] > 0.0)) ++n_clamped;
         b.ttau[ix] = max0(b.ttau[ix]);     // the clamp of :274 is stored
         b.R[ix] = aux;                      // unchanged, or Inf for clamped sites (:287)
       } else {
@@ -1643,6 +1645,7 @@ __global__ void __launch_bounds__(256) ihgp_aff_apply_kernel(Shape sh, Bufs b, I
       }
     }
   }
+  if (MODE == 0 && n_clamped) atomicAdd(&b.counters[(size_t)pb * 4 + 1], n_clamped);
   if (MODE == 1) {
     mxM = wave_max(mxM);
     mxP = wave_max(mxP);

@@ -80,10 +80,12 @@ def _newton_dare(A, Q, h, rr, P):
     return np.where(better[:, None, None], Pn, P)
 
 
-def build_tables(A, Q, offsets, h_val, n_grid=200, n_knots=32):
-    """Returns (r, PPlist, pp_offsets, PGlist, pg_offsets) in the flat layout of nagp_ihgp_tables."""
+def build_knots(A, Q, offsets, h_val, n_knots=32):
+    """The solved level of the tables (PPlisto of ihgp_ep_modulator_nmf.m:107-127 and its smoother counterpart): returns
+    (ro, PPs, PGs, good) with PPs[n] (len(good[n]) x b^2) and PGs[n] (len(good[n]) x 2 b^2, rows [PS2(:)' G(:)']) on the knots
+    ro[good[n]] of block n.  build_tables interpolates these to the look-up grid."""
     M = len(h_val)
-    r = np.logspace(-2, 4, n_grid); ro = np.logspace(-2, 4, n_knots)
+    ro = np.logspace(-2, 4, n_knots)
     sizes = [int(offsets[n + 1]) - int(offsets[n]) for n in range(M)]
     PPs = [None] * M; PGs = [None] * M; good = [None] * M
     for b in sorted(set(sizes)):
@@ -141,6 +143,14 @@ def build_tables(A, Q, offsets, h_val, n_grid=200, n_knots=32):
             # MATLAB column-major flattening PP(:)'
             PPs[n] = np.stack([PP[sl][j].flatten(order='F') for j in g])
             PGs[n] = np.stack([np.concatenate([PS2[sl][j].flatten(order='F'), G[sl][j].flatten(order='F')]) for j in g])
+    return ro, PPs, PGs, good
+
+
+def build_tables(A, Q, offsets, h_val, n_grid=200, n_knots=32):
+    """Returns (r, PPlist, pp_offsets, PGlist, pg_offsets) in the flat layout of nagp_ihgp_tables."""
+    M = len(h_val)
+    r = np.logspace(-2, 4, n_grid)
+    ro, PPs, PGs, good = build_knots(A, Q, offsets, h_val, n_knots)
     pp_parts, pg_parts, pp_off, pg_off = [], [], [], []
     npp = npg = 0
     for n in range(M):

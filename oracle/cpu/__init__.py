@@ -79,7 +79,7 @@ def _p(a):
 def _cub(mom, dim):
     """(lik_kind, link_kind, link_shift, wn, xn[dim][npts]) of an oracle.lik.Mom"""
     from .. import cubature as ocub, lik as olik
-    if mom.kind == olik.LIK_POWER_NMF_SQRT:
+    if mom.kind == olik.LIK_POWER_NMF_SQRT or mom.wn is not None:      # (explicit points: tools/make_ep_fixture.py hands over the stored ones)
         wn, xn = mom.wn, mom.xn_unscaled
     else:
         wn, xn = ocub.sigma_points(mom.p, dim, mom.quirks)

@@ -5,6 +5,8 @@ full-covariance Power-EP Kalman filter + RTS smoother.
 PARITY UNPINNED: the reference has no tests/golden vectors for this path and no
 MATLAB/Octave exists here; pinned by tests/test_oracle_selfpins.py (Gaussian-site EP
 == exact GP regression, etc).
+The ARITHMETIC of run_predict (predict mode) is pinned: tools/make_ep_fixture.py restates it as written in 320-bit arithmetic from exact
+f64 inputs, and tests/test_ep_fixture.py holds this file to tests/golden/ep_multiprecision.npz at the stored err_oracle (1e-15 .. 1e-13).
 
 Follows (file:line under /root/reference/matlab):
   gf_ep_modulator_nmf.m:58-66 (input merge), :92-352 (predict mode), :357-533 (nlml mode)

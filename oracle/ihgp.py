@@ -3,6 +3,8 @@
 Line-by-line CPU restatement of the reference's infinite-horizon (steady-state) Power-EP
 filter/smoother.  PARITY UNPINNED (no reference fixtures, no MATLAB); self-pinned by
 tests/test_oracle_selfpins.py (DARE residuals, IHGP filter == full KF after burn-in).
+The ARITHMETIC of run_predict on given tables is pinned: tools/make_ep_fixture.py restates it as written in 320-bit arithmetic (the tables
+are inputs there), and tests/test_ep_fixture.py holds this file to tests/golden/ep_multiprecision.npz at the stored err_oracle.
 
 Follows (file:line under /root/reference/matlab):
   ihgp_ep_modulator_nmf.m:59-97 (set-up), :99-141 (forward DARE tables), :148-191 (smoother

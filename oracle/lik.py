@@ -3,6 +3,8 @@
 CPU restatement of the reference's `mom` callbacks (tilted-distribution moments by cubature).
 PARITY UNPINNED (no reference fixtures); self-pinned by tests/test_oracle_selfpins.py
 (test_mom_derivatives_vs_finite_differences, test_ep_with_gaussian_site_is_exact_gp_regression).
+Its ARITHMETIC is pinned: _moments is restated in 384-bit floats by tools/make_ep_fixture.py, and tests/test_ep_fixture.py holds this file
+to that restatement (all three likelihoods, both links, the shift, the power-EP constant; tests/golden/ep_multiprecision.npz, err_oracle).
 
 Follows (file:line under /root/reference/matlab):
   likModulatorPower.m:25-100            (one modulator per sub-band, jitter 1e-8)
