@@ -74,7 +74,8 @@ struct DevSwitches {
   bool nmft_valu = false;        // NAGP_NMFT_VALU: the H' dA partial products of nmft_pass_kernel on the VALU instead of the matrix cores
   bool ih_roles = true;          // NAGP_IH_ROLES: off when the value starts with '0'
   bool ih_tables = false;        // NAGP_IH_TABLES: on when the value starts with '1' (table form of stage 1b in ihgp_adf8_kernel)
-  int gain_form = 0;             // NAGP_GAIN_FORM: 0 = the plan's rule, 1 = solve, 2 = inv
+  bool ih_qform = true;          // NAGP_IH_QFORM: off when the value starts with '0' (every D runs the run-time form of Q / 2Q / v, nagp_qform.hpp)
+  int gain_form = 0;            // NAGP_GAIN_FORM: 0 = the plan's rule, 1 = solve, 2 = inv
   // numeric switches (0: not set, unless said otherwise)
   int chunks = 12;               // NAGP_CHUNKS (>= 1): smoother chunks per sweep
   int pipeline_slots = 0;        // NAGP_PIPELINE_SLOTS (>= 1; at most nc - 1 at the use)
@@ -117,6 +118,7 @@ static DevSwitches read_dev_switches() {
   const char* v;
   if ((v = env("NAGP_IH_ROLES"))) s.ih_roles = v[0] != '0';
   if ((v = env("NAGP_IH_TABLES"))) s.ih_tables = v[0] == '1';
+  if ((v = env("NAGP_IH_QFORM"))) s.ih_qform = v[0] != '0';
   if ((v = env("NAGP_GAIN_FORM"))) s.gain_form = !strcmp(v, "solve") ? 1 : (!strcmp(v, "inv") ? 2 : 0);
   if ((v = env("NAGP_CHUNKS"))) s.chunks = std::max(1, atoi(v));
   if ((v = env("NAGP_PIPELINE_SLOTS"))) s.pipeline_slots = std::max(1, atoi(v));
@@ -194,6 +196,7 @@ struct nagp_plan {
   int a8_gf = 0, a8_tpt = 1, a8_st = 0, kb_a8 = 16; size_t lds_a8 = 0;   // ADF sweep of the gf filter with role-specialised waves (gf_adf8_kernel)
   int seq_ih = 0;      // developer switch NAGP_IH_SEQ in force: the sequential kernels (general ADF filter, ihgp_scan_kernel) in every sweep instead of the affine scans
   int sp_ih8 = 0; size_t lds_sp8 = 0;   // the role-specialised 512-thread form of the same sweep (ihgp_adf8_kernel)
+  int qf_sp = 0;                        // ... its form of Q / 2Q / v on wave 0 (QForm, nagp_qform.hpp; the three-barrier schedule)
   hipStream_t stream = nullptr;
   // chunk-pipelined smoother (gf / giekf): while the sequential filter occupies one CU per problem, the parallel smoother kernels
   // of the chunks it has finished (rts_gain + the compose pass) run on `stream2` on the rest of the chip

@@ -752,7 +752,8 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
             if (need8() <= 156 * 1024) p->lds_sp8 = need8(); else p->kb_sp = kb1;
           }
         }
-        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SP, o->cub_dim, p->sp_ih8, dev.ih_tables, dev.stamps), p->sp_ih8 ? p->lds_sp8 : p->lds_sp));
+        p->qf_sp = (p->sp_ih8 && !dev.ih_tables && o->cub_dim <= 6) ? qform_pick(sh.D, !dev.ih_qform) : QF_RUNTIME;
+        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SP, o->cub_dim, p->sp_ih8, dev.ih_tables, dev.stamps, p->qf_sp), p->sp_ih8 ? p->lds_sp8 : p->lds_sp));
       }
     }
     // likModulatorPreCalcwn: the role-specialised sweep of nagp_momsq.hpp
@@ -763,12 +764,12 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
       if (needq() > 156 * 1024) p->hph_sq = 0;
       if (needq() <= 156 * 1024) {
         p->sq_ih = 1; p->lds_sq = needq();
-        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SQ, o->cub_dim, true, false, false), p->lds_sq));
+        PLAN_TRY(set_kernel(p->k.ih_adf, pick_ih_adf(FORM_SQ, o->cub_dim, true, false, false, QF_RUNTIME), p->lds_sq));
       }
     }
     p->seq_ih = dev.ih_seq && !p->sq_ih && !p->sp_ih && !p->src_f;
     if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);
-    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B), table form of stage 1b %d, sequential kernels in every sweep %d\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8, (int)(p->sp_ih8 && dev.ih_tables), p->seq_ih);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B), table form of stage 1b %d, Q/v form %s, sequential kernels in every sweep %d\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8, (int)(p->sp_ih8 && dev.ih_tables), qform_name(p->qf_sp), p->seq_ih);
     PLAN_TRY(set_kernel(p->k.ih_filter, pick_ih_filter(mom_variant(mc), p->src_f, sh.BS == 8), p->lds_ih));
     for (int mode = 0; mode < 2; ++mode) {      // the affine scans and the sequential scan use no dynamic LDS
       PLAN_TRY(set_kernel(p->k.aff_compose[mode], pick_aff_compose(mode, sh.BS), 0));

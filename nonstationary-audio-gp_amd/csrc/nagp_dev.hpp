@@ -9,6 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "nagp_explog.hpp"
 
 namespace nagp {
 
@@ -30,12 +31,15 @@ __device__ __forceinline__ double rsqrt_nr(double s) {
 // Gaussian weight of one sigma point: pdf = N(y; sam, sig2), q = (y - sam)/sig2, inv = 1/sig2 -- normpdf(y,mu,sigma),
 // (y-mu)./sigma2 and 1./sigma2 of likModulatorNMFPower.m:52-70 through ONE reciprocal square root instead of a square root
 // and three divisions (same values to ~2 ulp; the per-point phase of mom was half divisions)
+// LE0 (the three-barrier schedule of ihgp_adf8_kernel): exp_le0 of nagp_explog.hpp -- the exponent is <= 0 or NaN; the same bits
+template <bool LE0 = false>
 __device__ __forceinline__ void gauss_terms(double y, double sam, double sig2, double& pdf, double& q, double& inv) {
   const double rs = rsqrt_nr(sig2);
   inv = rs * rs;
   const double dy = y - sam;
   q = dy * inv;
-  pdf = exp(-0.5 * dy * q) * (rs * kInvSqrt2Pi);
+  const double ex = -0.5 * dy * q;
+  pdf = (LE0 ? exp_le0(ex) : exp(ex)) * (rs * kInvSqrt2Pi);
 }
 
 // ---------------------------------------------------------------------------------------------

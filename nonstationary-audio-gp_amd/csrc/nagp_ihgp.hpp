@@ -616,7 +616,11 @@ __device__ __forceinline__ void ih_window_pick(int mid, double r0, double r1, do
 // tables (wave 1) | B2 | ... as above with msr_reduce behind B5.  TAB = true (developer switch NAGP_IH_TABLES=1, the form of the
 // four-wave kernel, the in-build cross-check): B1 as for CD = 7; behind B2 the tables e / t1 / ve on wave 1 and q0 / s0 on workers 3 and
 // 4, one more barrier (B3), then the weights from those tables (msp_stage1b).
-template <int CD, bool TAB, bool STAMPS = false>
+// QF (nagp_qform.hpp; the three-barrier schedule only): the form of Q / 2Q / v on wave 0 -- K and PAD fixed in the instantiation the plan
+// picks by its D (qform_pick), or QF_RUNTIME, which serves every D (the remaining padded shapes; every shape under NAGP_IH_QFORM=0).
+// The serial loop of wave 1 exists once per link kind, picked ahead of it.  The weights, the link and Q / 2Q / v of this schedule are
+// bit-equal to the forms the other schedules run (gauss_terms, msp_link, msp_qv).
+template <int CD, bool TAB, bool STAMPS = false, int QF = QF_RUNTIME>
 __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
@@ -625,6 +629,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   constexpr bool NB1 = !TAB && CD <= 6;              // the three-barrier schedule (see above)
   constexpr bool ST_ON = !NB1 || STAMPS;             // NB1: the stamps are a build of their own (STAMPS), IH_STAMP / WK_STAMP expand to nothing otherwise
   static_assert(NB1 || !STAMPS, "STAMPS selects among the instantiations of the three-barrier schedule only");
+  static_assert(NB1 || QF == QF_RUNTIME, "QF selects among the instantiations of the three-barrier schedule only");
   const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG;
   const int64_t T = sh.T;
   const int pb = blockIdx.x;
@@ -697,7 +702,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
         msp_stage1b<CD>(xw, mc, sp, sn2a, ry[kk], ws);
       } else {
         WK_STAMP(2);                   // (wait at B2: wave 1's link tables; NB1: the serial waves' tail, head, Q / v and link tables)
-        msr_stage1b_direct<CD>(xw, sn2a, ry[kk]);
+        msr_stage1b_direct<CD, NB1>(xw, sn2a, ry[kk]);
       }
       WK_STAMP(3);
       lds_barrier();                 // B4
@@ -811,10 +816,11 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
 
   // NB1: the two serial waves run separate copies of the loop below (WT = 0, 1: the wave index is a constant of the copy), so that each
   // holds the registers of its own chain only -- wave 0 the W row and the operands of Q / 2Q / v, wave 1 the link chain's constants.
-  // Otherwise (WT = -1) one copy serves both, as before.
+  // Otherwise (WT = -1) one copy serves both, as before.  Wave 1's copy exists once per link kind (LK = 0, 1: msr_link_serial; LK = -1:
+  // the kind is read where it is used, msp_link).
   const int wave_rt = wave;
-  auto serial = [&](auto WV) __attribute__((always_inline)) {
-  constexpr int WT = decltype(WV)::value;
+  auto serial = [&](auto WV, auto LKV) __attribute__((always_inline)) {
+  constexpr int WT = decltype(WV)::value, LK = decltype(LKV)::value;
   const int wave = (WT < 0) ? wave_rt : WT;
   // wave 0, lane d < D owns sub-band block d; wave 1, lane j < N owns modulator block D + j
   const int lane = tid & 63;
@@ -921,10 +927,17 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   };
   if (stamp) st_a = __builtin_readcyclecounter();      // (the prologue's head stamps slots 6 / 7 as the loop's do)
   if (wave <= 1) head(ip.k_start, std::false_type{});
+  // NB1: what the two chains below need of the kernel's arguments is in vector registers from here on, like the look-up's constants
+  double ls_shift = mc.link_shift;
+  int qv_dlim = mc.D - (lane & 1);                   // msr_qv_serial, padded forms
+  const bool ls_on = tid - 64 * x.lw >= 0 && tid - 64 * x.lw < CD * mc.nd;      // this lane's part in the link tables (msp_link)
+  if constexpr (NB1) asm volatile("" : "+v"(ls_shift), "+v"(qv_dlim));
   // NB1: the cubature's inputs of a step straight behind its head, each from this wave's own fmu / HPH stores (msp_wave_fence)
   auto qv_or_link = [&]() __attribute__((always_inline)) {
     msp_wave_fence();
-    if (wave == 0) msr_qv_serial<CD>(xq, mc); else msp_link<CD>(x, mc);
+    if (wave == 0) msr_qv_serial<CD, QF>(xq, mc, qv_dlim);
+    else if constexpr (LK >= 0) msr_link_serial<CD, LK>(x, ls_on, ls_shift);
+    else msp_link<CD>(x, mc);
   };
   if constexpr (NB1) qv_or_link();
   // link tables of a step (the exp / log chain of the modulators' sigma-point coordinates, ~1 000 cycles on wave 1): evaluated BEHIND
@@ -1053,8 +1066,11 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
     for (int i = 0; i < 8; ++i) mc.stamps[i] += st[i];
   };
   if constexpr (NB1) {
-    if (wave == 0) serial(std::integral_constant<int, 0>{}); else serial(std::integral_constant<int, 1>{});
-  } else serial(std::integral_constant<int, -1>{});
+    using std::integral_constant;
+    if (wave == 0) serial(integral_constant<int, 0>{}, integral_constant<int, -1>{});
+    else if (mc.link_kind == 0) serial(integral_constant<int, 1>{}, integral_constant<int, 0>{});      // (link_eval: 0 softplus, else exp)
+    else serial(integral_constant<int, 1>{}, integral_constant<int, 1>{});
+  } else serial(std::integral_constant<int, -1>{}, std::integral_constant<int, -1>{});
 }
 
 // The role-specialised sweep for likModulatorPreCalcwn (experiments/likModulatorPreCalcwn.m:28-86; nagp_momsq.hpp): 512 threads, waves

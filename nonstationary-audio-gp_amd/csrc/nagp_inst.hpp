@@ -177,6 +177,16 @@
   P void nagp::ihgp_adf8_kernel<3, false, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, false, true> NAGP_SIG_IHA;  \
   P void nagp::ihgp_adf8_kernel<5, false, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, false, true> NAGP_SIG_IHA;
 
+// the three-barrier schedule with K and PAD of Q / 2Q / v fixed (nagp_qform.hpp), plain and stamped: one translation unit per form
+#define NAGP_LIST_IHA8K_S(P, ST, QF)                                                                                        \
+  P void nagp::ihgp_adf8_kernel<1, false, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, false, ST, QF> NAGP_SIG_IHA;  \
+  P void nagp::ihgp_adf8_kernel<3, false, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, false, ST, QF> NAGP_SIG_IHA;  \
+  P void nagp::ihgp_adf8_kernel<5, false, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, false, ST, QF> NAGP_SIG_IHA;
+#define NAGP_LIST_IHA8K(P, QF) NAGP_LIST_IHA8K_S(P, false, QF) NAGP_LIST_IHA8K_S(P, true, QF)
+#define NAGP_LIST_IHA8K4(P) NAGP_LIST_IHA8K(P, nagp::QF_K4)
+#define NAGP_LIST_IHA8K8(P) NAGP_LIST_IHA8K(P, nagp::QF_K8)
+#define NAGP_LIST_IHA8K16(P) NAGP_LIST_IHA8K(P, nagp::QF_K16P)
+
 // the role-specialised sweep for likModulatorPreCalcwn (nagp_momsq.hpp)
 #define NAGP_LIST_IHA8Q(P)                                                                                                 \
   P void nagp::ihgp_adf8sq_kernel<1> NAGP_SIG_IHA; P void nagp::ihgp_adf8sq_kernel<2> NAGP_SIG_IHA;                      \
@@ -195,4 +205,4 @@
 
 #define NAGP_LIST_ALL(P)                                                                                                   \
   NAGP_LIST_GF_ADF1(P) NAGP_LIST_GF_ADF2(P) NAGP_LIST_GF_ADF3(P) NAGP_LIST_GF_ADF4(P) NAGP_LIST_GF_ADF5(P)               \
-  NAGP_LIST_GF_SP12(P) NAGP_LIST_GF_SP34(P) NAGP_LIST_GF_SQ12(P) NAGP_LIST_GF_SQ34(P) NAGP_LIST_GF_REST(P) NAGP_LIST_SMOOTH(P) NAGP_LIST_SMOOTH8(P) NAGP_LIST_BIG(P) NAGP_LIST_GAINM(P) NAGP_LIST_GAINI(P) NAGP_LIST_EP(P) NAGP_LIST_EPS(P) NAGP_LIST_EPQ(P) NAGP_LIST_IH0(P) NAGP_LIST_IH8(P) NAGP_LIST_IH1(P) NAGP_LIST_IHA(P) NAGP_LIST_IHA8(P) NAGP_LIST_IHA8S(P) NAGP_LIST_IHA8Q(P) NAGP_LIST_GF_A81(P) NAGP_LIST_GF_A82(P) NAGP_LIST_GF_A83(P) NAGP_LIST_GF_CPL1(P) NAGP_LIST_GF_CPL2(P) NAGP_LIST_GF_CPL4(P) NAGP_LIST_GF_CPLW(P) NAGP_LIST_GAIN_CPL(P) NAGP_LIST_GF_WIN(P) NAGP_LIST_GF_WINC(P)
+  NAGP_LIST_GF_SP12(P) NAGP_LIST_GF_SP34(P) NAGP_LIST_GF_SQ12(P) NAGP_LIST_GF_SQ34(P) NAGP_LIST_GF_REST(P) NAGP_LIST_SMOOTH(P) NAGP_LIST_SMOOTH8(P) NAGP_LIST_BIG(P) NAGP_LIST_GAINM(P) NAGP_LIST_GAINI(P) NAGP_LIST_EP(P) NAGP_LIST_EPS(P) NAGP_LIST_EPQ(P) NAGP_LIST_IH0(P) NAGP_LIST_IH8(P) NAGP_LIST_IH1(P) NAGP_LIST_IHA(P) NAGP_LIST_IHA8(P) NAGP_LIST_IHA8S(P) NAGP_LIST_IHA8K4(P) NAGP_LIST_IHA8K8(P) NAGP_LIST_IHA8K16(P) NAGP_LIST_IHA8Q(P) NAGP_LIST_GF_A81(P) NAGP_LIST_GF_A82(P) NAGP_LIST_GF_A83(P) NAGP_LIST_GF_CPL1(P) NAGP_LIST_GF_CPL2(P) NAGP_LIST_GF_CPL4(P) NAGP_LIST_GF_CPLW(P) NAGP_LIST_GAIN_CPL(P) NAGP_LIST_GF_WIN(P) NAGP_LIST_GF_WINC(P)

@@ -20,6 +20,7 @@
 //   3   (caller's choice of lanes, after a barrier) fixed-order sum of the partials, outputs d lZ, d2 lZ, Z
 #pragma once
 #include "nagp_dev.hpp"
+#include "nagp_qform.hpp"
 
 namespace nagp {
 
@@ -35,8 +36,7 @@ constexpr int MSP_CS = 4 * MSP_NW * MSP_NST + 1;   // stride of c0 / c1 / c2: ev
 typedef const double __attribute__((address_space(3))) * msp_rp;   // LDS read pointer (32-bit, register resident)
 typedef double __attribute__((address_space(3))) * msp_wp;
 
-// terms per lane of the 4-lane groups that form Q and v (stage A): the next of 4, 8, 16 that covers D sub-bands
-__host__ __device__ inline int msp_qterms(int D) { return D <= 16 ? 4 : (D <= 32 ? 8 : 16); }
+// terms per lane of the 4-lane groups that form Q and v (stage A): the next of 4, 8, 16 that covers D sub-bands -- msp_qterms, nagp_qform.hpp
 
 // LDS workspace (offsets in doubles).  Tables lk | xg | xg2 | e | t1 | ve, MSP_TS entries each.
 struct MspLay { int lk, xg, xg2, e, t1, ve, one, zero, Q, Q2, v, q0, s0, c0, c1, c2, part, acc, marg, wwt, total; };
@@ -285,6 +285,24 @@ __device__ __forceinline__ void msp_link(const X& x, const MomCfg& c) {
     x.a_out[0] = lk; x.a_out[MSP_TS] = xg; x.a_out[2 * MSP_TS] = xg * xg - inv;   // :79
   }
 }
+// msp_link on serial wave 1 of the three-barrier schedule of ihgp_adf8_kernel: the same operations on the same operands (the same bits),
+// with the link's kind a constant of the loop's copy (LK), its shift and the lane's part in the tables (on = its lane index < CD nd) in
+// registers set ahead of the loop -- the chain reads no kernel argument, whose scalar load would wait for every LDS operation in flight --
+// and exp / log as written out in nagp_explog.hpp (the argument of the log is 1 + exp(.) >= 1).
+template <int CD, int LK, class X>
+__device__ __forceinline__ void msr_link_serial(const X& x, bool on, double shift) {
+  static_assert(LK == 0 || LK == 1, "softplus or exp");
+  if (on) {
+    const double mu = *x.a_mu, s2 = *x.a_s2;
+    double sg, inv;
+    if (s2 > 1e-150 && s2 < 1e150) { const double rs = rsqrt_nr(s2); sg = s2 * rs; inv = rs * rs; }
+    else { sg = sqrt(s2); inv = 1.0 / s2; }
+    const double xn = mu + sg * x.xdc;                                   // likModulatorNMFPower.m:34
+    const double lk = (LK == 0) ? log_ge1(1.0 + exp_any(xn - shift)) : exp_any(xn);      // link_eval
+    const double xg = (xn - mu) * inv;                                   // (xn - mu_g)./s2_g  (:72)
+    x.a_out[0] = lk; x.a_out[MSP_TS] = xg; x.a_out[2 * MSP_TS] = xg * xg - inv;   // :79
+  }
+}
 // stage A, Q / 2Q / v part (the three other waves): needs fmu / HPH of the SUB-BAND sites; no barrier
 template <int CD, class X>
 __device__ __forceinline__ void msp_qv(const X& x, const MomCfg& c) {
@@ -438,7 +456,8 @@ __device__ __forceinline__ void msp_stage1b_qs(const X& x, const MomCfg& c, cons
 // (broadcast reads), all issued before the first FMA; CD independent chains, no cross-lane operation.  Needs nothing of stage B: no
 // e / t1 / ve tables, no q0 / s0, no barrier between msp_qv's and this stage's.  Every term is positive for W >= 0, lk > 0 (no
 // cancellation, where the centre + deviation form of msp_stage1b_qs adds terms of both signs).  Lanes without a point read the zero word.
-template <int CD, class X>
+// LE0: the weights' exp as exp_le0 (nagp_explog.hpp; the three-barrier schedule of ihgp_adf8_kernel)
+template <int CD, bool LE0 = false, class X>
 __device__ __forceinline__ void msr_stage1b_direct(const X& x, double sn2a, double y) {
   if (__builtin_amdgcn_readfirstlane(x.p_any[0]) == 0) return;   // wave-uniform skip
   constexpr int NO = CD * (CD - 1) / 2;
@@ -476,7 +495,7 @@ __device__ __forceinline__ void msr_stage1b_direct(const X& x, double sn2a, doub
   for (int j = CD - 1; j >= 0; --j) { if (j & 1) b1 = fma(lk[j], t[j], b1); else b0 = fma(lk[j], t[j], b0); }
   const double sa2 = b0 + b1;
   double pdf, q, inv;
-  gauss_terms(y, sam, sn2a + sa2, pdf, q, inv);
+  gauss_terms<LE0>(y, sam, sn2a + sa2, pdf, q, inv);
   const double w0 = x.p_wn[0] * pdf;
   if (x.p_ok[0]) {
     x.p_c[0][0] = w0;
@@ -850,15 +869,56 @@ __device__ __forceinline__ void msr_setup_Q(MsrQ<CD>& x, const MomCfg& c, const 
     x.src = (msp_rp)(((kind == 1) ? HPH : fmu) + h);
   }
 }
+typedef double msr_d2 __attribute__((ext_vector_type(2)));      // two terms of msr_qsum2 as one paired LDS read delivers them
 // PAD (4K > D): the operands beyond the sub-bands -- the modulators' entries, which wave 1 may be writing at this moment, and the zero
 // padding -- are replaced by zero before they are used (msp_qv multiplies them by a zero product: the same sum for finite entries)
-template <int K, bool PAD>
+// TIE = false (the forms with K and PAD fixed, msr_qv_serial): the same groups, reads and order of additions, with the pins on the
+// two-term tuples the paired reads deliver instead of on single terms.  A pin on one double of a four-register read result makes the
+// compiler copy it out of the tuple (a 64-bit register copy per term ahead of its FMA); a pin on the tuple leaves it where it is.
+template <int K, bool PAD, bool TIE = true>
 __device__ __forceinline__ void msr_qsum2(msp_rp ww, msp_rp src, int dlim, double& p, double& r) {
   // groups of MSR_QG terms, the reads of the next group in flight while a group multiplies: one LDS latency, then the rate of the reads,
   // with 2 MSR_QG terms in registers at a time (the serial role has few registers to spare beside its state).  The pins fix that order:
   // a group's reads are issued behind the FMAs of the group two ahead of it.
   constexpr int G = MSR_QG, NGR = 2 * K / G;
   double acc[4] = {0.0, 0.0, 0.0, 0.0};              // chain 2s + (q & 1): the even and the odd q of partial s, q ascending
+  if constexpr (!TIE) {
+    static_assert(G % 2 == 0 && K % 2 == 0, "terms t, t + 1 of a pair belong to one partial");
+    constexpr int H = G / 2;
+    msr_d2 w2[NGR][H], v2[NGR][H];
+    auto reads = [&](int g) __attribute__((always_inline)) {
+#pragma unroll
+      for (int u = 0; u < H; ++u) {
+        const int t = G * g + 2 * u, o = 2 * (t / K) + 4 * (t % K);
+        w2[g][u] = msr_d2{ww[64 * t], ww[64 * (t + 1)]};
+        v2[g][u] = msr_d2{src[o], src[o + 4]};
+      }
+    };
+#pragma unroll
+    for (int g = 0; g < 2 && g < NGR; ++g) reads(g);
+#pragma unroll
+    for (int g = 0; g < NGR; ++g) {
+#pragma unroll
+      for (int u = 0; u < H; ++u) asm volatile("" : "+v"(w2[g][u]), "+v"(v2[g][u]));
+#pragma unroll
+      for (int u = 0; u < H; ++u) {
+        const int t = G * g + 2 * u, s = t / K, o = 2 * s + 4 * (t % K);
+        double va = v2[g][u].x, vb = v2[g][u].y;
+        if (PAD) { va = (o < dlim) ? va : 0.0; vb = (o + 4 < dlim) ? vb : 0.0; }
+        const int ca = 2 * s + (t % K & 1), cb = 2 * s + ((t + 1) % K & 1);
+        acc[ca] = fma(w2[g][u].x, va, acc[ca]);
+        acc[cb] = fma(w2[g][u].y, vb, acc[cb]);
+      }
+      if (g + 2 < NGR) {
+        // (the chains of the second partial are pinned once they hold a term: a pinned zero would be a register set for nothing)
+        if ((G * g + G - 1) / K == 0) asm volatile("" : "+v"(ww), "+v"(src), "+v"(acc[0]), "+v"(acc[1]));
+        else asm volatile("" : "+v"(ww), "+v"(src), "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
+        reads(g + 2);
+      }
+    }
+    p = acc[0] + acc[1]; r = acc[2] + acc[3];
+    return;
+  }
   double w[NGR][G], v[NGR][G];
 #pragma unroll
   for (int g = 0; g < 2 && g < NGR; ++g)
@@ -884,17 +944,25 @@ __device__ __forceinline__ void msr_qsum2(msp_rp ww, msp_rp src, int dlim, doubl
 }
 // Q / 2Q / v of a step on wave 0, straight behind the head that wrote the sub-bands' fmu / HPH (the same lanes' stores: msp_wave_fence
 // between them); no barrier.  Every lane of the wave executes it.
-template <int CD>
-__device__ __forceinline__ void msr_qv_serial(const MsrQ<CD>& x, const MomCfg& c) {
+// QF (nagp_qform.hpp): K and PAD are constants of the instantiation -- one path, no branch nest walked every step, and the operands stay
+// in the registers their reads delivered them in (msr_qsum2, TIE = false); QF_RUNTIME: the six paths behind the run-time nest, any D.
+// dlim (PAD only) is D - (lane & 1), formed by the caller ahead of its loop.
+template <int CD, int QF = QF_RUNTIME>
+__device__ __forceinline__ void msr_qv_serial(const MsrQ<CD>& x, const MomCfg& c, int dlim_fixed = 0) {
   const int lane = threadIdx.x & 63, kind = msr_qkind<CD>(lane >> 1);
   if (kind) {
-    const int K = __builtin_amdgcn_readfirstlane(msp_qterms(c.D));
-    const bool pad = __builtin_amdgcn_readfirstlane(4 * K != c.D ? 1 : 0) != 0;
-    const int dlim = c.D - (lane & 1);               // operand 2s + 4q of this lane is a sub-band's while 2s + 4q < dlim
     double p = 0.0, r = 0.0;
-    if (K == 4) { if (pad) msr_qsum2<4, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<4, false>(x.ww, x.src, dlim, p, r); }
-    else if (K == 8) { if (pad) msr_qsum2<8, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<8, false>(x.ww, x.src, dlim, p, r); }
-    else { if (pad) msr_qsum2<16, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<16, false>(x.ww, x.src, dlim, p, r); }
+    if constexpr (QF == QF_K4) msr_qsum2<4, false, false>(x.ww, x.src, 0, p, r);
+    else if constexpr (QF == QF_K8) msr_qsum2<8, false, false>(x.ww, x.src, 0, p, r);
+    else if constexpr (QF == QF_K16P) msr_qsum2<16, true, false>(x.ww, x.src, dlim_fixed, p, r);
+    else {
+      const int K = __builtin_amdgcn_readfirstlane(msp_qterms(c.D));
+      const bool pad = __builtin_amdgcn_readfirstlane(4 * K != c.D ? 1 : 0) != 0;
+      const int dlim = c.D - (lane & 1);             // operand 2s + 4q of this lane is a sub-band's while 2s + 4q < dlim
+      if (K == 4) { if (pad) msr_qsum2<4, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<4, false>(x.ww, x.src, dlim, p, r); }
+      else if (K == 8) { if (pad) msr_qsum2<8, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<8, false>(x.ww, x.src, dlim, p, r); }
+      else { if (pad) msr_qsum2<16, true>(x.ww, x.src, dlim, p, r); else msr_qsum2<16, false>(x.ww, x.src, dlim, p, r); }
+    }
     p += dpp_mov<0xB1>(p);                           // lane 0 of the pair: p0 + p1
     r += dpp_mov<0xB1>(r);                           //                     p2 + p3
     const double a = p + r;
