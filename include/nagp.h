@@ -501,6 +501,64 @@ void nagp_nmf_temp_destroy(nagp_nmf_temp* handle);
  * its device batches). */
 int nagp_nmf_temp_timings(double* ms /* 1 */);
 
+/* The NMF whose activations are exp(mux + a squared-exponential GP) in its basis-function form -- experiments/nmf/tnmf.m, tnmf_inf.m and
+ * experiments/toolsGP/fitSEGP_BF.m minimise the three objectives below by conjugate gradients -- and the primitive they share,
+ * basis2SEGP.m:21-28, per column with its own lenx, varx:
+ *     tau = ceil(lenx / sqrt(2) * tol),   bh = sqrt(varx sqrt(2) / (lenx sqrt(pi))),   bas(s) = bh exp(-1 / lenx^2 * s^2),  s = -tau .. tau,
+ *     conv(Z)(t) = sum_{s = -tau .. tau} bas(s) Z(t - s),   Z = 0 outside 1 .. T      (conv(Z, bas, 'same'), 2 tau + 1 odd).
+ * Any tau >= 0, also 2 tau + 1 > T; no tap is dropped however small it is.  The taps are built on the host, once per handle (per call of
+ * the one-shot forms).  Every output adds its taps in ascending s, by a direct sum (there is no FFT form): no floating-point atomics and
+ * no order that depends on the grid, so a column's result is the same to the bit alone, in a batch, with or without dObj, through the
+ * one-shot or the resident form, and however the call is cut into device batches.  All matrices column-major.
+ *   nagp_sebf_conv (basis2SEGP.m): Y(:, q) = conv(Z(:, q)) for n_cols columns of T samples, lenx, varx n_cols each.
+ *   nagp_sebf_fit_* (getObj_fitSE_basis_func.m:25-43), n_problems columns, each with its own target x (T), lenx, varx:
+ *     xHat = conv(z), dx = xHat - x, obj = (1/2 sum dx^2 + 1/2 sum z^2) / T, dobj = (conv(dx) + z) / T.
+ *   nagp_tnmf_* (getObj_nmf_log_norm.m:31-83 with W = NULL, the learning form: x = [X(:); log W(:)], T K + K D entries per problem;
+ *   getObj_nmf_log_norm_inf.m:32-74 with W given, K x D per problem, used as it is and NOT renormalised: x = X(:), T K entries), for a
+ *   batch of problems that share A (T x D), vary, lenx, mux, varx (K each) and tol:
+ *     H(:, k) = exp(conv(X(:, k)) + mux(k)),   learning form: W = exp(logW), W = diag(1 ./ sum(W,2)) W,   Ahat = H W + vary,
+ *     obj1 = sum(A ./ Ahat + log(Ahat)),   dA = (Ahat - A) ./ Ahat.^2,   dX(:, k) = conv((dA W')(:, k) .* H(:, k)),
+ *     learning form: dW = H' dA, dWW = dW .* W, dlogw = dWW - diag(sum(dWW,2)) W,
+ *     obj = (obj1 + 1/2 sum X^2) / T,   dobj = [dX(:) + X(:); dlogw(:)] / T.
+ *   Between the two convolutions the row arithmetic is that of nagp_nmf_temp_obj with NAGP_NMFT_NONE on logH = conv(X) + mux (the same
+ *   kernels, on the device-resident array); the division by T is applied to (dA W') .* H before the second convolution and to X, and to
+ *   obj1 and 1/2 sum X^2 each.  1/2 sum X^2, sum dx^2 and sum z^2 are formed in an order that depends on the shape alone.
+ * vary = NULL: zeros.  dObj = NULL: the objective only (the same Obj bits).  The resident forms keep the taps, the targets (fit), A,
+ * vary, a given W and every intermediate on the device: *_eval moves x (z) in and Obj, dObj out.  *_obj is create + eval + destroy.
+ * All of the following is decided on the host before any device call.
+ * NAGP_EINVAL: a NULL handle, Z, Y, z, x, A, Obj, lenx, varx or mux; n_cols, n_problems, T, D or K < 1; lenx not finite or <= 0; varx not
+ *   finite or < 0; tol not finite or < 0; mux not finite; A, vary or W not finite or negative; an all-zero row of a given W.
+ * NAGP_EUNSUPPORTED: tau > 2^30 - 1 (2 tau + 1 taps are counted in an int32); D > 64 or K > 16 (the limits of nagp_nmf_temp_obj, whose
+ *   row kernels run here); one column or problem beyond the budget of the per-evaluation buffers, 1 GiB: a column of nagp_sebf_conv takes
+ *   16 T bytes of them, a problem of nagp_sebf_fit 8 (3 T + 1), a problem of nagp_tnmf, with nx = T K (+ K D in the learning form),
+ *   8 (4 nx + ceil(T / 256) ((K D in the learning form) + 1) + 1).  A batch that does not fit is evaluated in device batches of as many
+ *   as do.  (The taps, 8 (2 tau + 1) bytes per column, the targets and A, vary, W are outside it.)
+ * x, z, Z and the targets of the fit are not examined: a result that is not finite is returned as it is. */
+int nagp_sebf_conv(int32_t n_cols, int64_t T, const double* Z /* T x n_cols */, const double* lenx, const double* varx /* n_cols each */,
+                   double tol, double* Y /* T x n_cols */, int32_t device);
+typedef struct nagp_sebf_fit nagp_sebf_fit; /* opaque */
+int nagp_sebf_fit_obj(int32_t n_problems, int64_t T, const double* z /* T x n_problems */, const double* x /* T x n_problems: the targets */,
+                      const double* lenx, const double* varx /* n_problems each */, double tol,
+                      double* Obj /* n_problems */, double* dObj /* as z, or NULL = objective only */, int32_t device);
+int nagp_sebf_fit_create(nagp_sebf_fit** handle, int32_t n_problems, int64_t T, const double* x, const double* lenx, const double* varx,
+                         double tol, int32_t device);
+int nagp_sebf_fit_eval(nagp_sebf_fit* handle, const double* z, double* Obj, double* dObj /* or NULL */);
+void nagp_sebf_fit_destroy(nagp_sebf_fit* handle);
+typedef struct nagp_tnmf nagp_tnmf; /* opaque */
+int nagp_tnmf_obj(int32_t n_problems, int64_t T, int32_t D, int32_t K,
+                  const double* x /* n_problems x (T K + K D), or x (T K) with W */,
+                  const double* A /* T x D, shared */, const double* vary /* T x D shared, or NULL = zeros */,
+                  const double* W /* NULL: learning form; else K x D per problem: inference form */,
+                  const double* lenx, const double* mux, const double* varx /* K each, shared */, double tol,
+                  double* Obj /* n_problems */, double* dObj /* as x, or NULL = objective only */, int32_t device);
+int nagp_tnmf_create(nagp_tnmf** handle, int32_t n_problems, int64_t T, int32_t D, int32_t K, const double* A, const double* vary,
+                     const double* W, const double* lenx, const double* mux, const double* varx, double tol, int32_t device);
+int nagp_tnmf_eval(nagp_tnmf* handle, const double* x, double* Obj, double* dObj /* or NULL */);
+void nagp_tnmf_destroy(nagp_tnmf* handle);
+/* Device time of the last nagp_tnmf_eval, nagp_sebf_fit_eval (or their one-shot forms) or nagp_sebf_conv on this thread, in ms (HIP
+ * events, summed over its device batches): the forward convolution, the rows (the reduction of the fit), the adjoint convolution. */
+int nagp_tnmf_timings(double* ms /* 3: forward conv, rows, adjoint conv */);
+
 /* What the drivers do next with Eft / Varft (demo_toy_modulators_nmf.m:119-158, the same block in the other
  * demos): the reconstructed signal sig = sum_d (W link(g))_d z_d and the modulator amplitudes link(g_n) under the independent
  * posterior marginals z_d ~ N(Eft_d, Varft_d), g_n ~ N(Eft_{D+n}, Varft_{D+n}) of every time step:

@@ -44,6 +44,14 @@
  *                                    K x D x P -- the inference form, x (T K) x P; muinf, varinf, lam: K entries or []: varinf empty = no prior,
  *                                    muinf empty = the truncated-Gaussian chain, none empty = the inverse-gamma chain (nmf.m:119-131);
  *                                    Obj P x 1, dObj as x (formed only with two outputs)
+ *   [Obj, dObj] = nagp_mex('tnmf_obj', x, A, vary, W, lenx, mux, varx, tol [,device])                          nagp_tnmf_obj
+ *                                    A T x D; vary T x D or [] (zeros); W [] -- the learning form, x (T K + K D) x P -- or K x D (shared) or
+ *                                    K x D x P -- the inference form, x (T K) x P; lenx, mux, varx: K entries; tol a scalar;
+ *                                    Obj P x 1, dObj as x (formed only with two outputs)
+ *   [Obj, dObj] = nagp_mex('sebf_fit_obj', z, x, lenx, varx, tol [,device])                                    nagp_sebf_fit_obj
+ *                                    z and the targets x T x P; lenx, varx: scalars or P entries; Obj P x 1, dObj T x P (with two outputs)
+ *   Y = nagp_mex('sebf_conv', Z, lenx, varx, tol [,device])                                                    nagp_sebf_conv
+ *                                    Z T x K; lenx, varx: scalars or K entries; Y T x K
  *   [Esig,Vsig,Eft_mod,Varft_mod] = nagp_mex('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])
  *                                                                                                              nagp_reconstruct
  *   [Esig,Vsig,Esrc,Vsrc,Eenv,Eft_mod,Varft_mod] = nagp_mex('reconstruct_sources', Eft, Varft, Wnmf, ropts)    nagp_reconstruct_sources
@@ -443,6 +451,96 @@ static void cmd_nmf_temp_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray*
   for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
 }
 
+static void cmd_tnmf_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('tnmf_obj', x, A, vary, W, lenx, mux, varx, tol [,device]) -> [Obj, dObj]: the objectives of experiments/nmf/getObj_nmf_log_norm.m (W = [])
+     and getObj_nmf_log_norm_inf.m for P problems; dObj only when asked for */
+  size_t nx, na, nv, nw, n3[3], nt, P, T, D, K, X, q; const double *x, *A, *vary, *W, *par[3], *tol; double* wp = NULL; int32_t dev; int i, k;
+  mxArray* o[2] = {NULL, NULL};
+  static const char* names[3] = {"lenx", "mux", "varx"};
+  if (nrhs < 9 || nrhs > 10 || nlhs > 2) mexErrMsgIdAndTxt("nagp:arg", "usage: [Obj,dObj] = nagp_mex('tnmf_obj',x,A,vary,W,lenx,mux,varx,tol[,device])");
+  A = dvec(prhs[2], "A", &na); T = A ? mxGetM(prhs[2]) : 0;
+  if (!A || !T || na % T != 0) mexErrMsgIdAndTxt("nagp:arg", "A must be T x D");
+  D = na / T;
+  vary = dvec(prhs[3], "vary", &nv);
+  if (vary && nv != na) mexErrMsgIdAndTxt("nagp:arg", "vary must be T x D or []");
+  x = dvec(prhs[1], "x", &nx); X = x ? mxGetM(prhs[1]) : 0;
+  if (!x || !X || nx % X != 0) mexErrMsgIdAndTxt("nagp:arg", "x must hold one column per problem");
+  P = nx / X;
+  W = dvec(prhs[4], "W", &nw);
+  if (W) {
+    K = mxGetM(prhs[4]);
+    if (!K || (nw != K * D && nw != K * D * P)) mexErrMsgIdAndTxt("nagp:arg", "W must be K x D or K x D x P");
+    if (X != T * K) mexErrMsgIdAndTxt("nagp:arg", "x must be (T K) x P with a given W");
+  } else {
+    K = X / (T + D);
+    if (!K || K * (T + D) != X) mexErrMsgIdAndTxt("nagp:arg", "x must be (T K + K D) x P without W");
+  }
+  for (k = 0; k < 3; ++k) {
+    par[k] = dvec(prhs[5 + k], names[k], &n3[k]);
+    if (!par[k] || n3[k] != K) mexErrMsgIdAndTxt("nagp:arg", "%s must hold K entries", names[k]);
+  }
+  tol = dvec(prhs[8], "tol", &nt);
+  if (!tol || nt != 1) mexErrMsgIdAndTxt("nagp:arg", "tol must be a scalar");
+  dev = nrhs > 9 ? (int32_t)mxGetScalar(prhs[9]) : 0;
+  if (W && nw == K * D && P > 1) {                         /* a shared W: one copy per problem */
+    wp = (double*)mxCalloc(K * D * P, sizeof *wp);
+    for (q = 0; q < P; ++q) memcpy(wp + q * K * D, W, K * D * sizeof *wp);
+  }
+  o[0] = mxCreateDoubleMatrix((mwSize)P, 1, mxREAL);
+  if (nlhs > 1) o[1] = mxCreateDoubleMatrix((mwSize)X, (mwSize)P, mxREAL);
+  fail_if(nagp_tnmf_obj((int32_t)P, (int64_t)T, (int32_t)D, (int32_t)K, x, A, vary, wp ? wp : W, par[0], par[1], par[2], tol[0], mxGetPr(o[0]),
+                        o[1] ? mxGetPr(o[1]) : NULL, dev));
+  if (wp) mxFree(wp);
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
+}
+
+/* lenx, varx of the basis: a scalar or one entry per column -> n entries (mxCalloc) */
+static double* per_column(const mxArray* a, const char* what, size_t n) {
+  size_t m, q; const double* v = dvec(a, what, &m); double* out;
+  if (!v || (m != 1 && m != n)) mexErrMsgIdAndTxt("nagp:arg", "%s must be a scalar or hold one entry per column", what);
+  out = (double*)mxCalloc(n, sizeof *out);
+  for (q = 0; q < n; ++q) out[q] = v[m == 1 ? 0 : q];
+  return out;
+}
+
+static void cmd_sebf_fit_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('sebf_fit_obj', z, x, lenx, varx, tol [,device]) -> [Obj, dObj]: experiments/toolsGP/getObj_fitSE_basis_func.m for P columns */
+  size_t nz, nx, nt, T, P; const double *z, *x, *tol; double *len, *vx; int32_t dev; int i;
+  mxArray* o[2] = {NULL, NULL};
+  if (nrhs < 6 || nrhs > 7 || nlhs > 2) mexErrMsgIdAndTxt("nagp:arg", "usage: [Obj,dObj] = nagp_mex('sebf_fit_obj',z,x,lenx,varx,tol[,device])");
+  z = dvec(prhs[1], "z", &nz); T = z ? mxGetM(prhs[1]) : 0;
+  if (!z || !T || nz % T != 0) mexErrMsgIdAndTxt("nagp:arg", "z must be T x P");
+  P = nz / T;
+  x = dvec(prhs[2], "x", &nx);
+  if (!x || nx != nz || mxGetM(prhs[2]) != T) mexErrMsgIdAndTxt("nagp:arg", "x must be T x P as z");
+  len = per_column(prhs[3], "lenx", P); vx = per_column(prhs[4], "varx", P);
+  tol = dvec(prhs[5], "tol", &nt);
+  if (!tol || nt != 1) mexErrMsgIdAndTxt("nagp:arg", "tol must be a scalar");
+  dev = nrhs > 6 ? (int32_t)mxGetScalar(prhs[6]) : 0;
+  o[0] = mxCreateDoubleMatrix((mwSize)P, 1, mxREAL);
+  if (nlhs > 1) o[1] = mxCreateDoubleMatrix((mwSize)T, (mwSize)P, mxREAL);
+  fail_if(nagp_sebf_fit_obj((int32_t)P, (int64_t)T, z, x, len, vx, tol[0], mxGetPr(o[0]), o[1] ? mxGetPr(o[1]) : NULL, dev));
+  mxFree(len); mxFree(vx);
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
+}
+
+static void cmd_sebf_conv(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('sebf_conv', Z, lenx, varx, tol [,device]) -> Y: experiments/toolsGP/basis2SEGP.m */
+  size_t nz, nt, T, K; const double *Z, *tol; double *len, *vx; int32_t dev; mxArray* y;
+  if (nrhs < 5 || nrhs > 6 || nlhs > 1) mexErrMsgIdAndTxt("nagp:arg", "usage: Y = nagp_mex('sebf_conv',Z,lenx,varx,tol[,device])");
+  Z = dvec(prhs[1], "Z", &nz); T = Z ? mxGetM(prhs[1]) : 0;
+  if (!Z || !T || nz % T != 0) mexErrMsgIdAndTxt("nagp:arg", "Z must be T x K");
+  K = nz / T;
+  len = per_column(prhs[2], "lenx", K); vx = per_column(prhs[3], "varx", K);
+  tol = dvec(prhs[4], "tol", &nt);
+  if (!tol || nt != 1) mexErrMsgIdAndTxt("nagp:arg", "tol must be a scalar");
+  dev = nrhs > 5 ? (int32_t)mxGetScalar(prhs[5]) : 0;
+  y = mxCreateDoubleMatrix((mwSize)T, (mwSize)K, mxREAL);
+  fail_if(nagp_sebf_conv((int32_t)K, (int64_t)T, Z, len, vx, tol[0], mxGetPr(y), dev));
+  mxFree(len); mxFree(vx);
+  plhs[0] = y;
+}
+
 static void cmd_reconstruct(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('reconstruct', Eft, Varft, Wnmf, link_kind, link_shift, gh_x, gh_w, n_samples, seed [,device])  (demo_toy_modulators_nmf.m:119-158) */
   size_t n, nv, ngx, ngw, D, N, M, T; const double *E, *V, *W, *gx, *gw; int32_t dev; mxArray* o[4]; int i;
@@ -556,6 +654,9 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "segp_obj")) cmd_segp_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "gppad_obj")) cmd_gppad_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "nmf_temp_obj")) cmd_nmf_temp_obj(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "tnmf_obj")) cmd_tnmf_obj(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "sebf_fit_obj")) cmd_sebf_fit_obj(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "sebf_conv")) cmd_sebf_conv(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct")) cmd_reconstruct(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "reconstruct_sources")) cmd_reconstruct_sources(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "batch")) cmd_batch(nlhs, plhs, nrhs, prhs);

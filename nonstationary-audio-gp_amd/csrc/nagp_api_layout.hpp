@@ -76,4 +76,18 @@ struct NmftBat { size_t x, dg, pw, po, ob, total; };
 inline NmftBat nmft_bat(size_t nx, size_t D, size_t K, bool learn, size_t nwg, size_t n_po, size_t nb) {
   Layout l; return {l.take(nb * nx), l.take(nb * nx), l.take(learn ? nb * nwg * K * D : 0), l.take(nb * nwg * n_po), l.take(nb), l.total(2)};
 }
+// the squared-exponential basis of a nagp_sebf_fit / nagp_tnmf handle or a nagp_sebf_conv call, resident: taps | first tap of every tap
+// column (int64) | tau (int) | mux | the targets of the fit
+struct SebfRes { size_t tp, of, ta, c, e, total; };
+inline SebfRes sebf_res(size_t n_taps, size_t n_tc, size_t n_targets) {
+  Layout l; return {l.take(n_taps), l.take(n_tc), l.take(n_tc / 2 + 1), l.take(n_tc), l.take(n_targets), l.total(2)};
+}
+// per device batch.  nagp_sebf_conv: Z | Y;  nagp_sebf_fit: z | dx | dObj | Obj;  nagp_tnmf: x | logH (and log W) | the row kernel's gradient |
+// dObj | pw (learning form) | po | Obj
+struct SebfBat { size_t x, lh, dg, out, pw, po, ob, total; };
+inline SebfBat sebf_conv_bat(size_t T, size_t nb) { Layout l; return {l.take(nb * T), 0, 0, l.take(nb * T), 0, 0, 0, l.total(2)}; }
+inline SebfBat sebf_fit_bat(size_t T, size_t nb) { Layout l; return {l.take(nb * T), l.take(nb * T), 0, l.take(nb * T), 0, 0, l.take(nb), l.total(2)}; }
+inline SebfBat tnmf_bat(size_t nx, size_t D, size_t K, bool learn, size_t nwg, size_t nb) {
+  Layout l; return {l.take(nb * nx), l.take(nb * nx), l.take(nb * nx), l.take(nb * nx), l.take(learn ? nb * nwg * K * D : 0), l.take(nb * nwg), l.take(nb), l.total(2)};
+}
 }  // namespace nagp

@@ -82,7 +82,9 @@ EXPORTS = ['nagp_version', 'nagp_device_count', 'nagp_strerror', 'nagp_last_erro
            'nagp_giekf_nlml_grad', 'nagp_plan_set_windows', 'nagp_plan_window_stats', 'nagp_window_partition', 'nagp_reconstruct_sources', 'nagp_fastfb_sample',
            'nagp_slowfb_run', 'nagp_slowfb_timings', 'nagp_nmf_fp', 'nagp_nmf_timings', 'nagp_pstft_obj', 'nagp_pstft_timings',
            'nagp_segp_obj', 'nagp_segp_timings', 'nagp_gppad_obj', 'nagp_gppad_create', 'nagp_gppad_eval', 'nagp_gppad_destroy', 'nagp_gppad_timings',
-           'nagp_nmf_temp_obj', 'nagp_nmf_temp_create', 'nagp_nmf_temp_eval', 'nagp_nmf_temp_destroy', 'nagp_nmf_temp_timings']
+           'nagp_nmf_temp_obj', 'nagp_nmf_temp_create', 'nagp_nmf_temp_eval', 'nagp_nmf_temp_destroy', 'nagp_nmf_temp_timings',
+           'nagp_sebf_conv', 'nagp_sebf_fit_obj', 'nagp_sebf_fit_create', 'nagp_sebf_fit_eval', 'nagp_sebf_fit_destroy',
+           'nagp_tnmf_obj', 'nagp_tnmf_create', 'nagp_tnmf_eval', 'nagp_tnmf_destroy', 'nagp_tnmf_timings']
 NMFT_NONE, NMFT_TG, NMFT_IG = 0, 1, 2
 
 
@@ -247,6 +249,17 @@ def lib():
     L.nagp_nmf_temp_eval.argtypes = [C.c_void_p, c_dp, c_dp, c_dp]; L.nagp_nmf_temp_eval.restype = C.c_int
     L.nagp_nmf_temp_destroy.argtypes = [C.c_void_p]; L.nagp_nmf_temp_destroy.restype = None
     L.nagp_nmf_temp_timings.argtypes = [c_dp]; L.nagp_nmf_temp_timings.restype = C.c_int
+    L.nagp_sebf_conv.argtypes = [C.c_int32, C.c_int64, c_dp, c_dp, c_dp, C.c_double, c_dp, C.c_int32]; L.nagp_sebf_conv.restype = C.c_int
+    L.nagp_sebf_fit_obj.argtypes = [C.c_int32, C.c_int64, c_dp, c_dp, c_dp, c_dp, C.c_double, c_dp, c_dp, C.c_int32]; L.nagp_sebf_fit_obj.restype = C.c_int
+    L.nagp_sebf_fit_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, c_dp, c_dp, c_dp, C.c_double, C.c_int32]; L.nagp_sebf_fit_create.restype = C.c_int
+    L.nagp_sebf_fit_eval.argtypes = [C.c_void_p, c_dp, c_dp, c_dp]; L.nagp_sebf_fit_eval.restype = C.c_int
+    L.nagp_sebf_fit_destroy.argtypes = [C.c_void_p]; L.nagp_sebf_fit_destroy.restype = None
+    tnmf_data = [c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_double]                       # A, vary, W, lenx, mux, varx, tol
+    L.nagp_tnmf_obj.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, c_dp] + tnmf_data + [c_dp, c_dp, C.c_int32]; L.nagp_tnmf_obj.restype = C.c_int
+    L.nagp_tnmf_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int32, C.c_int32] + tnmf_data + [C.c_int32]; L.nagp_tnmf_create.restype = C.c_int
+    L.nagp_tnmf_eval.argtypes = [C.c_void_p, c_dp, c_dp, c_dp]; L.nagp_tnmf_eval.restype = C.c_int
+    L.nagp_tnmf_destroy.argtypes = [C.c_void_p]; L.nagp_tnmf_destroy.restype = None
+    L.nagp_tnmf_timings.argtypes = [c_dp]; L.nagp_tnmf_timings.restype = C.c_int
     L.nagp_giekf_nlml_grad.argtypes = [C.c_int32, C.POINTER(Model), C.POINTER(c_dp), C.c_int64, C.c_int32, C.POINTER(c_dp), C.POINTER(c_dp), C.POINTER(c_dp),
                                        c_dp, c_ip, c_ip, c_ip, c_dp, c_dp, C.c_int32]
     L.nagp_giekf_nlml_grad.restype = C.c_int

@@ -14,8 +14,9 @@ put the float64 restatement through the same drivers.
 The priors are selected as nmf.m:119-131 does: varinf empty (None or []) -- none; muinf empty -- the truncated-Gaussian chain (varinf,
 lam); none empty -- the inverse-gamma chain (muinf, varinf, lam).
 
-Not built, and refused by name: the squared-exponential basis-function variant (tnmf.m, tnmf_inf.m on getObj_nmf_log_norm*.m and
-fitSEGP_BF.m) and the samplers randnmf.m / randtnmf.m.
+The squared-exponential basis-function variant (tnmf.m, tnmf_inf.m on getObj_nmf_log_norm*.m and fitSEGP_BF.m) and the sampler
+randtnmf.m live in nagp.tnmf; the names tnmf, tnmf_inf and randtnmf of THIS module still refuse and name the reference file.  Not built:
+the sampler randnmf.m.
 """
 import math
 
