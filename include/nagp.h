@@ -446,6 +446,46 @@ void nagp_gppad_destroy(nagp_gppad* handle);
  * batches). */
 int nagp_gppad_timings(double* ms /* 1 */);
 
+/* The objective that experiments/gppad/Cascade/MAPGPCasFast.m minimises -- the joint fine tuning of a cascade of M modulators,
+ * GPPAD(Y,[len1;...;lenM]): Cascade/GetObjCasGPFAST.m:19-50 with its gradient, for a batch of cascades.  One cascade is X (Tx x M, the
+ * .m's x = X(:)), y (T), one varc, and per column m a spectrum c_m (Tx, real), varx_m and mux_m.  With amp = GetAmp as above and
+ * s = 1/(1 + exp(-x)):
+ *     A_tm = amp(X_tm) (t < T),   P_t = prod_m A_tm (m ascending),   ObjA = sum_m sum_t log A_tm + (sum_t 1/2 (y_t / P_t)^2) / varc,
+ *     D_t = 1 - y_t^2 / (varc P_t^2),   u_m = real(ifft(fft(X_:m - mux_m) ./ c_m)),   ObjB = sum_m (u_m' (X_:m - mux_m)) / (2 varx_m),
+ *     dObj_tm = u_tm / varx_m + (t < T ? s_tm / A_tm D_t : 0),   Obj = ObjA + ObjB.
+ * (No vary, no 1/2 log v and no 1e-5 in this objective.)  Wherever the .m's plain log(1 + exp(x)) is finite amp equals it to rounding,
+ * and it stays finite beyond; entries of x outside +-700 give Inf or NaN as the .m does.
+ * Layout, C order: x and dObj (n_problems, M, Tx) -- per cascade the .m's X(:) --, y (n_problems, T), len, varx, mux (n_problems, M), varc
+ * (n_problems).  The spectra are either given -- fftCovs (M, Tx) shared by the cascades (cov_stride = 0) or (n_problems, M, Tx)
+ * (cov_stride = M Tx), len = NULL -- or formed on the device from len (fftCovs = NULL) as for nagp_gppad_obj.  dObj = NULL: the
+ * objective only (the same Obj bits).
+ * The transforms are those of nagp_gppad_obj, one per column.  A pre-pass (one thread per sample) forms P_t, D_t and the sums of ObjA
+ * over workgroups of 256 samples; the per-sample pass behind the inverse transform adds D_t; a finish kernel adds the workgroups, then the
+ * columns, in ascending order (no floating-point atomics): the bits of a cascade are a function of (M, T, Tx) and its own data alone --
+ * the same alone, in a batch, with shared or own spectra, with or without dObj, one-shot or resident, however the call is cut into
+ * device batches.
+ * All of the following is decided on the host before any device call.
+ * NAGP_EUNSUPPORTED: M outside 1 .. 8; Tx not a power of two, or outside 2 .. 2^20; one cascade beyond the budget of the per-evaluation
+ *   buffers (the 1 GiB of nagp_gppad_obj and its developer switch): a cascade takes
+ *   8 (M (2 Tx (4 Tx when Tx > 4096) + 2 max(1, Tx / 4096)) + T + 2 ceil(T / 256) + 1) bytes of them.
+ * NAGP_EINVAL: a NULL handle, x, y, varx, mux, varc or Obj; n_problems < 1; T < 1; T > Tx; cov_stride not 0 or M Tx; both or neither of
+ *   len and fftCovs; y, len, fftCovs, varx, mux or varc not finite; varx <= 0; varc <= 0; len <= 0; fftCovs <= 0.
+ * x is not examined. */
+typedef struct nagp_gppad_cas nagp_gppad_cas; /* opaque */
+int nagp_gppad_cas_obj(int32_t n_problems, int32_t M, int64_t T, int64_t Tx,
+                       const double* x /* n_problems x M x Tx */, const double* y /* n_problems x T */,
+                       const double* len /* n_problems x M, read when fftCovs == NULL */,
+                       const double* fftCovs, int64_t cov_stride /* NULL, or 0 = M x Tx shared, M Tx = per cascade */,
+                       const double* varx, const double* mux /* n_problems x M each */, const double* varc /* n_problems */,
+                       double* Obj /* n_problems */, double* dObj /* n_problems x M x Tx, or NULL */, int32_t device);
+int nagp_gppad_cas_create(nagp_gppad_cas** handle, int32_t n_problems, int32_t M, int64_t T, int64_t Tx, const double* y,
+                          const double* len, const double* fftCovs, int64_t cov_stride,
+                          const double* varx, const double* mux, const double* varc, int32_t device);
+int nagp_gppad_cas_eval(nagp_gppad_cas* handle, const double* x, double* Obj, double* dObj /* or NULL */);
+void nagp_gppad_cas_destroy(nagp_gppad_cas* handle);
+/* Device time of the kernels of the last nagp_gppad_cas_eval (or nagp_gppad_cas_obj) on this thread, in ms. */
+int nagp_gppad_cas_timings(double* ms /* 1 */);
+
 /* The objectives that experiments/nmf/nmf.m and nmf_inf.m minimise by conjugate gradients -- the NMF with temporal priors on the
  * activations that the training drivers keep next to their nmf_fp call (train_model.m:123), and its inference-only form for missing
  * data and denoising: getObj_nmf_temp.m (learning form, W = NULL: x = [log H(:); log W(:)], T K + K D entries per problem) and

@@ -39,6 +39,9 @@
  *   [Obj, dObj] = nagp_mex('gppad_obj', x, y, fftCov, varx, mux, varc, vary [,device])                         nagp_gppad_obj
  *                                    x Tx x P; y T x P; fftCov Tx x 1 (shared) or Tx x P; varx, mux, varc: scalars or P entries;
  *                                    vary a scalar, T x 1 (the same for every problem) or T x P; Obj P x 1, dObj Tx x P (formed only with two outputs)
+ *   [Obj, dObj] = nagp_mex('gppad_cas_obj', x, y, fftCovs, varx, mux, varc [,device])                          nagp_gppad_cas_obj
+ *                                    x (M Tx) x P, a column the X(:) of one cascade; y T x P; fftCovs Tx x M (shared) or Tx x M x P; varx, mux:
+ *                                    M entries or M x P; varc a scalar or P entries; Obj P x 1, dObj (M Tx) x P (formed only with two outputs)
  *   [Obj, dObj] = nagp_mex('nmf_temp_obj', x, A, vary, W, muinf, varinf, lam [,device])                        nagp_nmf_temp_obj
  *                                    A T x D; vary T x D or [] (zeros); W [] -- the learning form, x (T K + K D) x P -- or K x D (shared) or
  *                                    K x D x P -- the inference form, x (T K) x P; muinf, varinf, lam: K entries or []: varinf empty = no prior,
@@ -408,6 +411,40 @@ static void cmd_gppad_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* pr
   for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
 }
 
+static void cmd_gppad_cas_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('gppad_cas_obj', x, y, fftCovs, varx, mux, varc [,device]) -> [Obj, dObj]: the objective of gppad/Cascade/GetObjCasGPFAST.m for P
+     cascades of M modulators; dObj only when asked for */
+  size_t nx, ny, nc, n3[3], P, M, MTx, Tx, T, q, m; const double *x, *y, *cov, *par[3]; double* sc[3]; int32_t dev; int i, k;
+  mxArray* o[2] = {NULL, NULL};
+  static const char* names[3] = {"varx", "mux", "varc"};
+  if (nrhs < 7 || nrhs > 8 || nlhs > 2) mexErrMsgIdAndTxt("nagp:arg", "usage: [Obj,dObj] = nagp_mex('gppad_cas_obj',x,y,fftCovs,varx,mux,varc[,device])");
+  x = dvec(prhs[1], "x", &nx); MTx = x ? mxGetM(prhs[1]) : 0;
+  cov = dvec(prhs[3], "fftCovs", &nc); Tx = cov ? mxGetM(prhs[3]) : 0;
+  if (!x || !MTx || nx % MTx != 0) mexErrMsgIdAndTxt("nagp:arg", "x must be (M Tx) x P");
+  if (!cov || !Tx || MTx % Tx != 0) mexErrMsgIdAndTxt("nagp:arg", "fftCovs must be Tx x M or Tx x M x P, with the M Tx rows of x");
+  P = nx / MTx; M = MTx / Tx;
+  if (nc != MTx && nc != MTx * P) mexErrMsgIdAndTxt("nagp:arg", "fftCovs must be Tx x M or Tx x M x P, with the M Tx rows of x");
+  y = dvec(prhs[2], "y", &ny); T = y ? mxGetM(prhs[2]) : 0;
+  if (!y || !T || ny != T * P) mexErrMsgIdAndTxt("nagp:arg", "y must be T x P");
+  for (k = 0; k < 3; ++k) {
+    const size_t per = k < 2 ? M : 1;
+    par[k] = dvec(prhs[4 + k], names[k], &n3[k]);
+    if (!par[k] || (n3[k] != per && n3[k] != per * P)) mexErrMsgIdAndTxt("nagp:arg", k < 2 ? "%s must hold M entries or be M x P" : "%s must be a scalar or hold P entries", names[k]);
+  }
+  dev = nrhs > 7 ? (int32_t)mxGetScalar(prhs[7]) : 0;
+  for (k = 0; k < 3; ++k) {
+    const size_t per = k < 2 ? M : 1;
+    sc[k] = (double*)mxCalloc(per * P, sizeof(double));
+    for (q = 0; q < P; ++q) for (m = 0; m < per; ++m) sc[k][q * per + m] = par[k][n3[k] == per ? m : q * per + m];
+  }
+  o[0] = mxCreateDoubleMatrix((mwSize)P, 1, mxREAL);
+  if (nlhs > 1) o[1] = mxCreateDoubleMatrix((mwSize)MTx, (mwSize)P, mxREAL);
+  fail_if(nagp_gppad_cas_obj((int32_t)P, (int32_t)M, (int64_t)T, (int64_t)Tx, x, y, NULL, cov, nc == MTx * P && P > 1 ? (int64_t)MTx : 0,
+                             sc[0], sc[1], sc[2], mxGetPr(o[0]), o[1] ? mxGetPr(o[1]) : NULL, dev));
+  for (k = 0; k < 3; ++k) mxFree(sc[k]);
+  for (i = 0; i < (nlhs > 1 ? nlhs : 1); ++i) plhs[i] = o[i];
+}
+
 static void cmd_nmf_temp_obj(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
   /* ('nmf_temp_obj', x, A, vary, W, muinf, varinf, lam [,device]) -> [Obj, dObj]: the objectives of experiments/nmf/getObj_nmf_temp.m (W = [])
      and getObj_nmf_temp_inf.m for P problems; dObj only when asked for */
@@ -653,6 +690,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     else if (!strcmp(cmd, "pstft_obj")) cmd_pstft_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "segp_obj")) cmd_segp_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "gppad_obj")) cmd_gppad_obj(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "gppad_cas_obj")) cmd_gppad_cas_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "nmf_temp_obj")) cmd_nmf_temp_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "tnmf_obj")) cmd_tnmf_obj(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "sebf_fit_obj")) cmd_sebf_fit_obj(nlhs, plhs, nrhs, prhs);

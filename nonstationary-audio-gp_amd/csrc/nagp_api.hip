@@ -23,6 +23,7 @@ NAGP_LIST_NMF(extern template __global__)
 NAGP_LIST_PSTFT(extern template __global__)
 NAGP_LIST_SEGP(extern template __global__)
 NAGP_LIST_GPPAD(extern template __global__)
+NAGP_LIST_GPPAD_CAS(extern template __global__)
 NAGP_LIST_NMFT(extern template __global__)
 NAGP_LIST_SEBF(extern template __global__)
 
@@ -52,7 +53,7 @@ static thread_local std::string g_last_error;
 // and the scripts under tools/ set it; bench.py and the MEX gateway never do).  The switches that make results meaningless (phase-skipping
 // timing probes) and the test hooks that replace devices or fail allocations say so on stderr once when they are active.
 // read_dev_switches() is the only reader of the environment: nagp_plan_create takes one snapshot into the plan (nagp_plan::dev), which
-// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run, nagp_fastfb_sample, nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj, nagp_gppad_create, nagp_nmf_temp_create, nagp_sebf_conv, nagp_sebf_fit_create and nagp_tnmf_create one per call.
+// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run, nagp_fastfb_sample, nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj, nagp_gppad_create, nagp_gppad_cas_create, nagp_nmf_temp_create, nagp_sebf_conv, nagp_sebf_fit_create and nagp_tnmf_create one per call.
 struct DevSwitches {
   // presence switches: on when the variable is set to anything
   bool no_wide = false;          // NAGP_NO_WIDE
@@ -83,7 +84,7 @@ struct DevSwitches {
   int pipeline_slots = 0;        // NAGP_PIPELINE_SLOTS (>= 1; at most nc - 1 at the use)
   int mom_chunk = 0;             // NAGP_MOM_CHUNK (>= 64)
   // NAGP_<FBS|SFB|NMF|PSTFT|SEGP|GPPAD|NMFT|SEBF>_BUDGET_MB (>= 1): the device-memory budget in MiB, instead of the <...>_BUDGET_BYTES of its file, of nagp_fastfb_sample,
-  // nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj and of the per-evaluation buffers of a nagp_gppad / nagp_nmf_temp / nagp_sebf_fit / nagp_tnmf handle and of nagp_sebf_conv (budget_bytes, nagp_api_layout.hpp)
+  // nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj and of the per-evaluation buffers of a nagp_gppad / nagp_gppad_cas (the GPPAD slot) / nagp_nmf_temp / nagp_sebf_fit / nagp_tnmf handle and of nagp_sebf_conv (budget_bytes, nagp_api_layout.hpp)
   enum Budget { FBS, SFB, NMF, PSTFT, SEGP, GPPAD, NMFT, SEBF, N_BUDGETS };
   int budget_mb[N_BUDGETS] = {0, 0, 0, 0, 0, 0, 0, 0};
   int kb_f = 0;                  // NAGP_KB_F (1 .. 16)
@@ -452,5 +453,6 @@ struct Timed {
 #include "nagp_api_pstft.hpp"
 #include "nagp_api_segp.hpp"
 #include "nagp_api_gppad.hpp"
+#include "nagp_api_gppad_cas.hpp"
 #include "nagp_api_nmf_temp.hpp"
 #include "nagp_api_sebf.hpp"

@@ -1,6 +1,6 @@
 // nagp_api_entry.hpp -- part of the ONE translation unit nagp_api.hip (included there after nagp_api_plan.hpp, nagp_api_sweep.hpp and
 // nagp_api_batch.hpp; the plan struct, the error helpers and the developer switches live in nagp_api.hip itself).
-// The plan-based entry points (ep / ihgp / giekf run), mom, iekf_update1, nagp_batch_run (RCCL), reconstruction; the batched ones: nagp_api_{fastfb,slowfb,nmf,pstft,segp,gppad,nmf_temp,sebf}.hpp.
+// The plan-based entry points (ep / ihgp / giekf run), mom, iekf_update1, nagp_batch_run (RCCL), reconstruction; the batched ones: nagp_api_{fastfb,slowfb,nmf,pstft,segp,gppad,gppad_cas,nmf_temp,sebf}.hpp.
 
 // ---------------------------------------------------------------------------------------------
 static int run_one(const nagp_model* model, const nagp_ihgp_tables* tables, const double* y, int64_t T,

@@ -67,6 +67,17 @@ struct GppadBat { size_t x, dg, wk, pt, ob, total; };
 inline GppadBat gppad_bat(size_t Tx, bool four_step, size_t nwg, size_t nb) {
   Layout l; return {l.take(nb * Tx), l.take(nb * Tx), l.take(four_step ? 2 * nb * Tx : 0), l.take(2 * nb * nwg), l.take(nb), l.total(2)};
 }
+// nagp_gppad_cas handle (n cascades of M columns), resident: y | ic | varx | mux | varc;  per device batch: x | dObj | work (four-step
+// form) | part | D | partA | Obj
+struct GppadCasRes { size_t y, ic, vx, mu, vc, total; };
+inline GppadCasRes gppad_cas_res(size_t n, size_t M, size_t T, size_t Tx, bool ic_per_cascade) {
+  Layout l; return {l.take(n * T), l.take(ic_per_cascade ? n * M * Tx : M * Tx), l.take(n * M), l.take(n * M), l.take(n), l.total(2)};
+}
+struct GppadCasBat { size_t x, dg, wk, pt, d, pa, ob, total; };
+inline GppadCasBat gppad_cas_bat(size_t M, size_t T, size_t Tx, bool four_step, size_t nwg, size_t nwgA, size_t nb) {
+  Layout l; return {l.take(nb * M * Tx), l.take(nb * M * Tx), l.take(four_step ? 2 * nb * M * Tx : 0), l.take(2 * nb * M * nwg), l.take(nb * T), l.take(2 * nb * nwgA),
+          l.take(nb), l.total(2)};
+}
 // nagp_nmf_temp handle, resident: A | vary | W (inference form) | muinf, varinf, lam;  per device batch: x | dObj | pw (learning form) | po | Obj
 struct NmftRes { size_t a, vy, w, pr, total; };
 inline NmftRes nmft_res(size_t n, size_t T, size_t D, size_t K, bool vary, bool given_W) {

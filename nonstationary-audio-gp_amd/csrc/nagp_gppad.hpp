@@ -58,6 +58,11 @@ struct GppadPar {
   double* dObj;            // problems x Tx
   const double* len;       // problems (gppad_cov_kernel)
   double* ic_out;          // problems x Tx (gppad_cov_kernel)
+  // the cascade form (V = 1, see below): a "problem" is column m of cascade prob / M
+  int M;                   // columns of a cascade
+  int nwgA;                // workgroups of the pre-pass per cascade
+  double* D;               // cascades x T: D_t = 1 - y_t^2 / (varc P_t^2) (written by the pre-pass, read by the per-sample pass)
+  double* partA;           // cascades x nwgA x 2: the pre-pass's sums of log A and of 1/2 (y / P)^2
 };
 
 __host__ __device__ inline int gp_pad(int i) { return i + (i >> 4); }
@@ -159,9 +164,22 @@ __host__ __device__ inline void gp_point(const GppadPar& p, int prob, const GpSc
   if (p.grad) p.dObj[ix] = g;
 }
 
-// the workgroup's two sums to part[prob][blk][]: xor butterfly in a wave, waves in wave order (red: 2 x 8 doubles of LDS)
-__host__ __device__ inline void gp_block_sums(const GppadPar& p, int prob, int blk, double oa, double ob, double* red, int tid, int nt) {
-  double* out = p.part + ((size_t)prob * p.nwg + blk) * 2;
+// sample n of column prob of a cascade (V = 1) with u_n as above and D_n from the pre-pass: the ObjB sum and dObj_n
+__host__ __device__ inline void gp_point_cas(const GppadPar& p, int prob, const GpScal& sc, int64_t n, double u, double& ob) {
+  const size_t ix = (size_t)prob * (size_t)p.Tx + (size_t)n;
+  const double x = p.x[ix];
+  ob += u * (x - sc.mux);
+  double g = u / sc.varx;
+  if (n < p.T) {
+    double a, s;
+    gp_amp(x, a, s);
+    g += s / a * p.D[(size_t)(prob / p.M) * (size_t)p.T + (size_t)n];
+  }
+  if (p.grad) p.dObj[ix] = g;
+}
+
+// the workgroup's two sums to out[2]: xor butterfly in a wave, waves in wave order (red: 2 x 8 doubles of LDS)
+__host__ __device__ inline void gp_block_sums_to(double* out, double oa, double ob, double* red, int tid, int nt) {
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) { oa += __shfl_xor(oa, m); ob += __shfl_xor(ob, m); }
@@ -177,24 +195,40 @@ __host__ __device__ inline void gp_block_sums(const GppadPar& p, int prob, int b
   out[0] = oa; out[1] = ob;
 #endif
 }
+__host__ __device__ inline void gp_block_sums(const GppadPar& p, int prob, int blk, double oa, double ob, double* red, int tid, int nt) {
+  gp_block_sums_to(p.part + ((size_t)prob * p.nwg + blk) * 2, oa, ob, red, tid, nt);
+}
 
-__host__ __device__ inline GpScal gp_scalars(const GppadPar& p, int prob) { return GpScal{p.varx[prob], p.mux[prob], p.varc[prob]}; }
+// V = 0: GetGPObjFast.m, one problem per transform.  V = 1: the cascade (GetObjCasGPFAST.m, header below): varx, mux, 1 / c per column,
+// varc per cascade (read by the pre-pass and the finish only)
+template <int V>
+__host__ __device__ inline GpScal gp_scalars(const GppadPar& p, int prob) { return GpScal{p.varx[prob], p.mux[prob], V ? 0.0 : p.varc[prob]}; }
+// 1 / (c Tx) of a problem; a spectrum shared by the cascades (ic_stride = 0) is M x Tx
+template <int V>
+__host__ __device__ inline const double* gp_ic(const GppadPar& p, int prob) {
+  return p.ic + (V && !p.ic_stride ? (size_t)(prob % p.M) * (size_t)p.Tx : (size_t)prob * (size_t)p.ic_stride);
+}
+template <int V>
+__host__ __device__ inline void gp_sample(const GppadPar& p, int prob, const GpScal& sc, int64_t n, double u, double& oa, double& ob) {
+  if (V) gp_point_cas(p, prob, sc, n, u, ob); else gp_point(p, prob, sc, n, u, oa, ob);
+}
 
 // Tx <= 4096: one workgroup per problem
+template <int V = 0>
 __host__ __device__ inline void gppad_lds_body(const GppadPar& p, int prob, int tid, int nt, double2* lds, double* red) {
   const int n = (int)p.Tx, ln = gp_log2(n);
   double2* src = lds; double2* dst = lds + gp_pad(n - 1) + 1;
-  const GpScal sc = gp_scalars(p, prob);
+  const GpScal sc = gp_scalars<V>(p, prob);
   const double* x = p.x + (size_t)prob * (size_t)p.Tx;
   for (int e = tid; e < n; e += nt) src[gp_pad(e)] = make_double2(x[e] - sc.mux, 0.0);
   gp_sync();
   gp_fft<1>(src, dst, ln, 0, p.tw, 1, tid, nt);
-  const double* ic = p.ic + (size_t)prob * (size_t)p.ic_stride;
+  const double* ic = gp_ic<V>(p, prob);
   for (int e = tid; e < n; e += nt) { const double f = ic[e]; double2 v = src[gp_pad(e)]; v.x *= f; v.y *= f; src[gp_pad(e)] = v; }
   gp_sync();
   gp_fft<-1>(src, dst, ln, 0, p.tw, 1, tid, nt);
   double oa = 0.0, ob = 0.0;
-  for (int e = tid; e < n; e += nt) gp_point(p, prob, sc, e, src[gp_pad(e)].x, oa, ob);
+  for (int e = tid; e < n; e += nt) gp_sample<V>(p, prob, sc, e, src[gp_pad(e)].x, oa, ob);
   gp_block_sums(p, prob, 0, oa, ob, red, tid, nt);
 }
 
@@ -218,6 +252,7 @@ __host__ __device__ inline void gppad_colf_body(const GppadPar& p, int prob, int
 }
 
 // four-step, second kernel: row k1 = blk, forward along n2, times ic, inverse, conjugate twiddle, in place
+template <int V = 0>
 __host__ __device__ inline void gppad_row_body(const GppadPar& p, int prob, int blk, int tid, int nt, double2* lds) {
   const int n = p.N2, ln = gp_log2(n);
   double2* src = lds; double2* dst = lds + gp_pad(n - 1) + 1;
@@ -225,7 +260,7 @@ __host__ __device__ inline void gppad_row_body(const GppadPar& p, int prob, int 
   for (int e = tid; e < n; e += nt) src[gp_pad(e)] = row[e];
   gp_sync();
   gp_fft<1>(src, dst, ln, 0, p.tw, p.N1, tid, nt);
-  const double* ic = p.ic + (size_t)prob * (size_t)p.ic_stride + (size_t)blk * (size_t)n;
+  const double* ic = gp_ic<V>(p, prob) + (size_t)blk * (size_t)n;
   for (int e = tid; e < n; e += nt) { const double f = ic[e]; double2 v = src[gp_pad(e)]; v.x *= f; v.y *= f; src[gp_pad(e)] = v; }
   gp_sync();
   gp_fft<-1>(src, dst, ln, 0, p.tw, p.N1, tid, nt);
@@ -233,10 +268,11 @@ __host__ __device__ inline void gppad_row_body(const GppadPar& p, int prob, int 
 }
 
 // four-step, third kernel: column tile blk, inverse along k1, the per-sample pass
+template <int V = 0>
 __host__ __device__ inline void gppad_coli_body(const GppadPar& p, int prob, int blk, int tid, int nt, double2* lds, double* red) {
   const int lcb = p.lcb, cb = 1 << lcb, pts = p.N1 << lcb, c0 = blk << lcb, ln = gp_log2(p.N1);
   double2* src = lds; double2* dst = lds + gp_pad(pts - 1) + 1;
-  const GpScal sc = gp_scalars(p, prob);
+  const GpScal sc = gp_scalars<V>(p, prob);
   const double2* work = p.work + (size_t)prob * (size_t)p.Tx;
   for (int e = tid; e < pts; e += nt) src[gp_pad(e)] = work[(int64_t)(e >> lcb) * p.N2 + c0 + (e & (cb - 1))];
   gp_sync();
@@ -244,7 +280,7 @@ __host__ __device__ inline void gppad_coli_body(const GppadPar& p, int prob, int
   double oa = 0.0, ob = 0.0;
   for (int e = tid; e < pts; e += nt) {
     const int64_t n = (int64_t)(e >> lcb) * p.N2 + c0 + (e & (cb - 1));
-    gp_point(p, prob, sc, n, src[gp_pad(e)].x, oa, ob);
+    gp_sample<V>(p, prob, sc, n, src[gp_pad(e)].x, oa, ob);
   }
   gp_block_sums(p, prob, blk, oa, ob, red, tid, nt);
 }
@@ -268,10 +304,62 @@ __host__ __device__ inline void gppad_finish_item(const GppadPar& p, int prob) {
   p.Obj[prob] = sa + 1.0 / (2.0 * p.varx[prob]) * sb;
 }
 
-// (templates so that the one instantiation lives in inst_gppad.hip)
+// ---- the cascade, Cascade/GetObjCasGPFAST.m:19-50: X (Tx x M, column m = "problem" cas M + m of the kernels above), one y and one varc,
+// per column a spectrum, varx and mux:
+//     A_tm = amp(X_tm) (t < T),  P_t = prod_m A_tm (m ascending),  ObjA = sum_t sum_m log A_tm + (sum_t 1/2 (y_t / P_t)^2) / varc,
+//     D_t = 1 - y_t^2 / (varc P_t^2),  u_m = real(ifft(fft(X_:m - mux_m) ./ c_m)),  ObjB = sum_m (u_m' (X_:m - mux_m)) / (2 varx_m),
+//     dObj_tm = u_tm / varx_m + (t < T ? s_tm / A_tm D_t : 0),  Obj = ObjA + ObjB      (no vary, no 1/2 log v, no 1e-5 in this objective).
+// amp is gp_amp: wherever the .m's plain log(1 + exp(x)) is finite it equals it to rounding, and it stays finite beyond (x up to 700 and
+// past it: a = x); entries outside +-700 give Inf or NaN (A = 0 below -745: log A = -Inf, s / A = 0 / 0) as the .m does, never a fault.
+//   gppad_cas_pre_kernel     grid (ceil(T / 256), cascades), 256 threads, one per sample: the M amp calls, the product, D_t to the
+//                            workspace, the workgroup's sums of sum_m log A_tm and of 1/2 (y_t / P_t)^2 to partA;
+//   the transform kernels    in their V = 1 instantiation on cascades x M "problems" (the forward column kernel and the spectrum kernel do
+//                            not differ: V = 0 serves): the per-sample pass of a column is one amp, D_t and u (gp_point_cas), ObjA's slot of part is 0;
+//   gppad_cas_finish_kernel  one thread per cascade: the pre-pass's workgroups in ascending order, / varc, then the columns in ascending order,
+//                            each the sum of its workgroups in ascending order / (2 varx_m).  No atomics.
+// The bits of a cascade are a function of (M, T, Tx) and its own data.
+constexpr int GPPAD_CAS_NT = 256;
+constexpr int GPPAD_CAS_MAX_M = 8;
+__host__ __device__ inline int gppad_cas_nwg(int64_t T) { return (int)((T + GPPAD_CAS_NT - 1) / GPPAD_CAS_NT); }
+
+__host__ __device__ inline void gppad_cas_pre_body(const GppadPar& p, int cas, int blk, int tid, int nt, double* red) {
+  const int64_t t0 = (int64_t)blk * GPPAD_CAS_NT, t1 = t0 + GPPAD_CAS_NT < p.T ? t0 + GPPAD_CAS_NT : p.T;
+  const double* x = p.x + (size_t)cas * (size_t)p.M * (size_t)p.Tx;
+  const double varc = p.varc[cas];
+  double ol = 0.0, oq = 0.0;
+  for (int64_t t = t0 + tid; t < t1; t += nt) {
+    double P = 1.0, l = 0.0;
+    for (int m = 0; m < p.M; ++m) {
+      double a, s;
+      gp_amp(x[(size_t)m * (size_t)p.Tx + (size_t)t], a, s);
+      l += log(a); P *= a;
+    }
+    const double y = p.y[(size_t)cas * (size_t)p.T + (size_t)t], r = y / P;
+    ol += l; oq += 0.5 * (r * r);
+    p.D[(size_t)cas * (size_t)p.T + (size_t)t] = 1.0 - y * y / (varc * (P * P));
+  }
+  gp_block_sums_to(p.partA + ((size_t)cas * p.nwgA + blk) * 2, ol, oq, red, tid, nt);
+}
+
+__host__ __device__ inline void gppad_cas_finish_item(const GppadPar& p, int cas) {
+  const double* pa = p.partA + (size_t)cas * p.nwgA * 2;
+  double sl = 0.0, sq = 0.0;
+  for (int w = 0; w < p.nwgA; ++w) { sl += pa[2 * w]; sq += pa[2 * w + 1]; }
+  double ob = 0.0;
+  for (int m = 0; m < p.M; ++m) {
+    const size_t q = (size_t)cas * p.M + m;
+    const double* pp = p.part + q * p.nwg * 2;
+    double sb = 0.0;
+    for (int w = 0; w < p.nwg; ++w) sb += pp[2 * w + 1];
+    ob += sb / (2.0 * p.varx[q]);
+  }
+  p.Obj[cas] = (sl + sq / p.varc[cas]) + ob;
+}
+
+// (templates so that the instantiations live in inst_gppad.hip and inst_gppad_cas.hip)
 template <int V> __global__ void __launch_bounds__(GPPAD_MAX_NT) gppad_lds_kernel(GppadPar p) {
   extern __shared__ double2 gp_lds[];
-  gppad_lds_body(p, blockIdx.x, threadIdx.x, blockDim.x, gp_lds, reinterpret_cast<double*>(gp_lds + gppad_lds_points(p.Tx)));
+  gppad_lds_body<V>(p, blockIdx.x, threadIdx.x, blockDim.x, gp_lds, reinterpret_cast<double*>(gp_lds + gppad_lds_points(p.Tx)));
 }
 template <int V> __global__ void __launch_bounds__(GPPAD_MAX_NT) gppad_colf_kernel(GppadPar p) {
   extern __shared__ double2 gp_lds[];
@@ -279,11 +367,11 @@ template <int V> __global__ void __launch_bounds__(GPPAD_MAX_NT) gppad_colf_kern
 }
 template <int V> __global__ void __launch_bounds__(GPPAD_MAX_NT) gppad_row_kernel(GppadPar p) {
   extern __shared__ double2 gp_lds[];
-  gppad_row_body(p, blockIdx.y, blockIdx.x, threadIdx.x, blockDim.x, gp_lds);
+  gppad_row_body<V>(p, blockIdx.y, blockIdx.x, threadIdx.x, blockDim.x, gp_lds);
 }
 template <int V> __global__ void __launch_bounds__(GPPAD_MAX_NT) gppad_coli_kernel(GppadPar p) {
   extern __shared__ double2 gp_lds[];
-  gppad_coli_body(p, blockIdx.y, blockIdx.x, threadIdx.x, blockDim.x, gp_lds, reinterpret_cast<double*>(gp_lds + gppad_lds_points(p.Tx)));
+  gppad_coli_body<V>(p, blockIdx.y, blockIdx.x, threadIdx.x, blockDim.x, gp_lds, reinterpret_cast<double*>(gp_lds + gppad_lds_points(p.Tx)));
 }
 template <int V> __global__ void __launch_bounds__(256) gppad_cov_kernel(GppadPar p) {
   const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -294,8 +382,20 @@ template <int V> __global__ void __launch_bounds__(64) gppad_finish_kernel(Gppad
   if (prob < n) gppad_finish_item(p, prob);
 }
 
+template <int V> __global__ void __launch_bounds__(GPPAD_CAS_NT) gppad_cas_pre_kernel(GppadPar p) {
+  __shared__ double red[16];
+  gppad_cas_pre_body(p, blockIdx.y, blockIdx.x, threadIdx.x, blockDim.x, red);
+}
+template <int V> __global__ void __launch_bounds__(64) gppad_cas_finish_kernel(GppadPar p, int n) {
+  const int cas = blockIdx.x * 64 + threadIdx.x;
+  if (cas < n) gppad_cas_finish_item(p, cas);
+}
+
 }  // namespace nagp
 
 #define NAGP_LIST_GPPAD(X) X void nagp::gppad_lds_kernel<0>(nagp::GppadPar); X void nagp::gppad_colf_kernel<0>(nagp::GppadPar); \
   X void nagp::gppad_row_kernel<0>(nagp::GppadPar); X void nagp::gppad_coli_kernel<0>(nagp::GppadPar); \
   X void nagp::gppad_cov_kernel<0>(nagp::GppadPar); X void nagp::gppad_finish_kernel<0>(nagp::GppadPar, int);
+#define NAGP_LIST_GPPAD_CAS(X) X void nagp::gppad_lds_kernel<1>(nagp::GppadPar); X void nagp::gppad_row_kernel<1>(nagp::GppadPar); \
+  X void nagp::gppad_coli_kernel<1>(nagp::GppadPar); X void nagp::gppad_cas_pre_kernel<1>(nagp::GppadPar); \
+  X void nagp::gppad_cas_finish_kernel<1>(nagp::GppadPar, int);

@@ -84,7 +84,8 @@ EXPORTS = ['nagp_version', 'nagp_device_count', 'nagp_strerror', 'nagp_last_erro
            'nagp_segp_obj', 'nagp_segp_timings', 'nagp_gppad_obj', 'nagp_gppad_create', 'nagp_gppad_eval', 'nagp_gppad_destroy', 'nagp_gppad_timings',
            'nagp_nmf_temp_obj', 'nagp_nmf_temp_create', 'nagp_nmf_temp_eval', 'nagp_nmf_temp_destroy', 'nagp_nmf_temp_timings',
            'nagp_sebf_conv', 'nagp_sebf_fit_obj', 'nagp_sebf_fit_create', 'nagp_sebf_fit_eval', 'nagp_sebf_fit_destroy',
-           'nagp_tnmf_obj', 'nagp_tnmf_create', 'nagp_tnmf_eval', 'nagp_tnmf_destroy', 'nagp_tnmf_timings']
+           'nagp_tnmf_obj', 'nagp_tnmf_create', 'nagp_tnmf_eval', 'nagp_tnmf_destroy', 'nagp_tnmf_timings',
+           'nagp_gppad_cas_obj', 'nagp_gppad_cas_create', 'nagp_gppad_cas_eval', 'nagp_gppad_cas_destroy', 'nagp_gppad_cas_timings']
 NMFT_NONE, NMFT_TG, NMFT_IG = 0, 1, 2
 
 
@@ -241,6 +242,12 @@ def lib():
     L.nagp_gppad_eval.argtypes = [C.c_void_p, c_dp, c_dp, c_dp]; L.nagp_gppad_eval.restype = C.c_int
     L.nagp_gppad_destroy.argtypes = [C.c_void_p]; L.nagp_gppad_destroy.restype = None
     L.nagp_gppad_timings.argtypes = [c_dp]; L.nagp_gppad_timings.restype = C.c_int
+    cas_data = [c_dp, c_dp, c_dp, C.c_int64, c_dp, c_dp, c_dp]                           # y, len, fftCovs, cov_stride, varx, mux, varc
+    L.nagp_gppad_cas_obj.argtypes = [C.c_int32, C.c_int32, C.c_int64, C.c_int64, c_dp] + cas_data + [c_dp, c_dp, C.c_int32]; L.nagp_gppad_cas_obj.restype = C.c_int
+    L.nagp_gppad_cas_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int64, C.c_int64] + cas_data + [C.c_int32]; L.nagp_gppad_cas_create.restype = C.c_int
+    L.nagp_gppad_cas_eval.argtypes = [C.c_void_p, c_dp, c_dp, c_dp]; L.nagp_gppad_cas_eval.restype = C.c_int
+    L.nagp_gppad_cas_destroy.argtypes = [C.c_void_p]; L.nagp_gppad_cas_destroy.restype = None
+    L.nagp_gppad_cas_timings.argtypes = [c_dp]; L.nagp_gppad_cas_timings.restype = C.c_int
     nmft_data = [c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]                                   # A, vary, W, muinf, varinf, lam
     L.nagp_nmf_temp_obj.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_dp] + nmft_data + [c_dp, c_dp, C.c_int32]
     L.nagp_nmf_temp_obj.restype = C.c_int

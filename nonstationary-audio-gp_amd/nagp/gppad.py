@@ -16,8 +16,9 @@ conjugate-gradient line search (minimize.minimize_steps) stay on the host.  Ther
 that the tests can put the float64 restatement through the same driver.
 
 Not built, and refused with the name of the reference file that would serve them: length-scale learning (LrnLen = 1, 2:
-FBGPMAPLearnLen.m), the Laplace error bars (outputs 6-8: FBGPMAPLearnLen.m with LoadErrorBarsLapOpts.m), cascades (a column of
-length-scales: FBCasGPMAP.m).
+FBGPMAPLearnLen.m) and the Laplace error bars (outputs 6-8: FBGPMAPLearnLen.m with LoadErrorBarsLapOpts.m).  Cascades (a column of
+length-scales) are built, in gppad_cas.py under the names of their own .m files (FBCasGPMAP, CasGPMAP, MAPGPCasFast, GetObjCasGPFAST);
+GPPAD and FBGPMAP keep refusing a column of length-scales with the name FBCasGPMAP.m.
 """
 import math
 
