@@ -486,6 +486,55 @@ void nagp_gppad_cas_destroy(nagp_gppad_cas* handle);
 /* Device time of the kernels of the last nagp_gppad_cas_eval (or nagp_gppad_cas_obj) on this thread, in ms. */
 int nagp_gppad_cas_timings(double* ms /* 1 */);
 
+/* The Laplace step of GPPAD -- experiments/gppad/GPModelFast/Laplace: the error bars of the envelope (GetErrorBarGPPAD.m) and the three
+ * terms of the approximate marginal likelihood that the time-scale is learnt with (GetLaplaceObjGPPADOneChunk.m) -- for a batch of
+ * problems (one chunk of one channel at one time-scale each) that share T and Tx.  With y, vary, len, varx, mux, varc as for
+ * nagp_gppad_create, amp and s as there, c2 = 1/4 / cosh(x/2)^2, v = amp^2 varc + (vary + 1e-5), dv = 2 varc amp s (GetHessian.m):
+ *     d_t = (c2 amp + s^2)/v (1 - y^2/v) varc - s amp/v^2 (1 - y^2/v) varc dv + s amp/v y^2/v^2 varc dv          (t < T),
+ *     h = c varx (c = GetFFTCovFast(len, Tx)),   A v = ifft(h^1/2 .* fft([d .* a(1:T); 0])) with a = ifft(h^1/2 .* fft(v))   (SigDSigTimesV.m).
+ * nagp_gppad_lap_hess sets the MAP point x (n_problems x Tx) and leaves d resident; nagp_gppad_lap_apply is A on given vectors.
+ * nagp_gppad_lap_eig runs LanczosGPPAD.m on every problem from its own vstart (n_problems x Tx) with at most jmax steps (GetEigSigDSig.m:
+ * jmax = 2 nev, tresh = 1e-12, tolconv = 1e-8): the three-term recurrence, the omega-recurrence with sign(0) = 0, the selective
+ * reorthogonalisation (classical Gram-Schmidt of [v_j r] against v_1 .. v_{j-1}, a second pass when the spectral norm of h1 exceeds
+ * 10 sqrt(eps), then r against v_j; beta(j+1) is not recomputed, as in the .m), the convergence test after a reorthogonalisation, at
+ * jmax and when beta(j+1) < epert, the stop at beta(j+1) < epert or nconv >= nev.  The problems of a device batch run in lock-step; a
+ * problem that has stopped is masked out of the later launches.  Per step alpha and beta (and h1 on a reorthogonalisation) come to the
+ * host, which holds the recurrences and solves the tridiagonal eigenproblems (implicit QL; no LAPACK); the basis stays on the device.
+ * Outputs: lmb (n_problems x jmax) the converged Ritz values in descending order, NaN beyond nconv; info per problem (steps,
+ * reorthogonalisations, status: 0 fine, 1 a tridiagonal entry that is not finite, 2 the QL iteration did not converge -- with either,
+ * nconv = 0 and the caller may draw another vstart); anorm the .m's estimate of |A|; xv (n_problems x jmax x Tx, rows beyond nconv not
+ * written) = V s.  It also leaves Varx = varx - sum_k |ifft(h^1/2 .* fft(xv_k))|^2 l_k/(l_k + 1), l = max(lmb, 0), k ascending, on
+ * the device; nagp_gppad_lap_varx(handle, 0, NULL, NULL, ...) fetches it, and with (K, xv, lmb) (n_problems x K x Tx, n_problems x K; a
+ * NaN lmb skips its pair) forms it from given pairs instead.  n_negative counts the entries of Varx below 0 per problem (the .m stops
+ * in the debugger there).  nconv = 0 is legal: Varx = varx, Obj0 = 0.
+ * nagp_gppad_lap_obj: Obj (n_problems x 3) = Obj0 = -1/2 sum_k log|1 + l_k| (NaN before an eigen-solve), Obj1 = -1/2 sum_t (log v +
+ * y^2/v), Obj2 = -(u' xe)/(2 varx): Obj1 + Obj2 is minus nagp_gppad_obj at x, from the same kernels.
+ * Deviation: the Lanczos vectors are kept real (the .m carries the imaginary rounding noise of ifft along and drops it with real(lmb)).
+ * Sums are formed in a fixed order without atomics: a problem's bits depend neither on its batch mates nor on the device batches.
+ * NAGP_EUNSUPPORTED: Tx not a power of two, or outside 2 .. 2^20; one problem beyond the budget of the per-solve buffers (the 1 GiB of
+ *   nagp_gppad_obj and its developer switch): a problem takes 8 ((2 jmax + 2 (+ 2 when Tx > 4096)) Tx + jmax^2 + 3 jmax +
+ *   2 max(Tx / 256, 1) + 8) bytes of them (the basis and the Ritz vectors, jmax slots each).  The resident arrays (8 (4 Tx + 2 T) bytes
+ *   per problem and the parameters) are outside it.
+ * NAGP_EINVAL: a NULL argument that is not marked optional; n_problems < 1; T < 1; T > Tx; vary_stride not 0 or T; jmax outside
+ *   1 .. min(Tx, 4096); the data not finite or out of range as for nagp_gppad_create; nev < 1; tresh or tolconv not > 0; K outside
+ *   0 .. jmax; xv without lmb; apply, eig or obj before hess; varx without pairs before eig. */
+typedef struct nagp_gppad_lap nagp_gppad_lap; /* opaque */
+int nagp_gppad_lap_create(nagp_gppad_lap** handle, int32_t n_problems, int64_t T, int64_t Tx, const double* y,
+                          const double* vary, int64_t vary_stride, const double* len, const double* varx, const double* mux,
+                          const double* varc, int32_t jmax, int32_t device);
+int nagp_gppad_lap_hess(nagp_gppad_lap* handle, const double* x /* n_problems x Tx */, double* d /* n_problems x T, or NULL */);
+int nagp_gppad_lap_apply(nagp_gppad_lap* handle, const double* v, double* Av /* n_problems x Tx each */);
+int nagp_gppad_lap_eig(nagp_gppad_lap* handle, int32_t nev, double tresh, double tolconv, const double* vstart /* n_problems x Tx */,
+                       double* lmb /* n_problems x jmax */, int32_t* nconv /* n_problems */, int32_t* info /* n_problems x 3, or NULL */,
+                       double* anorm /* n_problems, or NULL */, double* xv /* n_problems x jmax x Tx, or NULL */);
+int nagp_gppad_lap_varx(nagp_gppad_lap* handle, int32_t K, const double* xv /* or NULL */, const double* lmb /* or NULL */,
+                        double* Varx /* n_problems x Tx */, int64_t* n_negative /* n_problems, or NULL */);
+int nagp_gppad_lap_obj(nagp_gppad_lap* handle, double* Obj /* n_problems x 3 */);
+void nagp_gppad_lap_destroy(nagp_gppad_lap* handle);
+/* Device span of the last nagp_gppad_lap_eig on this thread, in ms (HIP events around each device batch: the kernels and the host's
+ * control between them). */
+int nagp_gppad_lap_timings(double* ms /* 1 */);
+
 /* The objectives that experiments/nmf/nmf.m and nmf_inf.m minimise by conjugate gradients -- the NMF with temporal priors on the
  * activations that the training drivers keep next to their nmf_fp call (train_model.m:123), and its inference-only form for missing
  * data and denoising: getObj_nmf_temp.m (learning form, W = NULL: x = [log H(:); log W(:)], T K + K D entries per problem) and

@@ -11,6 +11,8 @@
 #include "nagp_pstft.hpp"
 #include "nagp_segp.hpp"
 #include "nagp_gppad.hpp"
+#include "nagp_gppad_lap.hpp"
+#include "nagp_tridiag.hpp"
 #include "nagp_nmf_temp.hpp"
 #include "nagp_sebf.hpp"
 #include "../../include/nagp.h"
@@ -24,6 +26,7 @@ NAGP_LIST_PSTFT(extern template __global__)
 NAGP_LIST_SEGP(extern template __global__)
 NAGP_LIST_GPPAD(extern template __global__)
 NAGP_LIST_GPPAD_CAS(extern template __global__)
+NAGP_LIST_GPPAD_LAP(extern template __global__)
 NAGP_LIST_NMFT(extern template __global__)
 NAGP_LIST_SEBF(extern template __global__)
 
@@ -454,5 +457,6 @@ struct Timed {
 #include "nagp_api_segp.hpp"
 #include "nagp_api_gppad.hpp"
 #include "nagp_api_gppad_cas.hpp"
+#include "nagp_api_gppad_lap.hpp"
 #include "nagp_api_nmf_temp.hpp"
 #include "nagp_api_sebf.hpp"

@@ -78,6 +78,21 @@ inline GppadCasBat gppad_cas_bat(size_t M, size_t T, size_t Tx, bool four_step, 
   Layout l; return {l.take(nb * M * Tx), l.take(nb * M * Tx), l.take(four_step ? 2 * nb * M * Tx : 0), l.take(2 * nb * M * nwg), l.take(nb * T), l.take(2 * nb * nwgA),
           l.take(nb), l.total(2)};
 }
+// nagp_gppad_lap handle, resident: y | vary | g | ic | varx | mux | varc | zeros | x | d | Varx;  per device batch (slot-major vectors, nb Tx
+// each): V (jmax slots) | xv (jmax slots) | r | tmp | work (four-step form) | part | alpha | beta | flag | sc | h1 | S | lambda | Obj
+struct LapRes { size_t y, vy, g, ic, vx, mu, vc, ze, x, d, var, total; };
+inline LapRes lap_res(size_t n, size_t T, size_t Tx, bool vary_per_sample) {
+  Layout l; return {l.take(n * T), l.take(vary_per_sample ? n * T : n), l.take(n * Tx), l.take(n * Tx), l.take(n), l.take(n), l.take(n), l.take(n), l.take(n * Tx), l.take(n * T),
+          l.take(n * Tx), l.total(2)};
+}
+struct LapBat { size_t V, xv, r, tmp, wk, pt, al, be, fl, sc, h1, S, lam, ob, total; };
+inline size_t lap_bat_per_problem(size_t Tx, size_t jmax, bool four_step, size_t np) {
+  return (2 * jmax + 2 + (four_step ? 2 : 0)) * Tx + 2 * np + 5 + 2 * jmax + jmax * jmax + jmax + 3;
+}
+inline LapBat lap_bat(size_t Tx, size_t jmax, bool four_step, size_t np, size_t nb) {
+  Layout l; return {l.take(jmax * nb * Tx), l.take(jmax * nb * Tx), l.take(nb * Tx), l.take(nb * Tx), l.take(four_step ? 2 * nb * Tx : 0), l.take(2 * nb * np), l.take(nb), l.take(nb),
+          l.take(nb), l.take(2 * nb), l.take(2 * nb * jmax), l.take(nb * jmax * jmax), l.take(jmax * nb), l.take(3 * nb), l.total(2)};
+}
 // nagp_nmf_temp handle, resident: A | vary | W (inference form) | muinf, varinf, lam;  per device batch: x | dObj | pw (learning form) | po | Obj
 struct NmftRes { size_t a, vy, w, pr, total; };
 inline NmftRes nmft_res(size_t n, size_t T, size_t D, size_t K, bool vary, bool given_W) {

@@ -22,6 +22,9 @@ from .gppad import (gppad_obj, GppadHandle, GetGPObjFast, GetFFTCovFast, GetTx, 
 from . import nmf_temp  # noqa: F401  (its driver `nmf` is reached as nagp.nmf_temp.nmf: nagp.nmf is the module of the fixed-point NMF)
 from .nmf_temp import nmf_temp_obj, NmfTempHandle, getObj_nmf_temp, getObj_nmf_temp_inf, nmf_inf, nmf_inf_many  # noqa: F401
 from .gppad_cas import (gppad_cas_obj, GppadCasHandle, GetObjCasGPFAST, PackDimsCas, UnpackDimsCas, MAPGPCasFast, CasGPMAP, FBCasGPMAP)  # noqa: F401
+from .gppad_lap import (GppadLapHandle, GetHessian, SigDSigTimesV, LanczosGPPAD, GetEigSigDSig, GetErrorBarGPPAD, GetLaplaceObjGPPADOneChunk,  # noqa: F401
+                        GetLaplaceObjGPPAD, GetLaplaceObjGPPADMulti, GetLaplaceObjGPPADStitched, GetLenGridSearch, GetLenGradAscent, FBGPMAPLearnLen,
+                        InferAmplitudeErrorBarsGPMAP, LoadLearnLenGradAscentGPPADOpts, LoadErrorBarsLapOpts)
 from . import tnmf  # noqa: F401  (its drivers are reached as nagp.tnmf.tnmf and nagp.tnmf.tnmf_inf: no top-level function shadows the module)
 from .tnmf import (basis2SEGP, getObj_fitSE_basis_func, getObj_nmf_log_norm, getObj_nmf_log_norm_inf, tnmf_obj, TnmfHandle, sebf_fit_obj,  # noqa: F401
                    SebfFitHandle, fitSEGP_BF, fitSEGP_BF_many, randtnmf)

@@ -85,7 +85,9 @@ EXPORTS = ['nagp_version', 'nagp_device_count', 'nagp_strerror', 'nagp_last_erro
            'nagp_nmf_temp_obj', 'nagp_nmf_temp_create', 'nagp_nmf_temp_eval', 'nagp_nmf_temp_destroy', 'nagp_nmf_temp_timings',
            'nagp_sebf_conv', 'nagp_sebf_fit_obj', 'nagp_sebf_fit_create', 'nagp_sebf_fit_eval', 'nagp_sebf_fit_destroy',
            'nagp_tnmf_obj', 'nagp_tnmf_create', 'nagp_tnmf_eval', 'nagp_tnmf_destroy', 'nagp_tnmf_timings',
-           'nagp_gppad_cas_obj', 'nagp_gppad_cas_create', 'nagp_gppad_cas_eval', 'nagp_gppad_cas_destroy', 'nagp_gppad_cas_timings']
+           'nagp_gppad_cas_obj', 'nagp_gppad_cas_create', 'nagp_gppad_cas_eval', 'nagp_gppad_cas_destroy', 'nagp_gppad_cas_timings',
+           'nagp_gppad_lap_create', 'nagp_gppad_lap_hess', 'nagp_gppad_lap_apply', 'nagp_gppad_lap_eig', 'nagp_gppad_lap_varx', 'nagp_gppad_lap_obj',
+           'nagp_gppad_lap_destroy', 'nagp_gppad_lap_timings']
 NMFT_NONE, NMFT_TG, NMFT_IG = 0, 1, 2
 
 
@@ -248,6 +250,16 @@ def lib():
     L.nagp_gppad_cas_eval.argtypes = [C.c_void_p, c_dp, c_dp, c_dp]; L.nagp_gppad_cas_eval.restype = C.c_int
     L.nagp_gppad_cas_destroy.argtypes = [C.c_void_p]; L.nagp_gppad_cas_destroy.restype = None
     L.nagp_gppad_cas_timings.argtypes = [c_dp]; L.nagp_gppad_cas_timings.restype = C.c_int
+    L.nagp_gppad_lap_create.argtypes = [C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, c_dp, c_dp, C.c_int64, c_dp, c_dp, c_dp, c_dp, C.c_int32, C.c_int32]
+    L.nagp_gppad_lap_hess.argtypes = [C.c_void_p, c_dp, c_dp]
+    L.nagp_gppad_lap_apply.argtypes = [C.c_void_p, c_dp, c_dp]
+    L.nagp_gppad_lap_eig.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_double, c_dp, c_dp, c_ip, c_ip, c_dp, c_dp]
+    L.nagp_gppad_lap_varx.argtypes = [C.c_void_p, C.c_int32, c_dp, c_dp, c_dp, c_lp]
+    L.nagp_gppad_lap_obj.argtypes = [C.c_void_p, c_dp]
+    L.nagp_gppad_lap_destroy.argtypes = [C.c_void_p]; L.nagp_gppad_lap_destroy.restype = None
+    L.nagp_gppad_lap_timings.argtypes = [c_dp]
+    for f in ('create', 'hess', 'apply', 'eig', 'varx', 'obj', 'timings'):
+        getattr(L, 'nagp_gppad_lap_' + f).restype = C.c_int
     nmft_data = [c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]                                   # A, vary, W, muinf, varinf, lam
     L.nagp_nmf_temp_obj.argtypes = [C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, c_dp] + nmft_data + [c_dp, c_dp, C.c_int32]
     L.nagp_nmf_temp_obj.restype = C.c_int

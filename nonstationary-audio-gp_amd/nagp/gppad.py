@@ -15,8 +15,9 @@ parameters (500 samples x 250 grid points), the first-level initialisation, resa
 conjugate-gradient line search (minimize.minimize_steps) stay on the host.  There is no CPU fallback: the `evaluator` argument exists so
 that the tests can put the float64 restatement through the same driver.
 
-Not built, and refused with the name of the reference file that would serve them: length-scale learning (LrnLen = 1, 2:
-FBGPMAPLearnLen.m) and the Laplace error bars (outputs 6-8: FBGPMAPLearnLen.m with LoadErrorBarsLapOpts.m).  Cascades (a column of
+Refused here with the name of the reference file that serves them: length-scale learning (LrnLen = 1, 2: FBGPMAPLearnLen.m) and the
+Laplace error bars (outputs 6-8: FBGPMAPLearnLen.m with LoadErrorBarsLapOpts.m).  Both are built in gppad_lap.py under the names of their
+own .m files (FBGPMAPLearnLen, InferAmplitudeErrorBarsGPMAP, GetLenGradAscent, GetLenGridSearch, ...), with explicit randomness.  Cascades (a column of
 length-scales) are built, in gppad_cas.py under the names of their own .m files (FBCasGPMAP, CasGPMAP, MAPGPCasFast, GetObjCasGPFAST);
 GPPAD and FBGPMAP keep refusing a column of length-scales with the name FBCasGPMAP.m.
 """
@@ -496,7 +497,7 @@ def GPPAD(Y, len, LrnLen=0, Opts=None, nout=5, evaluator=None, device=0):
     the remaining parameters learned per column -- and GPPAD(Y, Params).  Opts modifies the defaults of LoadLearnMargGPPADOpts.m and
     LoadInferenceGPMAPOpts.m.  nout stands for nargout: more than 5 outputs are the error bars."""
     if LrnLen != 0:
-        raise NotImplementedError('LrnLen = %r: learning the time-scale is FBGPMAPLearnLen.m, which is not built (LrnLen = 0 is)' % (LrnLen,))
+        raise NotImplementedError('LrnLen = %r: learning the time-scale is FBGPMAPLearnLen.m, which this call does not run (LrnLen = 0 is served here; nagp.FBGPMAPLearnLen serves the learning)' % (LrnLen,))
     if nout > 5:
-        raise NotImplementedError('outputs 6-8 (VarX, Aupper, Alower) are the Laplace error bars of FBGPMAPLearnLen.m / LoadErrorBarsLapOpts.m, which are not built')
+        raise NotImplementedError('outputs 6-8 (VarX, Aupper, Alower) are the Laplace error bars of FBGPMAPLearnLen.m / LoadErrorBarsLapOpts.m, which this call does not run (nagp.FBGPMAPLearnLen with nout=8 serves them)')
     return FBGPMAP(Y, len, Opts, evaluator=evaluator, device=device)
