@@ -618,8 +618,11 @@ __device__ __forceinline__ void ih_window_pick(int mid, double r0, double r1, do
 // 4, one more barrier (B3), then the weights from those tables (msp_stage1b).
 // QF (nagp_qform.hpp; the three-barrier schedule only): the form of Q / 2Q / v on wave 0 -- K and PAD fixed in the instantiation the plan
 // picks by its D (qform_pick), or QF_RUNTIME, which serves every D (the remaining padded shapes; every shape under NAGP_IH_QFORM=0).
-// The serial loop of wave 1 exists once per link kind, picked ahead of it.  The weights, the link and Q / 2Q / v of this schedule are
-// bit-equal to the forms the other schedules run (gauss_terms, msp_link, msp_qv).
+// The serial loop of wave 1 exists once per link kind, picked ahead of it.  The weights, the exp link and Q / 2Q / v of this schedule are
+// bit-equal to the forms the other schedules run (gauss_terms, msp_link, msp_qv).  The softplus link (softplus_short, nagp_explog.hpp) and
+// the sub-bands' second moment w'Rw (static products, msp_outputs_b) are not: they round differently from link_eval and msp_outputs, and
+// the schedule's results are held by the multi-precision fixture and the oracle instead (tests/test_ep_fixture.py,
+// tests/test_ihgp_adf_lean_tail.py).
 template <int CD, bool TAB, bool STAMPS = false, int QF = QF_RUNTIME>
 __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -932,6 +935,18 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   int qv_dlim = mc.D - (lane & 1);                   // msr_qv_serial, padded forms
   const bool ls_on = tid - 64 * x.lw >= 0 && tid - 64 * x.lw < CD * mc.nd;      // this lane's part in the link tables (msp_link)
   if constexpr (NB1) asm volatile("" : "+v"(ls_shift), "+v"(qv_dlim));
+  // NB1: the address of the reduced sums as ONE register holding the whole address, so that the paired reads of msp_outputs_b reach every
+  // sum through their 8-bit offsets (with the region's constant offset left outside the register, each pair took an address addition)
+  msp_rp accp = x.accp;
+  if constexpr (NB1) asm volatile("" : "+v"(accp));
+  // NB1, wave 0: the static products of the second-moment contraction (msp_outputs_b), CD (CD + 1) / 2 registers of this copy of the loop
+  // for the whole launch (zero on a lane without a sub-band)
+  double pw[(NB1 && WT == 0) ? CD * (CD + 1) / 2 : 1] = {0.0};
+  if constexpr (NB1 && WT == 0) {
+    msp_wproducts<CD>(wrow, (ip.dbg_wave & 64) != 0, pw);
+#pragma unroll
+    for (int q = 0; q < CD * (CD + 1) / 2; ++q) asm volatile("" : "+v"(pw[q]));
+  }
   // NB1: the cubature's inputs of a step straight behind its head, each from this wave's own fmu / HPH stores (msp_wave_fence)
   auto qv_or_link = [&]() __attribute__((always_inline)) {
     msp_wave_fence();
@@ -989,7 +1004,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
         msp_wave_fence();
         if (act) {
           double Z, d1, d2;
-          if constexpr (NB1) msp_outputs_b<CD, WT == 0>(x.accp, n - D, wr, pEP1, mc.jitter, Z, d1, d2);
+          if constexpr (NB1) msp_outputs_b<CD, WT == 0>(accp, n - D, wr, pw, pEP1, mc.jitter, Z, d1, d2);
           else msp_outputs<CD>(x.accp, sub, n - D, wr, pEP1, mc.jitter, Z, d1, d2);
           if (stamp) { asm volatile("" :: "v"(d2)); IH_STAMP(4); }
           if constexpr (!NB1) { t_old = p_tt[ko]; n_old = p_tn[ko]; }

@@ -285,10 +285,12 @@ __device__ __forceinline__ void msp_link(const X& x, const MomCfg& c) {
     x.a_out[0] = lk; x.a_out[MSP_TS] = xg; x.a_out[2 * MSP_TS] = xg * xg - inv;   // :79
   }
 }
-// msp_link on serial wave 1 of the three-barrier schedule of ihgp_adf8_kernel: the same operations on the same operands (the same bits),
-// with the link's kind a constant of the loop's copy (LK), its shift and the lane's part in the tables (on = its lane index < CD nd) in
-// registers set ahead of the loop -- the chain reads no kernel argument, whose scalar load would wait for every LDS operation in flight --
-// and exp / log as written out in nagp_explog.hpp (the argument of the log is 1 + exp(.) >= 1).
+// msp_link on serial wave 1 of the three-barrier schedule of ihgp_adf8_kernel, with the link's kind a constant of the loop's copy (LK),
+// its shift and the lane's part in the tables (on = its lane index < CD nd) in registers set ahead of the loop -- the chain reads no
+// kernel argument, whose scalar load would wait for every LDS operation in flight.  The exp link is msp_link's operation for operation
+// (exp_any, nagp_explog.hpp: the same bits).  The softplus is softplus_short: max(x, 0) + log1p(exp(-|x|)), which never rounds
+// 1 + exp(x) -- about forty instructions fewer than the library's double-double log behind an exp, and closer to the true value than
+// link_eval's log(1 + exp(x)), whose bits it therefore is not (the ADF results are held by the multi-precision fixture instead).
 template <int CD, int LK, class X>
 __device__ __forceinline__ void msr_link_serial(const X& x, bool on, double shift) {
   static_assert(LK == 0 || LK == 1, "softplus or exp");
@@ -298,7 +300,7 @@ __device__ __forceinline__ void msr_link_serial(const X& x, bool on, double shif
     if (s2 > 1e-150 && s2 < 1e150) { const double rs = rsqrt_nr(s2); sg = s2 * rs; inv = rs * rs; }
     else { sg = sqrt(s2); inv = 1.0 / s2; }
     const double xn = mu + sg * x.xdc;                                   // likModulatorNMFPower.m:34
-    const double lk = (LK == 0) ? log_ge1(1.0 + exp_any(xn - shift)) : exp_any(xn);      // link_eval
+    const double lk = (LK == 0) ? softplus_short(xn - shift) : exp_any(xn);              // link_eval
     const double xg = (xn - mu) * inv;                                   // (xn - mu_g)./s2_g  (:72)
     x.a_out[0] = lk; x.a_out[MSP_TS] = xg; x.a_out[2 * MSP_TS] = xg * xg - inv;   // :79
   }
@@ -595,9 +597,24 @@ __device__ __forceinline__ void msp_outputs(msp_rp acc, bool sub, int jmod, cons
 
 // msp_outputs where the lane's kind is a constant of the caller's copy of the loop (the serial waves of the three-barrier schedule of
 // ihgp_adf8_kernel): Z's sum and the lane's own sums -- 27 words at CD = 6 on a sub-band lane, two on a modulator lane -- leave in ONE batch
-// of LDS reads ahead of any arithmetic.  The arithmetic is msp_outputs', operation for operation.
+// of LDS reads ahead of any arithmetic.  A modulator lane's arithmetic is msp_outputs', operation for operation.  A sub-band lane forms
+// w'Rw = sum_q P_q R_q from the lane's static products P (msp_wproducts: W_dj W_dj', doubled off the diagonal, in the order of R's upper
+// triangle): one FMA per entry of R in two chains, where msp_outputs scales and multiplies by the W row twice -- the same sum in exact
+// arithmetic, another order of roundings.  s1 = w'u is msp_outputs'.
+template <int CD>
+__device__ __forceinline__ void msp_wproducts(const double* wrow, bool plain_offdiag, double* pw /* [CD (CD + 1) / 2] */) {
+  int q = 0;
+#pragma unroll
+  for (int j = 0; j < CD; ++j)
+#pragma unroll
+    for (int j2 = j; j2 < CD; ++j2) {
+      // plain_offdiag: developer switch (bit 64 of NAGP_STAMP_WORKER) -- the off-diagonal entries NOT doubled, the wrong table a test shows to fail
+      pw[q] = (j2 == j || plain_offdiag) ? wrow[j] * wrow[j2] : (2.0 * wrow[j]) * wrow[j2];
+      ++q;
+    }
+}
 template <int CD, bool SUB>
-__device__ __forceinline__ void msp_outputs_b(msp_rp acc, int jmod, const double* wrow, double pEP, double jitter,
+__device__ __forceinline__ void msp_outputs_b(msp_rp acc, int jmod, const double* wrow, const double* pw, double pEP, double jitter,
                                               double& Z, double& d1, double& d2) {
   constexpr int nq = CD * (CD + 1) / 2;
   constexpr int NR = SUB ? CD + nq : 2;
@@ -612,7 +629,7 @@ __device__ __forceinline__ void msp_outputs_b(msp_rp acc, int jmod, const double
   asm volatile("" : "+v"(Zs));
 #pragma unroll
   for (int q = 0; q < NR; ++q) asm volatile("" : "+v"(av[q]));
-  Z = pEP * ((Zs > jitter) ? Zs : jitter);          // max(NaN, jitter) = jitter
+  Z = pEP * __builtin_fmax(Zs, jitter);             // (Zs > jitter) ? Zs : jitter as the maximum instruction: max(NaN, jitter) = jitter
   const double Zinv = pEP * rcp_nr(Z);              // Z >= pEP*jitter > 0, finite (or inf: Zinv = NaN like inf/inf)
   double s1, s2;
   if constexpr (SUB) {
@@ -621,14 +638,8 @@ __device__ __forceinline__ void msp_outputs_b(msp_rp acc, int jmod, const double
     for (int j = 0; j < CD; ++j) { if (j & 1) a1 = fma(wrow[j], av[j], a1); else a0 = fma(wrow[j], av[j], a0); }
     s1 = a0 + a1;
     double b0 = 0.0, b1 = 0.0;
-    int q = 0;
 #pragma unroll
-    for (int j = 0; j < CD; ++j) {
-      double t = 0.5 * av[CD + q] * wrow[j]; ++q;
-#pragma unroll
-      for (int j2 = j + 1; j2 < CD; ++j2) { t = fma(av[CD + q], wrow[j2], t); ++q; }
-      if (j & 1) b1 = fma(2.0 * wrow[j], t, b1); else b0 = fma(2.0 * wrow[j], t, b0);
-    }
+    for (int q = 0; q < nq; ++q) { if (q & 1) b1 = fma(pw[q], av[CD + q], b1); else b0 = fma(pw[q], av[CD + q], b0); }
     s2 = b0 + b1;
   } else {
     s1 = av[0]; s2 = av[1];
