@@ -452,6 +452,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
   const size_t BT = (size_t)B * T;
   Bufs& b = p->b;
   b.model = p->d_model;
+  b.md_observed = (o->flags & NAGP_FLAG_MIXTURE_RULE) ? 1 : 0;
   PLAN_TRY(dalloc(p, &p->d_y, BT)); b.y = p->d_y;
   PLAN_TRY(dalloc(p, &b.ttau, BT * sh.M));
   PLAN_TRY(dalloc(p, &b.tnu, BT * sh.M));

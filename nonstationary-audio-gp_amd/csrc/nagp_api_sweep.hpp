@@ -619,8 +619,10 @@ static int exec_gf(nagp_plan* p) {
       const bool ran = (!nlml || itt < I) && (!nlml || itt == 1 || itt < I);
       if (!ran) continue;
       if (itt < I && !nlml) p->nlZ[(size_t)q * I + itt] = -r[0];
-      p->mdM[(size_t)q * I + itt - 1] = r[1];
-      p->mdP[(size_t)q * I + itt - 1] = r[2];
+      // the mixture variant takes both differences inside `if itt < ep_itts` (gf_ep_mods_nmf_mixture.m:260, 287-288): the last sweep leaves 0
+      const bool none = mixture_rule(p) && itt == I;
+      p->mdM[(size_t)q * I + itt - 1] = none ? 0.0 : r[1];
+      p->mdP[(size_t)q * I + itt - 1] = none ? 0.0 : r[2];
     }
   }
   return NAGP_OK;
@@ -759,7 +761,8 @@ static int exec_ihgp(nagp_plan* p) {
       const double sumF = red[(size_t)q * 8], sumS = red[(size_t)q * 8 + 3];
       if (itt == 1) p->nlZ[(size_t)q * I] = -sumF;
       if (itt < I) p->nlZ[(size_t)q * I + itt] = -(sumF + (itt > 1 ? sumS : 0.0));
-      p->mdM[(size_t)q * I + itt - 1] = red[(size_t)q * 8 + 1];
+      // the mixture variant takes maxDiffM inside `if itt < ep_itts` (ihgp_ep_mods_nmf_mixture.m:420, 458): the last sweep leaves 0; maxDiffP (:465) is not gated
+      p->mdM[(size_t)q * I + itt - 1] = (mix && itt == I) ? 0.0 : red[(size_t)q * 8 + 1];
       p->mdP[(size_t)q * I + itt - 1] = red[(size_t)q * 8 + 2];
     }
   }

@@ -1422,7 +1422,7 @@ static __global__ void __launch_bounds__(64) ihgp_scan_kernel(Shape sh, Bufs b, 
       #pragma unroll
       for (int i = 0; i < BS; ++i) if (i < bs) g_MS[(size_t)k * S + o + i] = mreg[i];
       const double mnew = hn * mreg[0];
-      mxM = fmax(mxM, fabs(g_sm[(size_t)k * M + n] - mnew));
+      if (md_counts(b, pb, T, k)) mxM = fmax(mxM, fabs(g_sm[(size_t)k * M + n] - mnew));
       g_sm[(size_t)k * M + n] = mnew;
       g_sv[(size_t)k * M + n] = vlast;
     }
@@ -1666,7 +1666,7 @@ __global__ void __launch_bounds__(256) ihgp_aff_apply_kernel(Shape sh, Bufs b, I
         for (int i = 0; i < BS; ++i)
           if (i < bs) msp[i] = x[i];
         const double mnew = hn * x[0];
-        mxM = fmax(mxM, fabs(b.sm[ix] - mnew));
+        if (md_counts(b, pb, T, k)) mxM = fmax(mxM, fabs(b.sm[ix] - mnew));
         b.sm[ix] = mnew;
         b.sv[ix] = aux;
         if (k == 0) {

@@ -66,7 +66,10 @@ struct Bufs {
   double* state;        // [B][ntiles*16 + S]         scan state (E, e) between chunks; smoothed (P,m) at k=0 for EKF
   double* red;          // [B][8] reduction outputs (sum lZ, maxDiffM, maxDiffP, ...)
   unsigned long long* counters;  // [B][4]
+  int md_observed;      // maxDiffM / maxDiffP over the observed steps only: the mixture variant takes them where it refreshes (gf_ep_mods_nmf_mixture.m:261, 287-288)
 };
+
+__device__ __forceinline__ bool md_counts(const Bufs& b, size_t pb, int64_t T, int64_t k) { return !b.md_observed || !isnan(b.y[pb * T + k]); }
 
 // One window of a time-parallel fixed-site launch: steps [k_warm, k_begin) are the warm-up -- computed, nothing stored --, steps
 // [k_begin, k_end) store as usual.  seed = 0: start at k_warm from the prior (m = 0, P = Pinf; k_warm = 0 is the true start),
@@ -1852,7 +1855,7 @@ __global__ void __launch_bounds__(512) rts_apply_kernel(Shape sh, Bufs b, SpanPa
           const int n = c.own.I[q];
           const size_t ix = ((size_t)pb * T + k) * M + n;
           const double vnew = b.fv[ix] + shv[n] * shv[n] * acc[q][0];
-          mxP = fmax(mxP, fabs(b.sv[ix] - vnew));
+          if (md_counts(b, pb, T, k)) mxP = fmax(mxP, fabs(b.sv[ix] - vnew));
           b.sv[ix] = vnew;
         }
         if (sp.write_PSs || k == 0) {
@@ -1871,7 +1874,7 @@ __global__ void __launch_bounds__(512) rts_apply_kernel(Shape sh, Bufs b, SpanPa
       if (c.myrow == 0) {
         const size_t ix = ((size_t)pb * T + k) * M + c.myblk;
         const double mnew = shv[c.myblk] * ms;
-        mxM = fmax(mxM, fabs(b.sm[ix] - mnew));
+        if (md_counts(b, pb, T, k)) mxM = fmax(mxM, fabs(b.sm[ix] - mnew));
         b.sm[ix] = mnew;
       }
     }

@@ -213,7 +213,7 @@ __global__ void __launch_bounds__(256) rts_apply_mfma_kernel(Shape sh, Bufs b, M
               const double ev_ = (rr == 0) ? E[q][0] : ((rr == 1) ? E[q][1] : ((rr == 2) ? E[q][2] : E[q][3]));
               const size_t ix = ((size_t)pb * T + k) * M + n;
               const double vnew = b.fv[ix] + hv[n] * hv[n] * ev_;
-              mxP = fmax(mxP, fabs(b.sv[ix] - vnew));
+              if (md_counts(b, pb, T, k)) mxP = fmax(mxP, fabs(b.sv[ix] - vnew));
               b.sv[ix] = vnew;
             }
           }
@@ -250,7 +250,7 @@ __global__ void __launch_bounds__(256) rts_apply_mfma_kernel(Shape sh, Bufs b, M
       if (myrow == 0) {
         const size_t ix = ((size_t)pb * T + k) * M + myblk;
         const double mnew = hv[myblk] * ms;
-        mxM = fmax(mxM, fabs(b.sm[ix] - mnew));
+        if (md_counts(b, pb, T, k)) mxM = fmax(mxM, fabs(b.sm[ix] - mnew));
         b.sm[ix] = mnew;
       }
     }

@@ -307,7 +307,7 @@ __global__ void __launch_bounds__(64 * NTL) BIG_REG_CAP(NTL) rts_big_kernel(Shap
               const double ev_ = (rr == 0) ? e[0] : ((rr == 1) ? e[1] : ((rr == 2) ? e[2] : e[3]));
               const size_t ix = ((size_t)pb * T + k) * M + nn;
               const double vnew = b.fv[ix] + hv[nn] * hv[nn] * ev_;
-              mxP = fmax(mxP, fabs(b.sv[ix] - vnew));
+              if (md_counts(b, pb, T, k)) mxP = fmax(mxP, fabs(b.sv[ix] - vnew));
               b.sv[ix] = vnew;
             }
           }
@@ -329,7 +329,7 @@ __global__ void __launch_bounds__(64 * NTL) BIG_REG_CAP(NTL) rts_big_kernel(Shap
           if (myrow == 0) {
             const size_t ix = ((size_t)pb * T + k) * M + myblk;
             const double mnew = hv[myblk] * ms;
-            mxM = fmax(mxM, fabs(b.sm[ix] - mnew));
+            if (md_counts(b, pb, T, k)) mxM = fmax(mxM, fabs(b.sm[ix] - mnew));
             b.sm[ix] = mnew;
           }
         }
