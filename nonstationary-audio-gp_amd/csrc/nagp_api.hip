@@ -79,7 +79,7 @@ struct DevSwitches {
   bool stamps = false;           // NAGP_STAMPS
   bool nmft_valu = false;        // NAGP_NMFT_VALU: the H' dA partial products of nmft_pass_kernel on the VALU instead of the matrix cores
   bool ih_roles = true;          // NAGP_IH_ROLES: off when the value starts with '0'
-  bool ih_tables = false;        // NAGP_IH_TABLES: on when the value starts with '1' (table form of stage 1b in ihgp_adf8_kernel)
+  bool ih_tables = false;        // NAGP_IH_TABLES: on when the value starts with '1' (table form of stage 1b: ihgp_adf8b_kernel)
   bool ih_qform = true;          // NAGP_IH_QFORM: off when the value starts with '0' (every D runs the run-time form of Q / 2Q / v, nagp_qform.hpp)
   int gain_form = 0;            // NAGP_GAIN_FORM: 0 = the plan's rule, 1 = solve, 2 = inv
   // numeric switches (0: not set, unless said otherwise)
@@ -91,7 +91,7 @@ struct DevSwitches {
   enum Budget { FBS, SFB, NMF, PSTFT, SEGP, GPPAD, NMFT, SEBF, N_BUDGETS };
   int budget_mb[N_BUDGETS] = {0, 0, 0, 0, 0, 0, 0, 0};
   int kb_f = 0;                  // NAGP_KB_F (1 .. 16)
-  int ih_kb = 0;                 // NAGP_IH_KB (4, 8 or 16; anything else: not set): depth of the I/O ring of ihgp_adf8_kernel, where it fits
+  int ih_kb = 0;                 // NAGP_IH_KB (4, 8 or 16; anything else: not set): depth of the I/O ring of ihgp_adf8_kernel / ihgp_adf8b_kernel, where it fits
   int filter_dbg = 0;            // NAGP_FILTER_DBG
   int gainm_dbg = 0;             // NAGP_GAINM_DBG
   int stamp_worker = 0;          // NAGP_STAMP_WORKER
@@ -201,7 +201,7 @@ struct nagp_plan {
   int sq_c0 = -1, sq_ok = 0, sq_ih = 0, kb_sq = 16, hph_sq = 1; size_t lds_sq = 0; int sq_ep = 0; size_t lds_ep_sq = 0; int sq_gf = 0;   // likModulatorPreCalcwn in the staged form (nagp_momsq.hpp): centre code, rule fits, IHGP ADF sweep uses it
   int a8_gf = 0, a8_tpt = 1, a8_st = 0, kb_a8 = 16; size_t lds_a8 = 0;   // ADF sweep of the gf filter with role-specialised waves (gf_adf8_kernel)
   int seq_ih = 0;      // developer switch NAGP_IH_SEQ in force: the sequential kernels (general ADF filter, ihgp_scan_kernel) in every sweep instead of the affine scans
-  int sp_ih8 = 0; size_t lds_sp8 = 0;   // the role-specialised 512-thread form of the same sweep (ihgp_adf8_kernel)
+  int sp_ih8 = 0; size_t lds_sp8 = 0;   // the role-specialised 512-thread form of the same sweep (ihgp_adf8_kernel, ihgp_adf8b_kernel)
   int qf_sp = 0;                        // ... its form of Q / 2Q / v on wave 0 (QForm, nagp_qform.hpp; the three-barrier schedule)
   hipStream_t stream = nullptr;
   // chunk-pipelined smoother (gf / giekf): while the sequential filter occupies one CU per problem, the parallel smoother kernels

@@ -165,21 +165,21 @@ static IhFn pick_ih_filter(int mv, bool src, bool bs8) {
     return ihgp_filter_kernel<NAGP_V(V), false>;
   });
 }
-// FORM_SP: ihgp_adf_kernel, or with roles ihgp_adf8_kernel<cd, tab> (cd = 1 .. 7); FORM_SQ: ihgp_adf8sq_kernel (1 .. 6).  stamps (NAGP_STAMPS):
-// the three-barrier schedule (direct form, cd <= 6) has its stamps in instantiations of their own; every other kernel tests the pointer.
+// FORM_SP: ihgp_adf_kernel, or with roles ihgp_adf8_kernel<cd> (the three-barrier schedule: direct form, cd = 1 .. 6) and
+// ihgp_adf8b_kernel<cd, tab> (barrier B1: cd = 7, and the table form at cd = 1 .. 7); FORM_SQ: ihgp_adf8sq_kernel (1 .. 6).  stamps (NAGP_STAMPS):
+// the three-barrier schedule has its stamps in instantiations of their own; every other kernel tests the pointer.
 // qf (nagp_qform.hpp, qform_pick of the plan's D): the form of Q / 2Q / v on wave 0 of that schedule; every other kernel ignores it
 static IhaFn pick_ih_adf(MomForm form, int cd, bool roles, bool tab, bool stamps, int qf) {
   if (form == FORM_SQ) return pick_in<1, 6>(cd, [](auto V) -> IhaFn { return ihgp_adf8sq_kernel<NAGP_V(V)>; });
   return pick_in<1, 7>(cd, [&](auto V) -> IhaFn {
     if (!roles) return ihgp_adf_kernel<NAGP_V(V)>;
-    if (tab) return ihgp_adf8_kernel<NAGP_V(V), true>;
+    if (tab) return ihgp_adf8b_kernel<NAGP_V(V), true>;
     if constexpr (NAGP_V(V) <= 6) {
       return pick_of<QF_K4, QF_K8, QF_K16P, QF_RUNTIME>(qf, [&](auto F) -> IhaFn {
-        if (stamps) return ihgp_adf8_kernel<NAGP_V(V), false, true, NAGP_V(F)>;
-        return ihgp_adf8_kernel<NAGP_V(V), false, false, NAGP_V(F)>;
+        if (stamps) return ihgp_adf8_kernel<NAGP_V(V), true, NAGP_V(F)>;
+        return ihgp_adf8_kernel<NAGP_V(V), false, NAGP_V(F)>;
       });
-    }
-    return ihgp_adf8_kernel<NAGP_V(V), false>;
+    } else return ihgp_adf8b_kernel<NAGP_V(V), false>;
   });
 }
 // the affine scans and the sequential scan: block stride 8 for plans with a block of 5 .. 8 states, else 4; mode as AffPar::mode (0, else 1)

@@ -735,7 +735,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
       if (need() > 156 * 1024) p->hph_sp = 0;
       if (need() <= 156 * 1024) {
         p->sp_ih = 1; p->lds_sp = need();
-        // role-specialised waves: two serial + six worker waves, one sigma point per worker lane, the cubature sums from bin sums (msr_build_desc)
+        // role-specialised waves (ihgp_adf8_kernel; seven components and the table form: ihgp_adf8b_kernel): two serial + six worker waves, one sigma point per worker lane, the cubature sums from bin sums (msr_build_desc)
         // (its workspace is the larger one: where it alone does not fit, it gives up the same residents in the same order -- only one of the
         // two kernels is launched, so the ring and the table setting are that kernel's)
         if (p->sp.bdesc && dev.ih_roles) {

@@ -2,6 +2,9 @@
 //   ihgp_filter_kernel  forward filter with per-channel DARE table look-ups, mean-only recursion
 //                       (matlab/ihgp_ep_modulator_nmf.m:233-310); one workgroup per problem; block n's
 //                       state lives in the registers of thread n, the workgroup cooperates on `mom`.
+//   ihgp_adf_kernel, ihgp_adf8_kernel, ihgp_adf8b_kernel, ihgp_adf8sq_kernel   the ADF sweep of that filter organised around one
+//                       sequential chain: four waves; role-specialised waves in the three-barrier schedule (the product) and in the
+//                       schedule with barrier B1; the same for likModulatorPreCalcwn.  What they share is written once (IhLds .. ih_site_update)
 //   ihgp_scan_kernel    backward mean recursion with looked-up steady-state smoother gains (:373-394)
 // The EP refresh (:397-436) reuses ep_site_kernel (parallel over steps).
 #pragma once
@@ -69,7 +72,8 @@ struct IhgpPar {
   double R_init;     // exp(lik) (or 0 for the constraints variant): initial content of R(:,k)
   int hph_lds;       // filter: keep the H PP H' look-up table [M][NG] in LDS
   int kb;            // steps per I/O block of the filter (LDS ring), <= IH_KB
-  int dbg_wave;      // developer diagnostics (NAGP_STAMPS): which worker's time line goes to stamps[8..15] (NAGP_STAMP_WORKER, default 0)
+  int dbg_wave;      // developer diagnostics (NAGP_STAMP_WORKER, default 0): & 7 which worker's time line goes to stamps[8..15] (NAGP_STAMPS);
+                     // & 32 the serial time line is wave 1's; & 64 the wrong product table of msp_wproducts (a test shows it to fail)
   double w_old, w_new, mom_alpha;   // as FilterPar: (1-d, d, 1) ihgp_ep_modulator_nmf.m:210-211 ; (1-d, d/alpha, alpha) experiments/ihgp_ep_mods_nmf_mixture.m:291-297
 };
 
@@ -341,208 +345,280 @@ __device__ __forceinline__ int nearest_idx3(msp_rp r, int NG, double lr0, double
   return best;
 }
 
+// ---- What the ADF kernels below have in common, written once: ihgp_adf_kernel, ihgp_adf8b_kernel and ihgp_adf8sq_kernel use all of it;
+// the three-barrier ihgp_adf8_kernel the LDS set-up and the lane set-up only (its head, its site update and its ring are its own).
+// Functions of small structs of scalars and pointers, as MsrS / ih_window_pick: a lambda capturing by reference put its state into scratch.
+
+// LDS of one launch, and the scalars every role reads.  tail: doubles between the state map and the cubature's workspace (the square-root
+// kernel's W transposed)
+struct IhLds {
+  double *rMF, *rtt, *rtn, *rR, *rfm, *ry, *rlZ, *rZ;      // the I/O ring
+  double *sW, *fmu, *HPH, *rg, *thph; int* smap; double *tail, *ws;
+  const double *mdl, *tab; double sn2a, pEP1, rmax;
+};
+__device__ __forceinline__ void ih_lds_setup(IhLds& L, double* lds, const Shape& sh, const Bufs& b, const MomCfg& mc, const IhgpTabs& tb, const IhgpPar& ip,
+                                             int CD, int tail, int tid, int NT) {
+  const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG, KB = ip.kb;
+  L.mdl = b.model + (size_t)blockIdx.x * mdl_size(sh);
+  L.tab = tb.base + (size_t)blockIdx.x * itab_size(sh, NG);
+  L.rMF = lds;                                   // ring: m (filtered) [KB][M][4]   (16-byte aligned)
+  L.rtt = L.rMF + (size_t)KB * M * 4;            //       ttau[KB][M]
+  L.rtn = L.rtt + (size_t)KB * M;                //       tnu
+  L.rR = L.rtn + (size_t)KB * M;                 //       R
+  L.rfm = L.rR + (size_t)KB * M;                 //       H*m (filtered)
+  L.ry = L.rfm + (size_t)KB * M;                 //       y[KB]
+  L.rlZ = L.ry + KB;                             //       lZ[KB]
+  L.rZ = L.rlZ + KB;                             //       Z of the step; log taken at the flush
+  L.sW = L.rZ + KB;                              // [D][CD]
+  L.fmu = L.sW + (size_t)D * CD;                 // [68]: M sites, zero padded (stage A of the cubature reads 4*K entries)
+  L.HPH = L.fmu + 68;
+  L.rg = L.HPH + 68;                             // [NG] look-up grid
+  L.thph = L.rg + NG;                            // [M][NG] H PP H' table (ip.hph_lds)
+  L.smap = reinterpret_cast<int*>(L.thph + (ip.hph_lds ? (size_t)M * NG : 0));   // [S] state -> padded ring slot 4*block + row
+  L.tail = reinterpret_cast<double*>(L.smap) + (S + 1) / 2;
+  L.ws = L.tail + tail;
+  for (int i = tid; i < D * CD; i += NT) L.sW[i] = L.mdl[mdl_W(sh) + i];
+  for (int i = tid; i < NG; i += NT) L.rg[i] = tb.r[i];
+  if (ip.hph_lds)
+    for (int i = tid; i < M * NG; i += NT) L.thph[i] = L.tab[itab_hph(sh, NG) + i];
+  for (int i = tid; i < 68; i += NT) { L.fmu[i] = 0.0; L.HPH[i] = 0.0; }
+  for (int i = tid; i < M; i += NT)
+    for (int r = 0; r < sh.bsz[i]; ++r) L.smap[sh.off[i] + r] = 4 * i + r;
+  const double sn2 = L.mdl[mdl_sn2(sh)];
+  L.sn2a = sn2 / ip.mom_alpha;
+  L.pEP1 = mom_pEP(mc, sn2, ip.mom_alpha);
+  L.rmax = tb.r[NG - 1];
+  __syncthreads();
+}
+
+// global rows of this problem
+struct IhRows { const double* yv; double *g_tt, *g_tn, *g_R, *g_lZ, *g_MF, *g_fm; };
+__device__ __forceinline__ void ih_rows(IhRows& G, const Shape& sh, const Bufs& b) {
+  const size_t pT = (size_t)blockIdx.x * sh.T;
+  G.yv = b.y + pT; G.g_lZ = b.lZ + pT;
+  G.g_tt = b.ttau + pT * sh.M; G.g_tn = b.tnu + pT * sh.M; G.g_R = b.R + pT * sh.M; G.g_fm = b.fm + pT * sh.M;
+  G.g_MF = b.MF + pT * sh.S;
+}
+
+// the block ring: steps k0 .. k0+nb-1 in, by the whole workgroup ...
+__device__ __forceinline__ void ih_ring_fill(const IhLds& L, const IhRows& G, int64_t k0, int nb, int M, int tid, int NT) {
+  for (int i = tid; i < nb; i += NT) { L.ry[i] = G.yv[k0 + i]; L.rlZ[i] = G.g_lZ[k0 + i]; L.rZ[i] = -1.0; }
+  for (int i = tid; i < nb * M; i += NT) { L.rtt[i] = G.g_tt[(size_t)k0 * M + i]; L.rtn[i] = G.g_tn[(size_t)k0 * M + i]; }
+  __syncthreads();
+}
+// ... and out (the filtered means through the state map: the flush strips the padding).  The lane index is opaque here: the flush's
+// per-lane addresses are formed where they are used and not carried, as loop invariants, in vector registers across the serial chain
+__device__ __forceinline__ void ih_ring_flush(const IhLds& L, const IhRows& G, int64_t k0, int nb, int M, int S, int lane0, int NT) {
+  const int tid = lane0 + opaque_zero();
+  __syncthreads();
+  for (int i = tid; i < nb; i += NT) G.g_lZ[k0 + i] = (L.rZ[i] < 0.0) ? L.rlZ[i] : log(L.rZ[i]);
+  for (int i = tid; i < nb * M; i += NT) {
+    G.g_tt[(size_t)k0 * M + i] = L.rtt[i]; G.g_tn[(size_t)k0 * M + i] = L.rtn[i]; G.g_R[(size_t)k0 * M + i] = L.rR[i];
+    G.g_fm[(size_t)k0 * M + i] = L.rfm[i];
+  }
+  for (int i = tid; i < nb * S; i += NT) { const int q = i / S, e = i - q * S; G.g_MF[(size_t)k0 * S + i] = L.rMF[(size_t)q * M * 4 + L.smap[e]]; }
+  __syncthreads();
+}
+
+// developer diagnostics (NAGP_STAMPS): one time line, eight slots
+struct IhSt { bool on; unsigned long long a, t[8]; };
+__device__ __forceinline__ void ih_st_start(IhSt& s, bool on) {
+  s.on = on; s.a = 0;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s.t[i] = 0;
+  if (on) s.a = __builtin_readcyclecounter();
+}
+__device__ __forceinline__ void ih_stamp(IhSt& s, int slot) {
+  if (s.on) { const unsigned long long c = __builtin_readcyclecounter(); s.t[slot] += c - s.a; s.a = c; }
+}
+__device__ __forceinline__ void ih_st_store(const IhSt& s, unsigned long long* stamps) {
+  if (s.on)
+    for (int i = 0; i < 8; ++i) stamps[i] += s.t[i];
+}
+
+// The serial lane: wave 0, lane d < D owns sub-band block d; wave 1, lane j < N owns modulator block D + j.  Its state -- the block of A,
+// h, the filtered mean, R of the step before -- and its per-lane ring / table addresses (vector registers; the step index adds an
+// immediate-free scalar offset; the addresses of idle lanes are those of site 0).  wrow[NW]: a sub-band lane's row of W, zero on the
+// other lanes (NW = 0: the kernel has no use for it)
+struct IhLane {
+  bool sub, act; int n;
+  double A4[16], mreg[4], hn, Rprev;
+  msp_wp p_tt, p_tn, p_R, p_fm, p_MF, p_fmu, p_HPH; msp_rp p_hph, p_rg;
+  const double *g_wcol, *g_hph;
+  unsigned int n_clamped;
+};
+template <int NW>
+__device__ __forceinline__ void ih_lane_setup(IhLane& ln, const IhLds& L, const Shape& sh, const Bufs& b, const IhgpPar& ip, int NG, int wave, int lane, double* wrow) {
+  const int S = sh.S, M = sh.M, D = sh.D, pb = blockIdx.x;
+  const int64_t T = sh.T;
+  ln.sub = (wave == 0) && lane < D;
+  ln.act = ln.sub || ((wave == 1) && lane < sh.N);
+  const int n = (wave == 0) ? lane : D + lane;
+  const int nn = ln.act ? n : 0;
+  ln.n = n;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) ln.mreg[i] = 0.0;
+  ln.hn = 0.0;
+#pragma unroll
+  for (int j = 0; j < NW; ++j) wrow[j] = 0.0;
+  tile_zero(ln.A4);
+  if (ln.act) {
+    tile_load(ln.A4, L.mdl + mdl_A(sh) + (size_t)n * 16);
+    ln.hn = L.mdl[mdl_h(sh) + n];
+    const int o = sh.off[n], bs = sh.bsz[n];
+    if (ln.sub) {
+#pragma unroll
+      for (int j = 0; j < NW; ++j) wrow[j] = L.sW[n * NW + j];
+    }
+    if (ip.k_start > 0) {      // continue from the filtered mean of the previous step
+      const double* mp = b.MF + ((size_t)pb * T + (ip.k_start - 1)) * S;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (i < bs) ln.mreg[i] = mp[o + i];
+    } else if (ip.itt > 1) {   // m is NOT reset between sweeps (SURVEY C-22): smoothed mean at k=0
+      const double* ms0 = b.MS + (size_t)pb * T * S;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (i < bs) ln.mreg[i] = ms0[o + i];
+    }
+  }
+  ln.p_tt = (msp_wp)(L.rtt + nn); ln.p_tn = (msp_wp)(L.rtn + nn); ln.p_R = (msp_wp)(L.rR + nn); ln.p_fm = (msp_wp)(L.rfm + nn);
+  ln.p_MF = (msp_wp)(L.rMF + 4 * nn);
+  ln.p_fmu = (msp_wp)(L.fmu + nn); ln.p_HPH = (msp_wp)(L.HPH + nn);
+  ln.p_hph = (msp_rp)(L.thph + (size_t)nn * NG);
+  ln.p_rg = (msp_rp)L.rg + opaque_zero();
+  ln.g_wcol = L.tab + itab_wcol(sh, NG) + (size_t)nn * NG * 4;
+  ln.g_hph = L.tab + itab_hph(sh, NG) + (size_t)nn * NG;
+  ln.Rprev = (ln.act && ip.k_start > 0) ? b.R[((size_t)pb * T + (ip.k_start - 1)) * M + n] : 0.0;
+  ln.n_clamped = 0;
+}
+__device__ __forceinline__ void ih_lane_end(const IhLane& ln, const Bufs& b) {
+  if (ln.act && ln.n_clamped) atomicAdd(&b.counters[(size_t)blockIdx.x * 4 + 1], (unsigned long long)ln.n_clamped);
+}
+
+// Head of step k in the block-ring kernels: table look-up from R of step k-1 (k_pos: k > 0; the tables of k = 0 otherwise), A m, the
+// cubature's inputs fmu and H PP H' (no barrier: the lane's own entries)
+struct IhHead { double hph, wc[4], Am[4], fmun; };
+__device__ __forceinline__ void ih_head(IhLane& ln, IhHead& h, bool k_pos, const Shape& sh, const IhgpTabs& tb, const IhLds& L, const IhgpPar& ip, IhSt& st) {
+  if (!ln.act) return;
+  const int NG = tb.NG;
+  if (k_pos) {
+    const int idx = nearest_idx3(ln.p_rg, NG, tb.lr0, tb.inv_dlr, L.rmax, ln.Rprev);
+    if (st.on) { asm volatile("" :: "v"(idx)); ih_stamp(st, 6); }
+    h.hph = ip.hph_lds ? ln.p_hph[idx] : ln.g_hph[idx];
+    const double2* w = reinterpret_cast<const double2*>(ln.g_wcol + (size_t)idx * 4);
+    const double2 w0 = w[0], w1 = w[1];
+    h.wc[0] = w0.x; h.wc[1] = w0.y; h.wc[2] = w1.x; h.wc[3] = w1.y;
+  } else {
+    h.hph = L.tab[itab_hph0(sh, NG) + ln.n];
+    const double* w = L.tab + itab_wcol0(sh, NG) + (size_t)ln.n * 4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) h.wc[i] = w[i];
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    double a0 = ln.A4[4 * i] * ln.mreg[0], a1 = ln.A4[4 * i + 1] * ln.mreg[1];
+    a0 = fma(ln.A4[4 * i + 2], ln.mreg[2], a0); a1 = fma(ln.A4[4 * i + 3], ln.mreg[3], a1);
+    h.Am[i] = a0 + a1;
+  }
+  h.fmun = ln.hn * h.Am[0];
+  *ln.p_fmu = h.fmun; *ln.p_HPH = h.hph;
+  ih_stamp(st, 7);
+}
+
+// Site update of step k in the block-ring kernels, from the cubature's outputs Z, d1, d2 of this lane's site (msp_outputs, msq_outputs)
+// to the ring stores (slot kk) and R for the look-up of step k+1.  Active lanes only.
+__device__ __forceinline__ void ih_site_update(IhLane& ln, const IhHead& h, const IhgpPar& ip, const IhLds& L, int kk, int M, double Z, double d1, double d2, IhSt& st) {
+  const int ko = kk * M;
+  if (st.on) { asm volatile("" :: "v"(d2)); ih_stamp(st, 4); }
+  const double t_old = ln.p_tt[ko], n_old = ln.p_tn[ko];
+  // site update (:265-266): -d2/(1+d2 HPH), (d1 - fmu d2)/(1+d2 HPH) through one reciprocal
+  const double r1 = rcp_nr(fma(d2, h.hph, 1.0));
+  double tnew = fma(ip.w_new, -d2 * r1, ip.w_old * t_old);
+  const double nnew = fma(ip.w_new, fma(-h.fmun, d2, d1) * r1, ip.w_old * n_old);
+  if (!(tnew > 0.0)) ++ln.n_clamped;
+  tnew = max0(tnew);                                               // :274 (NaN -> 0, C-3)
+  const double Rn = 1.0 / tnew;                                    // R = 1/ttau: the look-up key and an output, exact division
+  // (for tnew > 0 the reference's R(:,k) = 1./ttau before the clamp is this value; otherwise :287 overwrites it with Inf)
+  // R = inf: ttau = 0, or ttau of underflow size (1/ttau overflows while ys = tnu/ttau stays finite): the reference's
+  // (ys - fmu)/(HPH + R) is 0 there; the reciprocal form below would multiply inf by 0
+  double g = 0.0;
+  if (Rn < INFINITY) g = fma(nnew, Rn, -h.fmun) * rcp_nr(h.hph + Rn);  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292)
+  typedef double d2v __attribute__((ext_vector_type(2)));
+  d2v m01, m23;
+  ln.mreg[0] = fma(h.wc[0], g, h.Am[0]); ln.mreg[1] = fma(h.wc[1], g, h.Am[1]); ln.mreg[2] = fma(h.wc[2], g, h.Am[2]); ln.mreg[3] = fma(h.wc[3], g, h.Am[3]);
+  m01.x = ln.mreg[0]; m01.y = ln.mreg[1]; m23.x = ln.mreg[2]; m23.y = ln.mreg[3];
+  ln.p_tt[ko] = tnew; ln.p_tn[ko] = nnew; ln.p_R[ko] = Rn;
+  typedef d2v __attribute__((address_space(3))) * lds_d2p;
+  lds_d2p mf = (lds_d2p)(ln.p_MF + 4 * ko);
+  mf[0] = m01; mf[1] = m23;
+  ln.p_fm[ko] = ln.hn * ln.mreg[0];
+  ln.Rprev = Rn;
+  if (ln.n == 0) L.rZ[kk] = Z;
+  if (st.on) { asm volatile("" :: "v"(ln.Rprev)); ih_stamp(st, 5); }
+}
+
 template <int CD>
 __global__ void __launch_bounds__(MSP_NT) ihgp_adf_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int NT = MSP_NT;
-  const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG;
+  const int S = sh.S, M = sh.M, D = sh.D, KB = ip.kb;
   const int64_t T = sh.T;
-  const int pb = blockIdx.x;
-  const double* mdl = b.model + (size_t)pb * mdl_size(sh);
-  const double* tab = tb.base + (size_t)pb * itab_size(sh, NG);
-
-  const int KB = ip.kb;
-  double* rMF = lds;                                 // ring: m (filtered) [KB][M][4]   (16-byte aligned)
-  double* rtt = rMF + (size_t)KB * M * 4;            //       ttau[KB][M]
-  double* rtn = rtt + (size_t)KB * M;                //       tnu
-  double* rR = rtn + (size_t)KB * M;                 //       R
-  double* rfm = rR + (size_t)KB * M;                 //       H*m (filtered)
-  double* ry = rfm + (size_t)KB * M;                 //       y[KB]
-  double* rlZ = ry + KB;                             //       lZ[KB]
-  double* rZ = rlZ + KB;                             //       Z of the step; log taken at the flush
-  double* sW = rZ + KB;                              // [D][CD]
-  double* fmu = sW + (size_t)D * CD;                 // [68]: M sites, zero padded (stage A of the cubature reads 4*K entries)
-  double* HPH = fmu + 68;
-  double* rg = HPH + 68;                          // [NG] look-up grid
-  double* thph = rg + NG;                            // [M][NG] H PP H' table (ip.hph_lds)
-  int* smap = reinterpret_cast<int*>(thph + (ip.hph_lds ? (size_t)M * NG : 0));   // [S] state -> padded ring slot 4*block + row
-  double* ws = reinterpret_cast<double*>(smap) + (S + 1) / 2;
-  for (int i = tid; i < D * CD; i += NT) sW[i] = mdl[mdl_W(sh) + i];
-  for (int i = tid; i < NG; i += NT) rg[i] = tb.r[i];
-  if (ip.hph_lds)
-    for (int i = tid; i < M * NG; i += NT) thph[i] = tab[itab_hph(sh, NG) + i];
-  for (int i = tid; i < 68; i += NT) { fmu[i] = 0.0; HPH[i] = 0.0; }
-  for (int i = tid; i < M; i += NT)
-    for (int r = 0; r < sh.bsz[i]; ++r) smap[sh.off[i] + r] = 4 * i + r;
-  const double sn2 = mdl[mdl_sn2(sh)];
-  const double sn2a = sn2 / ip.mom_alpha;
-  const double pEP1 = mom_pEP(mc, sn2, ip.mom_alpha);
-  const double rmax = tb.r[NG - 1];
-  __syncthreads();
+  IhLds L;
+  ih_lds_setup(L, lds, sh, b, mc, tb, ip, CD, 0, tid, NT);
+  IhRows G;
+  ih_rows(G, sh, b);
   MspCtx<CD> x;
-  msp_setup<CD>(x, mc, sp, sW, fmu, HPH, ws, 1);
+  msp_setup<CD>(x, mc, sp, L.sW, L.fmu, L.HPH, L.ws, 1);
 
-  // wave 0, lane d < D owns sub-band block d; wave 1, lane j < N owns modulator block D + j
-  const int lane = tid & 63;
-  const bool sub = (wave == 0) && lane < D;
-  const bool act = sub || ((wave == 1) && lane < sh.N);
-  const int n = (wave == 0) ? lane : D + lane;
-  const int nn = act ? n : 0;
-  double A4[16], mreg[4] = {0, 0, 0, 0}, wrow[CD];
-  double hn = 0.0;
-#pragma unroll
-  for (int j = 0; j < CD; ++j) wrow[j] = 0.0;
-  tile_zero(A4);
-  if (act) {
-    tile_load(A4, mdl + mdl_A(sh) + (size_t)n * 16);
-    hn = mdl[mdl_h(sh) + n];
-    const int o = sh.off[n], bs = sh.bsz[n];
-    if (sub) {
-#pragma unroll
-      for (int j = 0; j < CD; ++j) wrow[j] = sW[n * CD + j];
-    }
-    if (ip.k_start > 0) {      // continue from the filtered mean of the previous step
-      const double* mp = b.MF + ((size_t)pb * T + (ip.k_start - 1)) * S;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < bs) mreg[i] = mp[o + i];
-    } else if (ip.itt > 1) {   // m is NOT reset between sweeps (SURVEY C-22): smoothed mean at k=0
-      const double* ms0 = b.MS + (size_t)pb * T * S;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < bs) mreg[i] = ms0[o + i];
-    }
-  }
-  // per-lane ring / table addresses (vector registers; the step index adds an immediate-free scalar offset)
-  const msp_wp p_tt = (msp_wp)(rtt + nn), p_tn = (msp_wp)(rtn + nn), p_R = (msp_wp)(rR + nn), p_fm = (msp_wp)(rfm + nn);
-  const msp_wp p_MF = (msp_wp)(rMF + 4 * nn);
-  const msp_wp p_fmu = (msp_wp)(fmu + nn), p_HPH = (msp_wp)(HPH + nn);
-  const msp_rp p_hph = (msp_rp)(thph + (size_t)nn * NG);
-  const msp_rp p_rg = (msp_rp)rg + opaque_zero();
-  const double* g_wcol = tab + itab_wcol(sh, NG) + (size_t)nn * NG * 4;
-  const double* g_hph = tab + itab_hph(sh, NG) + (size_t)nn * NG;
-  const double* yv = b.y + (size_t)pb * T;
-  double* g_tt = b.ttau + (size_t)pb * T * M;
-  double* g_tn = b.tnu + (size_t)pb * T * M;
-  double* g_R = b.R + (size_t)pb * T * M;
-  double* g_lZ = b.lZ + (size_t)pb * T;
-  double* g_MF = b.MF + (size_t)pb * T * S;
-  double* g_fm = b.fm + (size_t)pb * T * M;
-  double Rprev = (act && ip.k_start > 0) ? b.R[((size_t)pb * T + (ip.k_start - 1)) * M + n] : 0.0;
-  unsigned int n_clamped = 0;
-  unsigned long long st_a = 0, st_b = 0, st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const bool stamp = mc.stamps && tid == 0;      // wave 0's time line
-#define IH_STAMP(slot) do { if (stamp) { st_b = __builtin_readcyclecounter(); st[slot] += st_b - st_a; st_a = st_b; } } while (0)
-
-  // head of step k: table look-up, A m, the cubature's inputs (wave 0, no barrier)
-  double hph = 0.0, wc[4] = {0, 0, 0, 0}, Am[4] = {0, 0, 0, 0}, fmun = 0.0;
-  auto head = [&](int64_t k) {
-    if (act) {
-      if (k > 0) {
-        const int idx = nearest_idx3(p_rg, NG, tb.lr0, tb.inv_dlr, rmax, Rprev);
-        if (stamp) { asm volatile("" :: "v"(idx)); IH_STAMP(6); }
-        hph = ip.hph_lds ? p_hph[idx] : g_hph[idx];
-        const double2* w = reinterpret_cast<const double2*>(g_wcol + (size_t)idx * 4);
-        const double2 w0 = w[0], w1 = w[1];
-        wc[0] = w0.x; wc[1] = w0.y; wc[2] = w1.x; wc[3] = w1.y;
-      } else {
-        hph = tab[itab_hph0(sh, NG) + n];
-        const double* w = tab + itab_wcol0(sh, NG) + (size_t)n * 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) wc[i] = w[i];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        double a0 = A4[4 * i] * mreg[0], a1 = A4[4 * i + 1] * mreg[1];
-        a0 = fma(A4[4 * i + 2], mreg[2], a0); a1 = fma(A4[4 * i + 3], mreg[3], a1);
-        Am[i] = a0 + a1;
-      }
-      fmun = hn * Am[0];
-      *p_fmu = fmun; *p_HPH = hph;
-      if (stamp) { IH_STAMP(7); }
-    }
-  };
-  if (wave <= 1) head(ip.k_start);
+  IhLane ln;
+  double wrow[CD];
+  ih_lane_setup<CD>(ln, L, sh, b, ip, tb.NG, wave, tid & 63, wrow);
+  IhSt st;                                           // wave 0's time line
+  ih_st_start(st, mc.stamps && tid == 0);
+  IhHead h = {0.0, {0, 0, 0, 0}, {0, 0, 0, 0}, 0.0};
+  if (wave <= 1) ih_head(ln, h, ip.k_start > 0, sh, tb, L, ip, st);
   if (wave == 1) { msp_wave_fence(); msp_link<CD>(x, mc); }      // link tables of the first step
-  if (stamp) st_a = __builtin_readcyclecounter();
+  if (st.on) st.a = __builtin_readcyclecounter();
 
   for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
     const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
-    // ---- fill the ring for steps k0 .. k0+nb-1
-    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
-    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
-    __syncthreads();
+    ih_ring_fill(L, G, k0, nb, M, tid, NT);
     for (int kk = 0; kk < nb; ++kk) {
       const int64_t k = k0 + kk;
       lds_barrier();                 // B1: fmu, HPH of step k; its link tables (written by wave 1 on its way here)
-      IH_STAMP(3);
+      ih_stamp(st, 3);
       msp_qv<CD>(x, mc);             // waves 0, 2, 3
       lds_barrier();                 // B2
-      IH_STAMP(0);
-      msp_stageB<CD>(x, mc, ws);
+      ih_stamp(st, 0);
+      msp_stageB<CD>(x, mc, L.ws);
       lds_barrier();                 // B3
-      msp_stage1b<CD>(x, mc, sp, sn2a, ry[kk], ws);
+      msp_stage1b<CD>(x, mc, sp, L.sn2a, L.ry[kk], L.ws);
       lds_barrier();                 // B4
-      IH_STAMP(1);
-      msp_stage2<CD>(x, mc, ws);
+      ih_stamp(st, 1);
+      msp_stage2<CD>(x, mc, L.ws);
       lds_barrier();                 // B5
-      IH_STAMP(2);
+      ih_stamp(st, 2);
       if (wave <= 1) {
         msp_reduce<CD>(x);
         msp_wave_fence();
-        if (act) {
-          const int ko = kk * M;
+        if (ln.act) {
           double Z, d1, d2;
-          msp_outputs<CD>(x.accp, sub, n - D, wrow, pEP1, mc.jitter, Z, d1, d2);
-          if (stamp) { asm volatile("" :: "v"(d2)); IH_STAMP(4); }
-          const double t_old = p_tt[ko], n_old = p_tn[ko];
-          // site update (:265-266): -d2/(1+d2 HPH), (d1 - fmu d2)/(1+d2 HPH) through one reciprocal
-          const double r1 = rcp_nr(fma(d2, hph, 1.0));
-          double tnew = fma(ip.w_new, -d2 * r1, ip.w_old * t_old);
-          const double nnew = fma(ip.w_new, fma(-fmun, d2, d1) * r1, ip.w_old * n_old);
-          if (!(tnew > 0.0)) ++n_clamped;
-          tnew = max0(tnew);                                               // :274 (NaN -> 0, C-3)
-          double Rn = 1.0 / tnew;                                          // R = 1/ttau: the look-up key and an output, exact division
-          // (for tnew > 0 the reference's R(:,k) = 1./ttau before the clamp is this value; otherwise :287 overwrites it with Inf)
-          // R = inf: ttau = 0, or ttau of underflow size (1/ttau overflows while ys = tnu/ttau stays finite): the reference's
-          // (ys - fmu)/(HPH + R) is 0 there; the reciprocal form below would multiply inf by 0
-          double g = 0.0;
-          if (Rn < INFINITY) g = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292)
-          typedef double d2v __attribute__((ext_vector_type(2)));
-          d2v m01, m23;
-          mreg[0] = fma(wc[0], g, Am[0]); mreg[1] = fma(wc[1], g, Am[1]); mreg[2] = fma(wc[2], g, Am[2]); mreg[3] = fma(wc[3], g, Am[3]);
-          m01.x = mreg[0]; m01.y = mreg[1]; m23.x = mreg[2]; m23.y = mreg[3];
-          p_tt[ko] = tnew; p_tn[ko] = nnew; p_R[ko] = Rn;
-          typedef d2v __attribute__((address_space(3))) * lds_d2p;
-          lds_d2p mf = (lds_d2p)(p_MF + 4 * ko);
-          mf[0] = m01; mf[1] = m23;
-          p_fm[ko] = hn * mreg[0];
-          Rprev = Rn;
-          if (n == 0) rZ[kk] = Z;
-          if (stamp) { asm volatile("" :: "v"(Rprev)); IH_STAMP(5); }
+          msp_outputs<CD>(x.accp, ln.sub, ln.n - D, wrow, L.pEP1, mc.jitter, Z, d1, d2);
+          ih_site_update(ln, h, ip, L, kk, M, Z, d1, d2, st);
         }
         if (k + 1 < T) {
-          head(k + 1);
+          ih_head(ln, h, true, sh, tb, L, ip, st);
           if (wave == 1) { msp_wave_fence(); msp_link<CD>(x, mc); }     // fmu / HPH of the modulators just written by this wave
         }
       }
     }
-    // ---- flush the ring
-    __syncthreads();
-    for (int i = tid; i < nb; i += NT) g_lZ[k0 + i] = (rZ[i] < 0.0) ? rlZ[i] : log(rZ[i]);
-    for (int i = tid; i < nb * M; i += NT) {
-      g_tt[(size_t)k0 * M + i] = rtt[i]; g_tn[(size_t)k0 * M + i] = rtn[i]; g_R[(size_t)k0 * M + i] = rR[i];
-      g_fm[(size_t)k0 * M + i] = rfm[i];
-    }
-    for (int i = tid; i < nb * S; i += NT) { const int q = i / S, e = i - q * S; g_MF[(size_t)k0 * S + i] = rMF[(size_t)q * M * 4 + smap[e]]; }
-    __syncthreads();
+    ih_ring_flush(L, G, k0, nb, M, S, tid, NT);
   }
-#undef IH_STAMP
-  if (act && n_clamped) atomicAdd(&b.counters[(size_t)pb * 4 + 1], (unsigned long long)n_clamped);
-  if (stamp)
-    for (int i = 0; i < 8; ++i) mc.stamps[i] += st[i];
+  ih_lane_end(ln, b);
+  ih_st_store(st, mc.stamps);
 }
 
 // The look-up of the three-barrier schedule of ihgp_adf8_kernel in its two halves (nagp_lookup.hpp).  ih_window_reads: the three grid
@@ -569,7 +645,8 @@ __device__ __forceinline__ void ih_window_pick(int mid, double r0, double r1, do
 // The same sweep with role-specialised waves (nagp_momsp.hpp, role layout): 512 threads, waves 0 / 1 as above, waves 2..7 run the
 // parallel stages of the cubature in their own loop.  A wave holds the registers of its role only, which is what lets two
 // waves share a SIMD.
-// Barriers of a step, TAB = false and CD <= 6 (the product, "NB1"): THREE.  B2 | Gaussian weights straight from Q, v and the link tables
+// ihgp_adf8_kernel is the product: the direct form of stage 1b at CD <= 6.  CD = 7 and the table form run ihgp_adf8b_kernel (below).
+// Barriers of a step: THREE.  B2 | Gaussian weights straight from Q, v and the link tables
 // (msr_stage1b_direct); e table (wave 1) | B4 | bin sums; table words of the reduction (serial waves) | B5 | serial tail, head of step
 // k+1, then Q / 2Q / v on wave 0 (msr_qv_serial) and the link tables on wave 1 (msp_link), each from the wave's own fmu / HPH stores.
 // The two serial chains run side by side from B5 to B2; no barrier puts one behind the other.  Without a barrier between the tail of
@@ -583,7 +660,7 @@ __device__ __forceinline__ void ih_window_pick(int mid, double r0, double r1, do
 //                                                                   msr_reduce_tab on the serial waves, B4(k) .. B5(k)
 //   e table                    wave 1, B2 .. B4                     level 2 of msr_sums, B4 .. B5                B5, B2
 //   level-2 results (part)     workers, B4 .. B5                    msr_reduce_bins, behind B5                   B2, B4 of step k+1
-//   c0 / c1 / c2, acc          as in the other schedule             (weights B2 .. B4, level 1 B4 .. B5; acc: one wave)
+//   c0 / c1 / c2, acc          as in ihgp_adf8b_kernel              (weights B2 .. B4, level 1 B4 .. B5; acc: one wave)
 //   wwt (static products)      wave 0, once                         wave 0                                       same lane
 //   W rows, look-up grid, H PP H' table: written ahead of the loop (one __syncthreads), read-only in it -- wave 0 reads its row of W
 //     between B4 and B5, both serial waves three grid words and three table entries round the seed in the site update (one batch of reads)
@@ -611,102 +688,45 @@ __device__ __forceinline__ void ih_window_pick(int mid, double r0, double r1, do
 // the step's barriers.
 // msr_reduce as a whole behind B5 would read l0_j and xg2_j(centre) while wave 1 -- whose tail is the shorter one -- may already be
 // writing the tables of step k+1; hence its split (msr_reduce_tab / msr_reduce_bins).
-// TAB = false, CD = 7 (the 2 x 35 outputs of Q / 2Q / v do not fit the lanes of wave 0) keeps the block ring (fill, KB steps, flush by the
-// whole workgroup round two __syncthreads) and FOUR barriers: B1 | Q / 2Q / v (workers 0..2), link
-// tables (wave 1) | B2 | ... as above with msr_reduce behind B5.  TAB = true (developer switch NAGP_IH_TABLES=1, the form of the
-// four-wave kernel, the in-build cross-check): B1 as for CD = 7; behind B2 the tables e / t1 / ve on wave 1 and q0 / s0 on workers 3 and
-// 4, one more barrier (B3), then the weights from those tables (msp_stage1b).
-// QF (nagp_qform.hpp; the three-barrier schedule only): the form of Q / 2Q / v on wave 0 -- K and PAD fixed in the instantiation the plan
+// QF (nagp_qform.hpp): the form of Q / 2Q / v on wave 0 -- K and PAD fixed in the instantiation the plan
 // picks by its D (qform_pick), or QF_RUNTIME, which serves every D (the remaining padded shapes; every shape under NAGP_IH_QFORM=0).
 // The serial loop of wave 1 exists once per link kind, picked ahead of it.  The weights, the exp link and Q / 2Q / v of this schedule are
 // bit-equal to the forms the other schedules run (gauss_terms, msp_link, msp_qv).  The softplus link (softplus_short, nagp_explog.hpp) and
 // the sub-bands' second moment w'Rw (static products, msp_outputs_b) are not: they round differently from link_eval and msp_outputs, and
 // the schedule's results are held by the multi-precision fixture and the oracle instead (tests/test_ep_fixture.py,
 // tests/test_ihgp_adf_lean_tail.py).
-template <int CD, bool TAB, bool STAMPS = false, int QF = QF_RUNTIME>
+// STAMPS: the stamps are a build of their own, IH_STAMP / WK_STAMP expand to nothing otherwise.
+template <int CD, bool STAMPS = false, int QF = QF_RUNTIME>
 __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
+  static_assert(CD >= 1 && CD <= 6, "the 2 x 35 outputs of Q / 2Q / v at CD = 7 do not fit the lanes of wave 0: ihgp_adf8b_kernel");
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int NT = MSR_NT;
-  constexpr bool NB1 = !TAB && CD <= 6;              // the three-barrier schedule (see above)
-  constexpr bool ST_ON = !NB1 || STAMPS;             // NB1: the stamps are a build of their own (STAMPS), IH_STAMP / WK_STAMP expand to nothing otherwise
-  static_assert(NB1 || !STAMPS, "STAMPS selects among the instantiations of the three-barrier schedule only");
-  static_assert(NB1 || QF == QF_RUNTIME, "QF selects among the instantiations of the three-barrier schedule only");
-  const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG;
+  const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG, KB = ip.kb;
   const int64_t T = sh.T;
-  const int pb = blockIdx.x;
-  const double* mdl = b.model + (size_t)pb * mdl_size(sh);
-  const double* tab = tb.base + (size_t)pb * itab_size(sh, NG);
-
-  const int KB = ip.kb;
-  double* rMF = lds;                                 // ring: m (filtered) [KB][M][4]   (16-byte aligned)
-  double* rtt = rMF + (size_t)KB * M * 4;            //       ttau[KB][M]
-  double* rtn = rtt + (size_t)KB * M;                //       tnu
-  double* rR = rtn + (size_t)KB * M;                 //       R
-  double* rfm = rR + (size_t)KB * M;                 //       H*m (filtered)
-  double* ry = rfm + (size_t)KB * M;                 //       y[KB]
-  double* rlZ = ry + KB;                             //       lZ[KB]
-  double* rZ = rlZ + KB;                             //       Z of the step; log taken at the flush
-  double* sW = rZ + KB;                              // [D][CD]
-  double* fmu = sW + (size_t)D * CD;                 // [68]: M sites, zero padded (stage A of the cubature reads 4*K entries)
-  double* HPH = fmu + 68;
-  double* rg = HPH + 68;                          // [NG] look-up grid
-  double* thph = rg + NG;                            // [M][NG] H PP H' table (ip.hph_lds)
-  int* smap = reinterpret_cast<int*>(thph + (ip.hph_lds ? (size_t)M * NG : 0));   // [S] state -> padded ring slot 4*block + row
-  double* ws = reinterpret_cast<double*>(smap) + (S + 1) / 2;
-  for (int i = tid; i < D * CD; i += NT) sW[i] = mdl[mdl_W(sh) + i];
-  for (int i = tid; i < NG; i += NT) rg[i] = tb.r[i];
-  if (ip.hph_lds)
-    for (int i = tid; i < M * NG; i += NT) thph[i] = tab[itab_hph(sh, NG) + i];
-  for (int i = tid; i < 68; i += NT) { fmu[i] = 0.0; HPH[i] = 0.0; }
-  for (int i = tid; i < M; i += NT)
-    for (int r = 0; r < sh.bsz[i]; ++r) smap[sh.off[i] + r] = 4 * i + r;
-  const double sn2 = mdl[mdl_sn2(sh)];
-  const double sn2a = sn2 / ip.mom_alpha;
-  const double pEP1 = mom_pEP(mc, sn2, ip.mom_alpha);
-  const double rmax = tb.r[NG - 1];
-  __syncthreads();
-  // global rows of this problem (the streamed ring: the I/O lanes of the worker role fill and flush it; the block ring: both roles)
-  const double* yv = b.y + (size_t)pb * T;
-  double* g_tt = b.ttau + (size_t)pb * T * M;
-  double* g_tn = b.tnu + (size_t)pb * T * M;
-  double* g_R = b.R + (size_t)pb * T * M;
-  double* g_lZ = b.lZ + (size_t)pb * T;
-  double* g_MF = b.MF + (size_t)pb * T * S;
-  double* g_fm = b.fm + (size_t)pb * T * M;
-  msr_init(CD, D, ws);
+  IhLds ld;
+  ih_lds_setup(ld, lds, sh, b, mc, tb, ip, CD, 0, tid, NT);
+  IhRows gr;                                         // (the streamed ring: the I/O lanes of the worker role fill and flush it)
+  ih_rows(gr, sh, b);
+  msr_init(CD, D, ld.ws);
   __syncthreads();
   if (wave >= MSR_W0) {
     // ================= worker role: the parallel stages of the cubature; the same barriers as the serial role below
-    const MspLay lay = msp_layout(CD, D, 1);
     MsrW<CD> xw;
-    msr_setup_W<CD>(xw, mc, sp, sW, fmu, HPH, ws, !NB1);
+    msr_setup_W<CD>(xw, mc, sp, ld.sW, ld.fmu, ld.HPH, ld.ws, false);
     // developer diagnostics (NAGP_STAMPS): time lines of worker (NAGP_STAMP_WORKER & 7) in stamps[8..15] and of the last worker in
     // stamps[16..23]
     const int wk_slot = (wave == MSR_W0 + (ip.dbg_wave & 7)) ? 8 : ((wave == MSR_W0 + MSR_NWK - 1) ? 16 : -1);
-    const bool wk_stamp = ST_ON && mc.stamps && wk_slot >= 0 && (tid & 63) == 0;
+    const bool wk_stamp = STAMPS && mc.stamps && wk_slot >= 0 && (tid & 63) == 0;
     unsigned long long wk_a = 0, wk_b = 0, wk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (wk_stamp) wk_a = __builtin_readcyclecounter();
-#define WK_STAMP(slot) do { if constexpr (ST_ON) if (wk_stamp) { wk_b = __builtin_readcyclecounter(); wk[slot] += wk_b - wk_a; wk_a = wk_b; } } while (0)
+#define WK_STAMP(slot) do { if constexpr (STAMPS) if (wk_stamp) { wk_b = __builtin_readcyclecounter(); wk[slot] += wk_b - wk_a; wk_a = wk_b; } } while (0)
     // one step between its barriers; kk = the step's ring slot
     auto wstep = [&](int kk) __attribute__((always_inline)) {
-      if constexpr (!NB1) {
-        lds_barrier();                 // B1
-        WK_STAMP(0);                   // (wait at B1: the serial waves' tail and head)
-        msp_qv<CD>(xw, mc);            // workers 0..2
-        WK_STAMP(1);
-      }
       lds_barrier();                 // B2
-      if constexpr (TAB) {
-        if (wave == MSR_W0 + 3 || wave == MSR_W0 + 4) msr_q0_or_s0(xw, wave == MSR_W0 + 3, ws + lay.q0, ws + lay.s0);
-        lds_barrier();                 // B3
-        WK_STAMP(2);                   // (B2 .. B3: tables on wave 1, q0 / s0 on workers 3, 4)
-        msp_stage1b<CD>(xw, mc, sp, sn2a, ry[kk], ws);
-      } else {
-        WK_STAMP(2);                   // (wait at B2: wave 1's link tables; NB1: the serial waves' tail, head, Q / v and link tables)
-        msr_stage1b_direct<CD, NB1>(xw, sn2a, ry[kk]);
-      }
+      WK_STAMP(2);                   // (wait at B2: the serial waves' tail, head, Q / v and link tables)
+      msr_stage1b_direct<CD, true>(xw, ld.sn2a, ld.ry[kk]);
       WK_STAMP(3);
       lds_barrier();                 // B4
       WK_STAMP(4);
@@ -715,7 +735,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       lds_barrier();                 // B5
       WK_STAMP(7);
     };
-    if constexpr (NB1) {
+    {
       // ---- the streamed ring (see the table above): the I/O lanes are the 256 lanes of waves 2, 3, 6, 7 -- the SIMDs that hold no serial
       // wave.  The lane -> item mapping is static: an LDS address, its stride per slot, a global pointer that advances by one step's row.
       // Outputs of a step: ttau | tnu | R | fm (M each) | MF (S, through smap), at most two per lane; lZ with its log on lane 0 of wave 7.
@@ -733,27 +753,27 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
         const int jj = o_on[t] ? j : 0;
         if (jj < n4) {
           const int a = jj / M, i = jj - a * M;
-          o_l[t] = (msp_rp)((a == 0 ? rtt : a == 1 ? rtn : a == 2 ? rR : rfm) + i);
-          o_g[t] = (a == 0 ? g_tt : a == 1 ? g_tn : a == 2 ? g_R : g_fm) + (size_t)ip.k_start * M + i;
+          o_l[t] = (msp_rp)((a == 0 ? ld.rtt : a == 1 ? ld.rtn : a == 2 ? ld.rR : ld.rfm) + i);
+          o_g[t] = (a == 0 ? gr.g_tt : a == 1 ? gr.g_tn : a == 2 ? gr.g_R : gr.g_fm) + (size_t)ip.k_start * M + i;
           o_ls[t] = M; o_gs[t] = M;
         } else {
           const int e = jj - n4;
-          o_l[t] = (msp_rp)(rMF + smap[e]);
-          o_g[t] = g_MF + (size_t)ip.k_start * S + e;
+          o_l[t] = (msp_rp)(ld.rMF + ld.smap[e]);
+          o_g[t] = gr.g_MF + (size_t)ip.k_start * S + e;
           o_ls[t] = n4; o_gs[t] = S;
         }
       }
       const bool z_on = io && L == 192;
-      double* z_g = g_lZ + ip.k_start;
-      const msp_rp z_r = (msp_rp)rZ, z_l = (msp_rp)rlZ;
+      double* z_g = gr.g_lZ + ip.k_start;
+      const msp_rp z_r = (msp_rp)ld.rZ, z_l = (msp_rp)ld.rlZ;
       const bool i_on = L < 2 * M + 2, i_z = L == 2 * M + 1;
-      msp_wp i_l = (msp_wp)rtt; const double* i_g = g_tt; int i_ls = M, i_gs = M;
+      msp_wp i_l = (msp_wp)ld.rtt; const double* i_g = gr.g_tt; int i_ls = M, i_gs = M;
       if (i_on) {
-        if (L < M) { i_l = (msp_wp)(rtt + L); i_g = g_tt + (size_t)ip.k_start * M + L; }
-        else if (L < 2 * M) { i_l = (msp_wp)(rtn + (L - M)); i_g = g_tn + (size_t)ip.k_start * M + (L - M); }
-        else { i_l = (msp_wp)(L == 2 * M ? ry : rlZ); i_g = (L == 2 * M ? yv : g_lZ) + ip.k_start; i_ls = 1; i_gs = 1; }
+        if (L < M) { i_l = (msp_wp)(ld.rtt + L); i_g = gr.g_tt + (size_t)ip.k_start * M + L; }
+        else if (L < 2 * M) { i_l = (msp_wp)(ld.rtn + (L - M)); i_g = gr.g_tn + (size_t)ip.k_start * M + (L - M); }
+        else { i_l = (msp_wp)(L == 2 * M ? ld.ry : ld.rlZ); i_g = (L == 2 * M ? gr.yv : gr.g_lZ) + ip.k_start; i_ls = 1; i_gs = 1; }
       }
-      const msp_wp i_rz = (msp_wp)rZ;
+      const msp_wp i_rz = (msp_wp)ld.rZ;
       auto flush = [&](int s) __attribute__((always_inline)) {
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -785,25 +805,6 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       }
       __syncthreads();
       if (io && T > ip.k_start) flush((int)((T - 1) & KM));
-    } else {
-  for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
-    const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
-    // ---- fill the ring for steps k0 .. k0+nb-1
-    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
-    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
-    __syncthreads();
-    WK_STAMP(6);                       // (the ring section: from B5 of a block's last step through the flush and the next fill)
-    for (int kk = 0; kk < nb; ++kk) wstep(kk);
-    // ---- flush the ring
-    __syncthreads();
-    for (int i = tid; i < nb; i += NT) g_lZ[k0 + i] = (rZ[i] < 0.0) ? rlZ[i] : log(rZ[i]);
-    for (int i = tid; i < nb * M; i += NT) {
-      g_tt[(size_t)k0 * M + i] = rtt[i]; g_tn[(size_t)k0 * M + i] = rtn[i]; g_R[(size_t)k0 * M + i] = rR[i];
-      g_fm[(size_t)k0 * M + i] = rfm[i];
-    }
-    for (int i = tid; i < nb * S; i += NT) { const int q = i / S, e = i - q * S; g_MF[(size_t)k0 * S + i] = rMF[(size_t)q * M * 4 + smap[e]]; }
-    __syncthreads();
-  }
     }
     if (wk_stamp)
       for (int i = 0; i < 8; ++i) mc.stamps[wk_slot + i] += wk[i];
@@ -812,76 +813,37 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   }
   // ================= serial role (waves 0 and 1)
   MsrS<CD> x;
-  msr_setup_S<CD>(x, mc, sp, fmu, HPH, ws);
-  MsrQ<CD> xq;                                       // NB1: Q / 2Q / v on wave 0
-  MsrRT rt;                                          //      table words of the reduction, read ahead of B5
-  if constexpr (NB1) msr_setup_Q<CD>(xq, mc, sW, fmu, HPH, ws);
+  msr_setup_S<CD>(x, mc, sp, ld.fmu, ld.HPH, ld.ws);
+  MsrQ<CD> xq;                                       // Q / 2Q / v on wave 0
+  MsrRT rt;                                          // table words of the reduction, read ahead of B5
+  msr_setup_Q<CD>(xq, mc, ld.sW, ld.fmu, ld.HPH, ld.ws);
 
-  // NB1: the two serial waves run separate copies of the loop below (WT = 0, 1: the wave index is a constant of the copy), so that each
+  // The two serial waves run separate copies of the loop below (WT = 0, 1: the wave index is a constant of the copy), so that each
   // holds the registers of its own chain only -- wave 0 the W row and the operands of Q / 2Q / v, wave 1 the link chain's constants.
-  // Otherwise (WT = -1) one copy serves both, as before.  Wave 1's copy exists once per link kind (LK = 0, 1: msr_link_serial; LK = -1:
-  // the kind is read where it is used, msp_link).
-  const int wave_rt = wave;
+  // Wave 1's copy exists once per link kind (LK = 0, 1: msr_link_serial; LK = -1: the kind is read where it is used, msp_link).
   auto serial = [&](auto WV, auto LKV) __attribute__((always_inline)) {
   constexpr int WT = decltype(WV)::value, LK = decltype(LKV)::value;
-  const int wave = (WT < 0) ? wave_rt : WT;
-  // wave 0, lane d < D owns sub-band block d; wave 1, lane j < N owns modulator block D + j
+  const int wave = WT;
   const int lane = tid & 63;
-  const bool sub = (wave == 0) && lane < D;
-  const bool act = sub || ((wave == 1) && lane < sh.N);
-  const int n = (wave == 0) ? lane : D + lane;
-  const int nn = act ? n : 0;
-  double A4[16], mreg[4] = {0, 0, 0, 0}, wrow[CD];      // (WT = 0: the W row is read again every step, p_w below)
-  double hn = 0.0;
-#pragma unroll
-  for (int j = 0; j < CD; ++j) wrow[j] = 0.0;
-  tile_zero(A4);
-  if (act) {
-    tile_load(A4, mdl + mdl_A(sh) + (size_t)n * 16);
-    hn = mdl[mdl_h(sh) + n];
-    const int o = sh.off[n], bs = sh.bsz[n];
-    if (sub) {
-#pragma unroll
-      for (int j = 0; j < CD; ++j) wrow[j] = sW[n * CD + j];
-    }
-    if (ip.k_start > 0) {      // continue from the filtered mean of the previous step
-      const double* mp = b.MF + ((size_t)pb * T + (ip.k_start - 1)) * S;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < bs) mreg[i] = mp[o + i];
-    } else if (ip.itt > 1) {   // m is NOT reset between sweeps (SURVEY C-22): smoothed mean at k=0
-      const double* ms0 = b.MS + (size_t)pb * T * S;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < bs) mreg[i] = ms0[o + i];
-    }
-  }
-  // per-lane ring / table addresses (vector registers; the step index adds an immediate-free scalar offset)
-  const msp_wp p_tt = (msp_wp)(rtt + nn), p_tn = (msp_wp)(rtn + nn), p_R = (msp_wp)(rR + nn), p_fm = (msp_wp)(rfm + nn);
-  const msp_wp p_MF = (msp_wp)(rMF + 4 * nn);
-  const msp_wp p_fmu = (msp_wp)(fmu + nn), p_HPH = (msp_wp)(HPH + nn);
-  const msp_rp p_hph = (msp_rp)(thph + (size_t)nn * NG);
-  const msp_rp p_rg = (msp_rp)rg + opaque_zero();
-  const msp_rp p_w = (msp_rp)(sW + (sub ? n : 0) * CD);      // WT = 0: this sub-band's row of W, beside the reads of the reduction
-  const double* g_wcol = tab + itab_wcol(sh, NG) + (size_t)nn * NG * 4;
-  const double* g_hph = tab + itab_hph(sh, NG) + (size_t)nn * NG;
-  double Rprev = (act && ip.k_start > 0) ? b.R[((size_t)pb * T + (ip.k_start - 1)) * M + n] : 0.0;
-  unsigned int n_clamped = 0;
+  IhLane ln;
+  double wrow[CD];      // (WT = 0: the W row is read again every step, p_w below)
+  ih_lane_setup<CD>(ln, ld, sh, b, ip, NG, wave, lane, wrow);
+  const msp_rp p_w = (msp_rp)(ld.sW + (ln.sub ? ln.n : 0) * CD);      // WT = 0: this sub-band's row of W, beside the reads of the reduction
   unsigned long long st_a = 0, st_b = 0, st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const bool stamp = ST_ON && mc.stamps && tid == ((ip.dbg_wave & 32) ? 64 : 0);      // time line of wave 0 (NAGP_STAMP_WORKER & 32: of wave 1)
-#define IH_STAMP(slot) do { if constexpr (ST_ON) if (stamp) { st_b = __builtin_readcyclecounter(); st[slot] += st_b - st_a; st_a = st_b; } } while (0)
+  const bool stamp = STAMPS && mc.stamps && tid == ((ip.dbg_wave & 32) ? 64 : 0);      // time line of wave 0 (NAGP_STAMP_WORKER & 32: of wave 1)
+#define IH_STAMP(slot) do { if constexpr (STAMPS) if (stamp) { st_b = __builtin_readcyclecounter(); st[slot] += st_b - st_a; st_a = st_b; } } while (0)
 
-  // NB1: the look-up's constants live in vector registers from here on, so that the loop reads no kernel argument again
-  double lk_lr0 = tb.lr0, lk_inv = tb.inv_dlr, lk_rmax = rmax;
+  // the look-up's constants live in vector registers from here on, so that the loop reads no kernel argument again
+  double lk_lr0 = tb.lr0, lk_inv = tb.inv_dlr, lk_rmax = ld.rmax;
   int lk_ng2 = NG - 2;
-  if constexpr (NB1) asm volatile("" : "+v"(lk_lr0), "+v"(lk_inv), "+v"(lk_rmax), "+v"(lk_ng2));
+  asm volatile("" : "+v"(lk_lr0), "+v"(lk_inv), "+v"(lk_rmax), "+v"(lk_ng2));
   double lk_c1, lk_c0;                               // the seed from ttau: its two folded constants
   lookup_seed_consts(tb.lr0, tb.inv_dlr, lk_c1, lk_c0);
-  if constexpr (NB1) asm volatile("" : "+v"(lk_c1), "+v"(lk_c0));
+  asm volatile("" : "+v"(lk_c1), "+v"(lk_c0));
   const bool hph_in_lds = ip.hph_lds != 0;
 
   // head of step k: table look-up, A m, the cubature's inputs (wave 0, no barrier).  IN_LOOP: k > 0 is known (the tables of k = 0 are the
-  // prologue's).  NB1: the straight-line look-up (nagp_lookup.hpp) -- one branch, for finite R beyond the grid; the three grid words and,
+  // prologue's).  The straight-line look-up (nagp_lookup.hpp) -- one branch, for finite R beyond the grid; the three grid words and,
   // with the H PP H' table in LDS, its three entries round the seed in ONE batch of LDS reads, the index selects among them.
   // The window of the look-up is seeded from ttau (lookup_mid_ttau_c) in the site update, beside the division R = 1 / ttau: the seed, the
   // address and the reads of the three grid words and, with the H PP H' table in LDS, its three entries are under way when R arrives;
@@ -892,86 +854,246 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   double w_r0 = 0.0, w_r1 = 0.0, w_r2 = 0.0, w_h0 = 0.0, w_h1 = 0.0, w_h2 = 0.0;
   int w_idx = 0;
   auto head = [&](int64_t k, auto IN_LOOP) __attribute__((always_inline)) {
-    if (act) {
+    if (ln.act) {
       if (decltype(IN_LOOP)::value || k > 0) {
         int idx;
-        if constexpr (NB1) {
+        {
           if constexpr (!decltype(IN_LOOP)::value) {
-            w_mid = lookup_mid(lk_ng2, lk_lr0, lk_inv, Rprev);
-            ih_window_reads(p_rg, p_hph, hph_in_lds, w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2);
-            ih_window_pick(w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2, p_rg, p_hph, g_hph, hph_in_lds, lk_rmax, lk_ng2 + 2, Rprev, w_idx, hph);
+            w_mid = lookup_mid(lk_ng2, lk_lr0, lk_inv, ln.Rprev);
+            ih_window_reads(ln.p_rg, ln.p_hph, hph_in_lds, w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2);
+            ih_window_pick(w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2, ln.p_rg, ln.p_hph, ln.g_hph, hph_in_lds, lk_rmax, lk_ng2 + 2, ln.Rprev, w_idx, hph);
           }
           idx = w_idx;      // (IN_LOOP: picked in the site update of the step before)
           if (stamp) { asm volatile("" :: "v"(idx), "v"(hph)); IH_STAMP(6); }
-        } else {
-          idx = nearest_idx3(p_rg, NG, tb.lr0, tb.inv_dlr, rmax, Rprev);
-          if (stamp) { asm volatile("" :: "v"(idx)); IH_STAMP(6); }
-          hph = ip.hph_lds ? p_hph[idx] : g_hph[idx];
         }
-        const double2* w = reinterpret_cast<const double2*>(g_wcol + (size_t)idx * 4);
+        const double2* w = reinterpret_cast<const double2*>(ln.g_wcol + (size_t)idx * 4);
         const double2 w0 = w[0], w1 = w[1];
         wc[0] = w0.x; wc[1] = w0.y; wc[2] = w1.x; wc[3] = w1.y;
       } else {
-        hph = tab[itab_hph0(sh, NG) + n];
-        const double* w = tab + itab_wcol0(sh, NG) + (size_t)n * 4;
+        hph = ld.tab[itab_hph0(sh, NG) + ln.n];
+        const double* w = ld.tab + itab_wcol0(sh, NG) + (size_t)ln.n * 4;
 #pragma unroll
         for (int i = 0; i < 4; ++i) wc[i] = w[i];
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        double a0 = A4[4 * i] * mreg[0], a1 = A4[4 * i + 1] * mreg[1];
-        a0 = fma(A4[4 * i + 2], mreg[2], a0); a1 = fma(A4[4 * i + 3], mreg[3], a1);
+        double a0 = ln.A4[4 * i] * ln.mreg[0], a1 = ln.A4[4 * i + 1] * ln.mreg[1];
+        a0 = fma(ln.A4[4 * i + 2], ln.mreg[2], a0); a1 = fma(ln.A4[4 * i + 3], ln.mreg[3], a1);
         Am[i] = a0 + a1;
       }
-      fmun = hn * Am[0];
-      *p_fmu = fmun; *p_HPH = hph;
+      fmun = ln.hn * Am[0];
+      *ln.p_fmu = fmun; *ln.p_HPH = hph;
       if (stamp) { IH_STAMP(7); }
     }
   };
   if (stamp) st_a = __builtin_readcyclecounter();      // (the prologue's head stamps slots 6 / 7 as the loop's do)
   if (wave <= 1) head(ip.k_start, std::false_type{});
-  // NB1: what the two chains below need of the kernel's arguments is in vector registers from here on, like the look-up's constants
+  // what the two chains below need of the kernel's arguments is in vector registers from here on, like the look-up's constants
   double ls_shift = mc.link_shift;
   int qv_dlim = mc.D - (lane & 1);                   // msr_qv_serial, padded forms
   const bool ls_on = tid - 64 * x.lw >= 0 && tid - 64 * x.lw < CD * mc.nd;      // this lane's part in the link tables (msp_link)
-  if constexpr (NB1) asm volatile("" : "+v"(ls_shift), "+v"(qv_dlim));
-  // NB1: the address of the reduced sums as ONE register holding the whole address, so that the paired reads of msp_outputs_b reach every
+  asm volatile("" : "+v"(ls_shift), "+v"(qv_dlim));
+  // the address of the reduced sums as ONE register holding the whole address, so that the paired reads of msp_outputs_b reach every
   // sum through their 8-bit offsets (with the region's constant offset left outside the register, each pair took an address addition)
   msp_rp accp = x.accp;
-  if constexpr (NB1) asm volatile("" : "+v"(accp));
-  // NB1, wave 0: the static products of the second-moment contraction (msp_outputs_b), CD (CD + 1) / 2 registers of this copy of the loop
+  asm volatile("" : "+v"(accp));
+  // wave 0: the static products of the second-moment contraction (msp_outputs_b), CD (CD + 1) / 2 registers of this copy of the loop
   // for the whole launch (zero on a lane without a sub-band)
-  double pw[(NB1 && WT == 0) ? CD * (CD + 1) / 2 : 1] = {0.0};
-  if constexpr (NB1 && WT == 0) {
+  double pw[(WT == 0) ? CD * (CD + 1) / 2 : 1] = {0.0};
+  if constexpr (WT == 0) {
     msp_wproducts<CD>(wrow, (ip.dbg_wave & 64) != 0, pw);
 #pragma unroll
     for (int q = 0; q < CD * (CD + 1) / 2; ++q) asm volatile("" : "+v"(pw[q]));
   }
-  // NB1: the cubature's inputs of a step straight behind its head, each from this wave's own fmu / HPH stores (msp_wave_fence)
+  // the cubature's inputs of a step straight behind its head, each from this wave's own fmu / HPH stores (msp_wave_fence)
   auto qv_or_link = [&]() __attribute__((always_inline)) {
     msp_wave_fence();
     if (wave == 0) msr_qv_serial<CD, QF>(xq, mc, qv_dlim);
     else if constexpr (LK >= 0) msr_link_serial<CD, LK>(x, ls_on, ls_shift);
     else msp_link<CD>(x, mc);
   };
-  if constexpr (NB1) qv_or_link();
-  // link tables of a step (the exp / log chain of the modulators' sigma-point coordinates, ~1 000 cycles on wave 1): evaluated BEHIND
-  // barrier B1, beside the worker waves' Q / 2Q / v stage -- nothing reads them before the stages behind B2.  (Evaluated
-  // ahead of B1 they were the tail of the serial chain: wave 0 waited ~800 cycles at B1 for them.)  ip.dbg_wave & 16: the old placement.
-  const bool link_early = !NB1 && (ip.dbg_wave & 16) != 0;
-  if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }      // link tables of the first step
+  qv_or_link();
   if (stamp) st_a = __builtin_readcyclecounter();
 
   // one step between its barriers; kk = the step's ring slot
   auto step = [&](const int64_t k, const int kk) __attribute__((always_inline)) {
-      if constexpr (!NB1) {
-        lds_barrier();                 // B1: fmu, HPH of step k; its link tables (written by wave 1 on its way here)
-        IH_STAMP(3);
-        // (Q / 2Q / v: worker waves)
-        if (wave == 1 && !link_early) msp_link<CD>(x, mc);
-      }
-      lds_barrier();                 // B2 (NB1: Q / 2Q / v and the link tables of step k, written by waves 0 and 1 on their way here)
+      lds_barrier();                 // B2 (Q / 2Q / v and the link tables of step k, written by waves 0 and 1 on their way here)
       IH_STAMP(0);
+      {
+        if (wave == 1) msr_etable<CD>(x, mc);      // read behind B4 only (level 2 of msr_sums): beside the workers' weights
+      }
+      // (Gaussian weights: worker waves)
+      lds_barrier();                 // B4
+      IH_STAMP(1);
+      // (bin sums: worker waves)
+      // What the serial tail needs and what exists ahead of B5 is read here, while the workers form the bin sums -- the site's ttau and
+      // tnu of the ring slot (in place since B2, next written by this lane), wave 0's row of W (static), and the link-table words of the
+      // reduction (no reader of the tables is left behind B5).  Every lane reads: the addresses of idle lanes are those of site 0.
+      const int ko = kk * M;
+      double wr[CD], t_old = 0.0, n_old = 0.0;
+      {
+        t_old = ln.p_tt[ko]; n_old = ln.p_tn[ko];
+#pragma unroll
+        for (int j = 0; j < CD; ++j) wr[j] = (WT == 0) ? p_w[j] : 0.0;      // (2 CD registers of wave 0's copy, free again behind the outputs)
+        msr_reduce_tab<CD>(x, rt);
+      }
+      lds_barrier();                 // B5
+      IH_STAMP(2);
+      {
+        msr_reduce_bins<CD>(x, rt);
+        msp_wave_fence();
+        if (ln.act) {
+          double Z, d1, d2;
+          msp_outputs_b<CD, WT == 0>(accp, ln.n - D, wr, pw, ld.pEP1, mc.jitter, Z, d1, d2);
+          if (stamp) { asm volatile("" :: "v"(d2)); IH_STAMP(4); }
+          // site update (:265-266): -d2/(1+d2 HPH), (d1 - fmu d2)/(1+d2 HPH) through one reciprocal
+          const double r1 = rcp_nr(fma(d2, hph, 1.0));
+          double tnew = fma(ip.w_new, -d2 * r1, ip.w_old * t_old);
+          const double nnew = fma(ip.w_new, fma(-fmun, d2, d1) * r1, ip.w_old * n_old);
+          if (!(tnew > 0.0)) ++ln.n_clamped;
+          tnew = max0(tnew);                                               // :274 (NaN -> 0, C-3)
+          {                                                                // beside the division; ahead of the ring stores
+            w_mid = lookup_mid_ttau_c(lk_ng2, lk_c1, lk_c0, tnew);
+            ih_window_reads(ln.p_rg, ln.p_hph, hph_in_lds, w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2);
+          }
+          double Rn = 1.0 / tnew;                                          // R = 1/ttau: the look-up key and an output, exact division
+          // (for tnew > 0 the reference's R(:,k) = 1./ttau before the clamp is this value; otherwise :287 overwrites it with Inf)
+          // R = inf: ttau = 0, or ttau of underflow size (1/ttau overflows while ys = tnu/ttau stays finite): the reference's
+          // (ys - fmu)/(HPH + R) is 0 there; the reciprocal form below would multiply inf by 0
+          double g = 0.0;                                                  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292)
+          {                                                                // by a select: clamped sites are every-step business
+            double gx = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);
+            asm volatile("" : "+v"(gx));
+            g = (Rn < INFINITY) ? gx : 0.0;
+          }
+          typedef double d2v __attribute__((ext_vector_type(2)));
+          d2v m01, m23;
+          ln.mreg[0] = fma(wc[0], g, Am[0]); ln.mreg[1] = fma(wc[1], g, Am[1]); ln.mreg[2] = fma(wc[2], g, Am[2]); ln.mreg[3] = fma(wc[3], g, Am[3]);
+          m01.x = ln.mreg[0]; m01.y = ln.mreg[1]; m23.x = ln.mreg[2]; m23.y = ln.mreg[3];
+          // the look-up of step k+1 from the window read above: ahead of the ring stores, so that the wait for the window takes no store
+          // with it, and behind the gain in program order, so that the window's reads have the division and the gain's chain to return in
+          ih_window_pick(w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2, ln.p_rg, ln.p_hph, ln.g_hph, hph_in_lds, lk_rmax, lk_ng2 + 2, Rn, w_idx, hph);
+          ln.p_tt[ko] = tnew; ln.p_tn[ko] = nnew; ln.p_R[ko] = Rn;
+          typedef d2v __attribute__((address_space(3))) * lds_d2p;
+          lds_d2p mf = (lds_d2p)(ln.p_MF + 4 * ko);
+          mf[0] = m01; mf[1] = m23;
+          ln.p_fm[ko] = ln.hn * ln.mreg[0];
+          ln.Rprev = Rn;
+          if (ln.n == 0) ld.rZ[kk] = Z;
+          if (stamp) { asm volatile("" :: "v"(ln.Rprev)); IH_STAMP(5); }
+        }
+        if (k + 1 < T) {
+          head(k + 1, std::true_type{});
+          qv_or_link(); IH_STAMP(3);      // (slot 3: Q / 2Q / v on wave 0, the link tables on wave 1)
+        }
+      }
+  };
+  {
+    // the streamed ring: the I/O lanes of the worker role fill and flush it; the serial waves only index it by the step's slot
+    __syncthreads();                 // the first step's inputs (prologue of the I/O lanes)
+    for (int64_t k = ip.k_start; k < T; ++k) step(k, (int)(k & (KB - 1)));
+    __syncthreads();                 // the last step's outputs, flushed by the I/O lanes
+  }
+#undef IH_STAMP
+  ih_lane_end(ln, b);
+  if (stamp)
+    for (int i = 0; i < 8; ++i) mc.stamps[i] += st[i];
+  };
+  {
+    using std::integral_constant;
+    if (wave == 0) serial(integral_constant<int, 0>{}, integral_constant<int, -1>{});
+    else if (mc.link_kind == 0) serial(integral_constant<int, 1>{}, integral_constant<int, 0>{});      // (link_eval: 0 softplus, else exp)
+    else serial(integral_constant<int, 1>{}, integral_constant<int, 1>{});
+  }
+}
+
+// The role-specialised sweep with barrier B1 and the block ring (fill, KB steps, flush by the whole workgroup round two __syncthreads):
+// what ihgp_adf8_kernel does not serve.  TAB = false, CD = 7 (the 2 x 35 outputs of Q / 2Q / v do not fit the lanes of wave 0): FOUR
+// barriers, B1 | Q / 2Q / v (workers 0..2), link tables (wave 1) | B2 | weights straight from Q, v and the link tables
+// (msr_stage1b_direct); e table (wave 1) | B4 | bin sums | B5 | msr_reduce, serial tail, head of step k+1.  TAB = true, CD = 1 .. 7
+// (developer switch NAGP_IH_TABLES=1, the form of the four-wave kernel, the in-build cross-check): B1 as above; behind B2 the tables
+// e / t1 / ve on wave 1 and q0 / s0 on workers 3 and 4, one more barrier (B3), then the weights from those tables (msp_stage1b).
+// One copy of the serial loop serves both serial waves; the stamps test the pointer.
+template <int CD, bool TAB>
+__global__ void __launch_bounds__(MSR_NT) ihgp_adf8b_kernel(Shape sh, Bufs b, MomCfg mc, MomSp sp, IhgpTabs tb, IhgpPar ip) {
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  constexpr int NT = MSR_NT;
+  const int S = sh.S, M = sh.M, D = sh.D, KB = ip.kb;
+  const int64_t T = sh.T;
+  IhLds L;
+  ih_lds_setup(L, lds, sh, b, mc, tb, ip, CD, 0, tid, NT);
+  IhRows G;                                          // (both roles fill and flush the ring)
+  ih_rows(G, sh, b);
+  msr_init(CD, D, L.ws);
+  __syncthreads();
+  if (wave >= MSR_W0) {
+    // ================= worker role: the parallel stages of the cubature; the same barriers as the serial role below
+    const MspLay lay = msp_layout(CD, D, 1);
+    MsrW<CD> xw;
+    msr_setup_W<CD>(xw, mc, sp, L.sW, L.fmu, L.HPH, L.ws, true);
+    // developer diagnostics (NAGP_STAMPS): time lines of worker (NAGP_STAMP_WORKER & 7) in stamps[8..15] and of the last worker in
+    // stamps[16..23]
+    const int wk_slot = (wave == MSR_W0 + (ip.dbg_wave & 7)) ? 8 : ((wave == MSR_W0 + MSR_NWK - 1) ? 16 : -1);
+    IhSt wk;
+    ih_st_start(wk, mc.stamps && wk_slot >= 0 && (tid & 63) == 0);
+    for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
+      const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
+      ih_ring_fill(L, G, k0, nb, M, tid, NT);
+      ih_stamp(wk, 6);                 // (the ring section: from B5 of a block's last step through the flush and the next fill)
+      for (int kk = 0; kk < nb; ++kk) {
+        lds_barrier();                 // B1
+        ih_stamp(wk, 0);               // (wait at B1: the serial waves' tail and head)
+        msp_qv<CD>(xw, mc);            // workers 0..2
+        ih_stamp(wk, 1);
+        lds_barrier();                 // B2
+        if constexpr (TAB) {
+          if (wave == MSR_W0 + 3 || wave == MSR_W0 + 4) msr_q0_or_s0(xw, wave == MSR_W0 + 3, L.ws + lay.q0, L.ws + lay.s0);
+          lds_barrier();                 // B3
+          ih_stamp(wk, 2);               // (B2 .. B3: tables on wave 1, q0 / s0 on workers 3, 4)
+          msp_stage1b<CD>(xw, mc, sp, L.sn2a, L.ry[kk], L.ws);
+        } else {
+          ih_stamp(wk, 2);               // (wait at B2: wave 1's link tables)
+          msr_stage1b_direct<CD, false>(xw, L.sn2a, L.ry[kk]);
+        }
+        ih_stamp(wk, 3);
+        lds_barrier();                 // B4
+        ih_stamp(wk, 4);
+        msr_sums(xw);                  // bin sums, then this wave's share of the 40 sums
+        ih_stamp(wk, 5);
+        lds_barrier();                 // B5
+        ih_stamp(wk, 7);
+      }
+      ih_ring_flush(L, G, k0, nb, M, S, tid, NT);
+    }
+    if (wk.on) ih_st_store(wk, mc.stamps + wk_slot);
+    return;
+  }
+  // ================= serial role (waves 0 and 1): one copy of the loop serves both
+  MsrS<CD> x;
+  msr_setup_S<CD>(x, mc, sp, L.fmu, L.HPH, L.ws);
+  IhLane ln;
+  double wrow[CD];
+  ih_lane_setup<CD>(ln, L, sh, b, ip, tb.NG, wave, tid & 63, wrow);
+  IhSt st;                                           // time line of wave 0 (NAGP_STAMP_WORKER & 32: of wave 1)
+  ih_st_start(st, mc.stamps && tid == ((ip.dbg_wave & 32) ? 64 : 0));      // (the prologue's head stamps slots 6 / 7 as the loop's do)
+  IhHead h = {0.0, {0, 0, 0, 0}, {0, 0, 0, 0}, 0.0};
+  ih_head(ln, h, ip.k_start > 0, sh, tb, L, ip, st);
+  if (st.on) st.a = __builtin_readcyclecounter();
+
+  for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
+    const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
+    ih_ring_fill(L, G, k0, nb, M, tid, NT);
+    for (int kk = 0; kk < nb; ++kk) {
+      lds_barrier();                 // B1: fmu, HPH of step k
+      ih_stamp(st, 3);
+      // (Q / 2Q / v: worker waves)
+      // link tables of the step (the exp / log chain of the modulators' sigma-point coordinates, ~1 000 cycles on wave 1): behind B1, beside
+      // the workers' Q / 2Q / v -- nothing reads them before the stages behind B2 (ahead of B1 they were the tail of the serial chain)
+      if (wave == 1) msp_link<CD>(x, mc);
+      lds_barrier();                 // B2
+      ih_stamp(st, 0);
       if constexpr (TAB) {
         if (wave == 1) msp_tables<CD>(x, mc);
         lds_barrier();                 // B3
@@ -980,112 +1102,23 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       }
       // (Gaussian weights: worker waves)
       lds_barrier();                 // B4
-      IH_STAMP(1);
+      ih_stamp(st, 1);
       // (bin sums: worker waves)
-      // NB1: what the serial tail needs and what exists ahead of B5 is read here, while the workers form the bin sums -- the site's ttau and
-      // tnu of the ring slot (in place since B2, next written by this lane), wave 0's row of W (static), and the link-table words of the
-      // reduction (no reader of the tables is left behind B5).  Every lane reads: the addresses of idle lanes are those of site 0.
-      const int ko = kk * M;
-      double wr[CD], t_old = 0.0, n_old = 0.0;
-      if constexpr (NB1) {
-        t_old = p_tt[ko]; n_old = p_tn[ko];
-#pragma unroll
-        for (int j = 0; j < CD; ++j) wr[j] = (WT == 0) ? p_w[j] : 0.0;      // (2 CD registers of wave 0's copy, free again behind the outputs)
-        msr_reduce_tab<CD>(x, rt);
-      }
       lds_barrier();                 // B5
-      IH_STAMP(2);
-      {
-        if constexpr (!NB1) {
-#pragma unroll
-          for (int j = 0; j < CD; ++j) wr[j] = wrow[j];
-        }
-        if constexpr (NB1) msr_reduce_bins<CD>(x, rt); else msr_reduce<CD>(x);
-        msp_wave_fence();
-        if (act) {
-          double Z, d1, d2;
-          if constexpr (NB1) msp_outputs_b<CD, WT == 0>(accp, n - D, wr, pw, pEP1, mc.jitter, Z, d1, d2);
-          else msp_outputs<CD>(x.accp, sub, n - D, wr, pEP1, mc.jitter, Z, d1, d2);
-          if (stamp) { asm volatile("" :: "v"(d2)); IH_STAMP(4); }
-          if constexpr (!NB1) { t_old = p_tt[ko]; n_old = p_tn[ko]; }
-          // site update (:265-266): -d2/(1+d2 HPH), (d1 - fmu d2)/(1+d2 HPH) through one reciprocal
-          const double r1 = rcp_nr(fma(d2, hph, 1.0));
-          double tnew = fma(ip.w_new, -d2 * r1, ip.w_old * t_old);
-          const double nnew = fma(ip.w_new, fma(-fmun, d2, d1) * r1, ip.w_old * n_old);
-          if (!(tnew > 0.0)) ++n_clamped;
-          tnew = max0(tnew);                                               // :274 (NaN -> 0, C-3)
-          if constexpr (NB1) {                                             // beside the division; ahead of the ring stores
-            w_mid = lookup_mid_ttau_c(lk_ng2, lk_c1, lk_c0, tnew);
-            ih_window_reads(p_rg, p_hph, hph_in_lds, w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2);
-          }
-          double Rn = 1.0 / tnew;                                          // R = 1/ttau: the look-up key and an output, exact division
-          // (for tnew > 0 the reference's R(:,k) = 1./ttau before the clamp is this value; otherwise :287 overwrites it with Inf)
-          // R = inf: ttau = 0, or ttau of underflow size (1/ttau overflows while ys = tnu/ttau stays finite): the reference's
-          // (ys - fmu)/(HPH + R) is 0 there; the reciprocal form below would multiply inf by 0
-          double g = 0.0;                                                  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292)
-          if constexpr (NB1) {                                             // by a select: clamped sites are every-step business
-            double gx = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);
-            asm volatile("" : "+v"(gx));
-            g = (Rn < INFINITY) ? gx : 0.0;
-          } else if (Rn < INFINITY) g = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);
-          typedef double d2v __attribute__((ext_vector_type(2)));
-          d2v m01, m23;
-          mreg[0] = fma(wc[0], g, Am[0]); mreg[1] = fma(wc[1], g, Am[1]); mreg[2] = fma(wc[2], g, Am[2]); mreg[3] = fma(wc[3], g, Am[3]);
-          m01.x = mreg[0]; m01.y = mreg[1]; m23.x = mreg[2]; m23.y = mreg[3];
-          // the look-up of step k+1 from the window read above: ahead of the ring stores, so that the wait for the window takes no store
-          // with it, and behind the gain in program order, so that the window's reads have the division and the gain's chain to return in
-          if constexpr (NB1) ih_window_pick(w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2, p_rg, p_hph, g_hph, hph_in_lds, lk_rmax, lk_ng2 + 2, Rn, w_idx, hph);
-          p_tt[ko] = tnew; p_tn[ko] = nnew; p_R[ko] = Rn;
-          typedef d2v __attribute__((address_space(3))) * lds_d2p;
-          lds_d2p mf = (lds_d2p)(p_MF + 4 * ko);
-          mf[0] = m01; mf[1] = m23;
-          p_fm[ko] = hn * mreg[0];
-          Rprev = Rn;
-          if (n == 0) rZ[kk] = Z;
-          if (stamp) { asm volatile("" :: "v"(Rprev)); IH_STAMP(5); }
-        }
-        if (k + 1 < T) {
-          head(k + 1, std::true_type{});
-          if constexpr (NB1) { qv_or_link(); IH_STAMP(3); }      // (slot 3: Q / 2Q / v on wave 0, the link tables on wave 1)
-          else if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }     // fmu / HPH of the modulators just written by this wave
-        }
+      ih_stamp(st, 2);
+      msr_reduce<CD>(x);
+      msp_wave_fence();
+      if (ln.act) {
+        double Z, d1, d2;
+        msp_outputs<CD>(x.accp, ln.sub, ln.n - D, wrow, L.pEP1, mc.jitter, Z, d1, d2);
+        ih_site_update(ln, h, ip, L, kk, M, Z, d1, d2, st);
       }
-  };
-  if constexpr (NB1) {
-    // the streamed ring: the I/O lanes of the worker role fill and flush it; the serial waves only index it by the step's slot
-    __syncthreads();                 // the first step's inputs (prologue of the I/O lanes)
-    for (int64_t k = ip.k_start; k < T; ++k) step(k, (int)(k & (KB - 1)));
-    __syncthreads();                 // the last step's outputs, flushed by the I/O lanes
-  } else {
-  for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
-    const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
-    // ---- fill the ring for steps k0 .. k0+nb-1
-    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
-    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
-    __syncthreads();
-    for (int kk = 0; kk < nb; ++kk) step(k0 + kk, kk);
-    // ---- flush the ring
-    __syncthreads();
-    for (int i = tid; i < nb; i += NT) g_lZ[k0 + i] = (rZ[i] < 0.0) ? rlZ[i] : log(rZ[i]);
-    for (int i = tid; i < nb * M; i += NT) {
-      g_tt[(size_t)k0 * M + i] = rtt[i]; g_tn[(size_t)k0 * M + i] = rtn[i]; g_R[(size_t)k0 * M + i] = rR[i];
-      g_fm[(size_t)k0 * M + i] = rfm[i];
+      if (k0 + kk + 1 < T) ih_head(ln, h, true, sh, tb, L, ip, st);
     }
-    for (int i = tid; i < nb * S; i += NT) { const int q = i / S, e = i - q * S; g_MF[(size_t)k0 * S + i] = rMF[(size_t)q * M * 4 + smap[e]]; }
-    __syncthreads();
+    ih_ring_flush(L, G, k0, nb, M, S, tid, NT);
   }
-  }
-#undef IH_STAMP
-  if (act && n_clamped) atomicAdd(&b.counters[(size_t)pb * 4 + 1], (unsigned long long)n_clamped);
-  if (stamp)
-    for (int i = 0; i < 8; ++i) mc.stamps[i] += st[i];
-  };
-  if constexpr (NB1) {
-    using std::integral_constant;
-    if (wave == 0) serial(integral_constant<int, 0>{}, integral_constant<int, -1>{});
-    else if (mc.link_kind == 0) serial(integral_constant<int, 1>{}, integral_constant<int, 0>{});      // (link_eval: 0 softplus, else exp)
-    else serial(integral_constant<int, 1>{}, integral_constant<int, 1>{});
-  } else serial(std::integral_constant<int, -1>{}, std::integral_constant<int, -1>{});
+  ih_lane_end(ln, b);
+  ih_st_store(st, mc.stamps);
 }
 
 // The role-specialised sweep for likModulatorPreCalcwn (experiments/likModulatorPreCalcwn.m:28-86; nagp_momsq.hpp): 512 threads, waves
@@ -1101,103 +1134,51 @@ __global__ void __launch_bounds__(MSQ_NT) ihgp_adf8sq_kernel(Shape sh, Bufs b, M
   const int tid = threadIdx.x;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int NT = MSQ_NT;
-  const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG;
+  const int S = sh.S, M = sh.M, D = sh.D, KB = ip.kb;
   const int64_t T = sh.T;
-  const int pb = blockIdx.x;
-  const double* mdl = b.model + (size_t)pb * mdl_size(sh);
-  const double* tab = tb.base + (size_t)pb * itab_size(sh, NG);
-
-  const int KB = ip.kb;
-  double* rMF = lds;                                 // ring: m (filtered) [KB][M][4]   (16-byte aligned)
-  double* rtt = rMF + (size_t)KB * M * 4;            //       ttau[KB][M]
-  double* rtn = rtt + (size_t)KB * M;                //       tnu
-  double* rR = rtn + (size_t)KB * M;                 //       R
-  double* rfm = rR + (size_t)KB * M;                 //       H*m (filtered)
-  double* ry = rfm + (size_t)KB * M;                 //       y[KB]
-  double* rlZ = ry + KB;                             //       lZ[KB]
-  double* rZ = rlZ + KB;                             //       Z of the step; log taken at the flush
-  double* sW = rZ + KB;                              // [D][CD]
-  double* fmu = sW + (size_t)D * CD;                 // [68]: M sites, zero padded (stage A of the cubature reads 4*K entries)
-  double* HPH = fmu + 68;
-  double* rg = HPH + 68;                          // [NG] look-up grid
-  double* thph = rg + NG;                            // [M][NG] H PP H' table (ip.hph_lds)
-  int* smap = reinterpret_cast<int*>(thph + (ip.hph_lds ? (size_t)M * NG : 0));   // [S] state -> padded ring slot 4*block + row
-  double* wt = reinterpret_cast<double*>(smap) + (S + 1) / 2;      // [8][64] W transposed for t = W' s2 (stage A)
-  double* ws = wt + 512;
-  for (int i = tid; i < D * CD; i += NT) sW[i] = mdl[mdl_W(sh) + i];
-  for (int i = tid; i < NG; i += NT) rg[i] = tb.r[i];
-  if (ip.hph_lds)
-    for (int i = tid; i < M * NG; i += NT) thph[i] = tab[itab_hph(sh, NG) + i];
-  for (int i = tid; i < 68; i += NT) { fmu[i] = 0.0; HPH[i] = 0.0; }
-  for (int i = tid; i < M; i += NT)
-    for (int r = 0; r < sh.bsz[i]; ++r) smap[sh.off[i] + r] = 4 * i + r;
-  const double sn2 = mdl[mdl_sn2(sh)];
-  const double sn2a = sn2 / ip.mom_alpha;
-  const double pEP1 = mom_pEP(mc, sn2, ip.mom_alpha);
-  const double rmax = tb.r[NG - 1];
-  __syncthreads();
-  // global rows of this problem (both roles fill and flush the ring)
-  const double* yv = b.y + (size_t)pb * T;
-  double* g_tt = b.ttau + (size_t)pb * T * M;
-  double* g_tn = b.tnu + (size_t)pb * T * M;
-  double* g_R = b.R + (size_t)pb * T * M;
-  double* g_lZ = b.lZ + (size_t)pb * T;
-  double* g_MF = b.MF + (size_t)pb * T * S;
-  double* g_fm = b.fm + (size_t)pb * T * M;
-  msq_init<MsqRole>(CD, ws, NT);
+  IhLds L;
+  ih_lds_setup(L, lds, sh, b, mc, tb, ip, CD, 512, tid, NT);      // tail: [8][64] W transposed for t = W' s2 (stage A)
+  IhRows G;                                          // (both roles fill and flush the ring)
+  ih_rows(G, sh, b);
+  msq_init<MsqRole>(CD, L.ws, NT);
   __syncthreads();
   const MsqLay lay = msq_layout<MsqRole>(CD);
   if (wave >= MSR_W0) {
     // ================= worker role: the parallel stages of the cubature; the same barriers as the serial role below
     MsqW<CD, MsqRole> xw;
-    msq_setup_W<CD, MsqRole>(xw, mc, sp.c0, sW, fmu, HPH, ws, wave - MSR_W0, tid - 64 * MSR_W0, wt);
+    msq_setup_W<CD, MsqRole>(xw, mc, sp.c0, L.sW, L.fmu, L.HPH, L.ws, wave - MSR_W0, tid - 64 * MSR_W0, L.tail);
     double amp[2 * MsqRole::NST];
 #pragma unroll
     for (int i = 0; i < 2 * MsqRole::NST; ++i) amp[i] = 0.0;
     // developer diagnostics (NAGP_STAMPS): time lines of worker 0 in stamps[8..15] and of the last worker (marginal sums) in stamps[16..23]
     const int wk_slot = (wave == MSR_W0 + (ip.dbg_wave & 7)) ? 8 : ((wave == MSR_W0 + MSQ_NWK - 1) ? 16 : -1);
-    const bool wk_stamp = mc.stamps && wk_slot >= 0 && (tid & 63) == 0;
-    unsigned long long wk_a = 0, wk_b = 0, wk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (wk_stamp) wk_a = __builtin_readcyclecounter();
-#define WK_STAMP(slot) do { if (wk_stamp) { wk_b = __builtin_readcyclecounter(); wk[slot] += wk_b - wk_a; wk_a = wk_b; } } while (0)
-  for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
-    const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
-    // ---- fill the ring for steps k0 .. k0+nb-1
-    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
-    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
-    __syncthreads();
-    for (int kk = 0; kk < nb; ++kk) {
-      lds_barrier();                 // B1
-      WK_STAMP(0);                   // (wait at B1: the serial waves' tail and head)
-      msq_stageA<CD, MsqRole>(xw);            // worker 0: t = W' s2_z
-      WK_STAMP(1);
-      lds_barrier();                 // B2: link tables (wave 1)
-      msq_stageS<CD, MsqRole>(xw, amp);       // gather, square roots, mu_p
-      WK_STAMP(2);
-      lds_barrier();                 // B3
-      msq_stage1b<CD, MsqRole>(xw, sn2a, ry[kk]);
-      WK_STAMP(3);
-      lds_barrier();                 // B4
-      WK_STAMP(4);
-      WK_STAMP(5);
-      msq_stageS2<CD, MsqRole>(xw, amp);
-      WK_STAMP(6);
-      lds_barrier();                 // B5
-      WK_STAMP(7);
+    IhSt wk;
+    ih_st_start(wk, mc.stamps && wk_slot >= 0 && (tid & 63) == 0);
+    for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
+      const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
+      ih_ring_fill(L, G, k0, nb, M, tid, NT);
+      for (int kk = 0; kk < nb; ++kk) {
+        lds_barrier();                 // B1
+        ih_stamp(wk, 0);               // (wait at B1: the serial waves' tail and head)
+        msq_stageA<CD, MsqRole>(xw);            // worker 0: t = W' s2_z
+        ih_stamp(wk, 1);
+        lds_barrier();                 // B2: link tables (wave 1)
+        msq_stageS<CD, MsqRole>(xw, amp);       // gather, square roots, mu_p
+        ih_stamp(wk, 2);
+        lds_barrier();                 // B3
+        msq_stage1b<CD, MsqRole>(xw, L.sn2a, L.ry[kk]);
+        ih_stamp(wk, 3);
+        lds_barrier();                 // B4
+        ih_stamp(wk, 4);
+        ih_stamp(wk, 5);
+        msq_stageS2<CD, MsqRole>(xw, amp);
+        ih_stamp(wk, 6);
+        lds_barrier();                 // B5
+        ih_stamp(wk, 7);
+      }
+      ih_ring_flush(L, G, k0, nb, M, S, tid, NT);
     }
-    // ---- flush the ring
-    __syncthreads();
-    for (int i = tid; i < nb; i += NT) g_lZ[k0 + i] = (rZ[i] < 0.0) ? rlZ[i] : log(rZ[i]);
-    for (int i = tid; i < nb * M; i += NT) {
-      g_tt[(size_t)k0 * M + i] = rtt[i]; g_tn[(size_t)k0 * M + i] = rtn[i]; g_R[(size_t)k0 * M + i] = rR[i];
-      g_fm[(size_t)k0 * M + i] = rfm[i];
-    }
-    for (int i = tid; i < nb * S; i += NT) { const int q = i / S, e = i - q * S; g_MF[(size_t)k0 * S + i] = rMF[(size_t)q * M * 4 + smap[e]]; }
-    __syncthreads();
-  }
-    if (wk_stamp)
-      for (int i = 0; i < 8; ++i) mc.stamps[wk_slot + i] += wk[i];
-#undef WK_STAMP
+    if (wk.on) ih_st_store(wk, mc.stamps + wk_slot);
     return;
   }
   // ================= serial role (waves 0 and 1)
@@ -1207,164 +1188,54 @@ __global__ void __launch_bounds__(MSQ_NT) ihgp_adf8sq_kernel(Shape sh, Bufs b, M
     const int t = (tl >= 0 && tl < TN) ? tl : 0;
     const int j = t / nd, cc = t - j * nd;
     x.lw = 1; x.xdc = mc.xd[cc];
-    x.a_mu = (msp_rp)(fmu + D + j); x.a_s2 = (msp_rp)(HPH + D + j);
-    x.a_out = (msp_wp)(ws + t);
-    x.accp = (msp_rp)(ws + lay.acc + ((wave == 1) ? 32 : 0)) + opaque_zero();
+    x.a_mu = (msp_rp)(L.fmu + D + j); x.a_s2 = (msp_rp)(L.HPH + D + j);
+    x.a_out = (msp_wp)(L.ws + t);
+    x.accp = (msp_rp)(L.ws + lay.acc + ((wave == 1) ? 32 : 0)) + opaque_zero();
     const int dl = tid & 63;
-    x.partp = (msp_rp)(ws + lay.part + (dl & 15) + 16 * ((dl >> 4) & 1));
+    x.partp = (msp_rp)(L.ws + lay.part + (dl & 15) + 16 * ((dl >> 4) & 1));
   }
   MsqM xm;      // marginal sums of c0 -> g1, g2, Z: the serial waves, idle between B4 and B5, take half of the dimensions each
-  msq_setup_M<CD, MsqRole>(xm, mc, sp.c0, ws, wave);
+  msq_setup_M<CD, MsqRole>(xm, mc, sp.c0, L.ws, wave);
 
-  // wave 0, lane d < D owns sub-band block d; wave 1, lane j < N owns modulator block D + j
-  const int lane = tid & 63;
-  const bool sub = (wave == 0) && lane < D;
-  const bool act = sub || ((wave == 1) && lane < sh.N);
-  const int n = (wave == 0) ? lane : D + lane;
-  const int nn = act ? n : 0;
-  double A4[16], mreg[4] = {0, 0, 0, 0};
-  double hn = 0.0;
-  tile_zero(A4);
-  if (act) {
-    tile_load(A4, mdl + mdl_A(sh) + (size_t)n * 16);
-    hn = mdl[mdl_h(sh) + n];
-    const int o = sh.off[n], bs = sh.bsz[n];
-    if (ip.k_start > 0) {      // continue from the filtered mean of the previous step
-      const double* mp = b.MF + ((size_t)pb * T + (ip.k_start - 1)) * S;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < bs) mreg[i] = mp[o + i];
-    } else if (ip.itt > 1) {   // m is NOT reset between sweeps (SURVEY C-22): smoothed mean at k=0
-      const double* ms0 = b.MS + (size_t)pb * T * S;
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        if (i < bs) mreg[i] = ms0[o + i];
-    }
-  }
-  // per-lane ring / table addresses (vector registers; the step index adds an immediate-free scalar offset)
-  const msp_wp p_tt = (msp_wp)(rtt + nn), p_tn = (msp_wp)(rtn + nn), p_R = (msp_wp)(rR + nn), p_fm = (msp_wp)(rfm + nn);
-  const msp_wp p_MF = (msp_wp)(rMF + 4 * nn);
-  const msp_wp p_fmu = (msp_wp)(fmu + nn), p_HPH = (msp_wp)(HPH + nn);
-  const msp_rp p_hph = (msp_rp)(thph + (size_t)nn * NG);
-  const msp_rp p_rg = (msp_rp)rg + opaque_zero();
-  const double* g_wcol = tab + itab_wcol(sh, NG) + (size_t)nn * NG * 4;
-  const double* g_hph = tab + itab_hph(sh, NG) + (size_t)nn * NG;
-  double Rprev = (act && ip.k_start > 0) ? b.R[((size_t)pb * T + (ip.k_start - 1)) * M + n] : 0.0;
-  unsigned int n_clamped = 0;
-  unsigned long long st_a = 0, st_b = 0, st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  const bool stamp = mc.stamps && tid == ((ip.dbg_wave & 32) ? 64 : 0);      // time line of wave 0 (NAGP_STAMP_WORKER & 32: of wave 1)
-#define IH_STAMP(slot) do { if (stamp) { st_b = __builtin_readcyclecounter(); st[slot] += st_b - st_a; st_a = st_b; } } while (0)
-
-  // head of step k: table look-up, A m, the cubature's inputs (wave 0, no barrier)
-  double hph = 0.0, wc[4] = {0, 0, 0, 0}, Am[4] = {0, 0, 0, 0}, fmun = 0.0;
-  auto head = [&](int64_t k) {
-    if (act) {
-      if (k > 0) {
-        const int idx = nearest_idx3(p_rg, NG, tb.lr0, tb.inv_dlr, rmax, Rprev);
-        if (stamp) { asm volatile("" :: "v"(idx)); IH_STAMP(6); }
-        hph = ip.hph_lds ? p_hph[idx] : g_hph[idx];
-        const double2* w = reinterpret_cast<const double2*>(g_wcol + (size_t)idx * 4);
-        const double2 w0 = w[0], w1 = w[1];
-        wc[0] = w0.x; wc[1] = w0.y; wc[2] = w1.x; wc[3] = w1.y;
-      } else {
-        hph = tab[itab_hph0(sh, NG) + n];
-        const double* w = tab + itab_wcol0(sh, NG) + (size_t)n * 4;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) wc[i] = w[i];
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        double a0 = A4[4 * i] * mreg[0], a1 = A4[4 * i + 1] * mreg[1];
-        a0 = fma(A4[4 * i + 2], mreg[2], a0); a1 = fma(A4[4 * i + 3], mreg[3], a1);
-        Am[i] = a0 + a1;
-      }
-      fmun = hn * Am[0];
-      *p_fmu = fmun; *p_HPH = hph;
-      if (stamp) { IH_STAMP(7); }
-    }
-  };
-  if (wave <= 1) head(ip.k_start);
-  // link tables of a step (the exp / log chain of the modulators' sigma-point coordinates, ~1 000 cycles on wave 1): evaluated BEHIND
-  // barrier B1, beside the worker waves' Q / 2Q / v stage -- nothing reads them before wave 1's own msp_tables behind B2.  (Evaluated
-  // ahead of B1 they were the tail of the serial chain: wave 0 waited ~800 cycles at B1 for them.)  ip.dbg_wave & 16: the old placement.
-  const bool link_early = (ip.dbg_wave & 16) != 0;
-  if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }      // link tables of the first step
-  if (stamp) st_a = __builtin_readcyclecounter();
+  IhLane ln;
+  ih_lane_setup<0>(ln, L, sh, b, ip, tb.NG, wave, tid & 63, nullptr);
+  IhSt st;                                           // time line of wave 0 (NAGP_STAMP_WORKER & 32: of wave 1)
+  ih_st_start(st, mc.stamps && tid == ((ip.dbg_wave & 32) ? 64 : 0));
+  IhHead h = {0.0, {0, 0, 0, 0}, {0, 0, 0, 0}, 0.0};
+  ih_head(ln, h, ip.k_start > 0, sh, tb, L, ip, st);
+  if (st.on) st.a = __builtin_readcyclecounter();
 
   for (int64_t k0 = ip.k_start; k0 < T; k0 += KB) {
     const int nb = (T - k0 < KB) ? (int)(T - k0) : KB;
-    // ---- fill the ring for steps k0 .. k0+nb-1
-    for (int i = tid; i < nb; i += NT) { ry[i] = yv[k0 + i]; rlZ[i] = g_lZ[k0 + i]; rZ[i] = -1.0; }
-    for (int i = tid; i < nb * M; i += NT) { rtt[i] = g_tt[(size_t)k0 * M + i]; rtn[i] = g_tn[(size_t)k0 * M + i]; }
-    __syncthreads();
+    ih_ring_fill(L, G, k0, nb, M, tid, NT);
     for (int kk = 0; kk < nb; ++kk) {
-      const int64_t k = k0 + kk;
-      lds_barrier();                 // B1: fmu, HPH of step k; its link tables (written by wave 1 on its way here)
-      IH_STAMP(3);
+      lds_barrier();                 // B1: fmu, HPH of step k
+      ih_stamp(st, 3);
       // (t = W' s2_z: worker 0)
-      if (wave == 1 && !link_early) msp_link<CD>(x, mc);
+      // link tables of the step (the exp / log chain of the modulators' sigma-point coordinates, ~1 000 cycles on wave 1): behind B1, beside
+      // the workers' stage A -- nothing reads them before the stages behind B2 (ahead of B1 they were the tail of the serial chain)
+      if (wave == 1) msp_link<CD>(x, mc);
       lds_barrier();                 // B2
-      IH_STAMP(0);
+      ih_stamp(st, 0);
       // (gather, square roots, mu_p: worker waves)
       lds_barrier();                 // B3
       // (Gaussian weights: worker waves)
       lds_barrier();                 // B4
-      IH_STAMP(1);
+      ih_stamp(st, 1);
       msq_marginals<CD, MsqRole>(xm);         // (sum c1 a, sum c2 a^2: worker waves)
       lds_barrier();                 // B5
-      IH_STAMP(2);
-      {
-        if (act) {
-          const int ko = kk * M;
-          double Z, d1, d2;
-          msq_outputs<CD, MsqRole>(x.accp, x.partp, sub, n - D, pEP1, mc.jitter, Z, d1, d2);
-          if (stamp) { asm volatile("" :: "v"(d2)); IH_STAMP(4); }
-          const double t_old = p_tt[ko], n_old = p_tn[ko];
-          // site update (:265-266): -d2/(1+d2 HPH), (d1 - fmu d2)/(1+d2 HPH) through one reciprocal
-          const double r1 = rcp_nr(fma(d2, hph, 1.0));
-          double tnew = fma(ip.w_new, -d2 * r1, ip.w_old * t_old);
-          const double nnew = fma(ip.w_new, fma(-fmun, d2, d1) * r1, ip.w_old * n_old);
-          if (!(tnew > 0.0)) ++n_clamped;
-          tnew = max0(tnew);                                               // :274 (NaN -> 0, C-3)
-          double Rn = 1.0 / tnew;                                          // R = 1/ttau: the look-up key and an output, exact division
-          // (for tnew > 0 the reference's R(:,k) = 1./ttau before the clamp is this value; otherwise :287 overwrites it with Inf)
-          // R = inf: ttau = 0, or ttau of underflow size (1/ttau overflows while ys = tnu/ttau stays finite): the reference's
-          // (ys - fmu)/(HPH + R) is 0 there; the reciprocal form below would multiply inf by 0
-          double g = 0.0;
-          if (Rn < INFINITY) g = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292)
-          typedef double d2v __attribute__((ext_vector_type(2)));
-          d2v m01, m23;
-          mreg[0] = fma(wc[0], g, Am[0]); mreg[1] = fma(wc[1], g, Am[1]); mreg[2] = fma(wc[2], g, Am[2]); mreg[3] = fma(wc[3], g, Am[3]);
-          m01.x = mreg[0]; m01.y = mreg[1]; m23.x = mreg[2]; m23.y = mreg[3];
-          p_tt[ko] = tnew; p_tn[ko] = nnew; p_R[ko] = Rn;
-          typedef d2v __attribute__((address_space(3))) * lds_d2p;
-          lds_d2p mf = (lds_d2p)(p_MF + 4 * ko);
-          mf[0] = m01; mf[1] = m23;
-          p_fm[ko] = hn * mreg[0];
-          Rprev = Rn;
-          if (n == 0) rZ[kk] = Z;
-          if (stamp) { asm volatile("" :: "v"(Rprev)); IH_STAMP(5); }
-        }
-        if (k + 1 < T) {
-          head(k + 1);
-          if (wave == 1 && link_early) { msp_wave_fence(); msp_link<CD>(x, mc); }     // fmu / HPH of the modulators just written by this wave
-        }
+      ih_stamp(st, 2);
+      if (ln.act) {
+        double Z, d1, d2;
+        msq_outputs<CD, MsqRole>(x.accp, x.partp, ln.sub, ln.n - D, L.pEP1, mc.jitter, Z, d1, d2);
+        ih_site_update(ln, h, ip, L, kk, M, Z, d1, d2, st);
       }
+      if (k0 + kk + 1 < T) ih_head(ln, h, true, sh, tb, L, ip, st);
     }
-    // ---- flush the ring
-    __syncthreads();
-    for (int i = tid; i < nb; i += NT) g_lZ[k0 + i] = (rZ[i] < 0.0) ? rlZ[i] : log(rZ[i]);
-    for (int i = tid; i < nb * M; i += NT) {
-      g_tt[(size_t)k0 * M + i] = rtt[i]; g_tn[(size_t)k0 * M + i] = rtn[i]; g_R[(size_t)k0 * M + i] = rR[i];
-      g_fm[(size_t)k0 * M + i] = rfm[i];
-    }
-    for (int i = tid; i < nb * S; i += NT) { const int q = i / S, e = i - q * S; g_MF[(size_t)k0 * S + i] = rMF[(size_t)q * M * 4 + smap[e]]; }
-    __syncthreads();
+    ih_ring_flush(L, G, k0, nb, M, S, tid, NT);
   }
-#undef IH_STAMP
-  if (act && n_clamped) atomicAdd(&b.counters[(size_t)pb * 4 + 1], (unsigned long long)n_clamped);
-  if (stamp)
-    for (int i = 0; i < 8; ++i) mc.stamps[i] += st[i];
+  ih_lane_end(ln, b);
+  ih_st_store(st, mc.stamps);
 }
 
 // Backward mean recursion: m <- MF_k + G (m - A MF_k) with (P,G) looked up from R(:,k)

@@ -164,24 +164,30 @@
   P void nagp::ihgp_adf_kernel<5> NAGP_SIG_IHA; P void nagp::ihgp_adf_kernel<6> NAGP_SIG_IHA;                            \
   P void nagp::ihgp_adf_kernel<7> NAGP_SIG_IHA;
 
-// (TAB = false: the direct stage 1b, the product; TAB = true: the table form, developer switch NAGP_IH_TABLES=1)
-#define NAGP_LIST_IHA8T(P, TAB)                                                                                            \
-  P void nagp::ihgp_adf8_kernel<1, TAB> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, TAB> NAGP_SIG_IHA;                \
-  P void nagp::ihgp_adf8_kernel<3, TAB> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, TAB> NAGP_SIG_IHA;                \
-  P void nagp::ihgp_adf8_kernel<5, TAB> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, TAB> NAGP_SIG_IHA;                \
-  P void nagp::ihgp_adf8_kernel<7, TAB> NAGP_SIG_IHA;
-#define NAGP_LIST_IHA8(P) NAGP_LIST_IHA8T(P, false) NAGP_LIST_IHA8T(P, true)
-// the three-barrier schedule (TAB = false, 1..6 components) with the stamps compiled in: the instantiations a plan takes under NAGP_STAMPS
+// the three-barrier schedule (the product: direct stage 1b, 1..6 components), QF_RUNTIME, not stamped
+#define NAGP_LIST_IHA8D(P)                                                                                                 \
+  P void nagp::ihgp_adf8_kernel<1> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2> NAGP_SIG_IHA;                          \
+  P void nagp::ihgp_adf8_kernel<3> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4> NAGP_SIG_IHA;                          \
+  P void nagp::ihgp_adf8_kernel<5> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6> NAGP_SIG_IHA;
+// the schedule with barrier B1: 7 components in the direct form; the table form (developer switch NAGP_IH_TABLES=1), 1..7 components
+#define NAGP_LIST_IHA8B(P)                                                                                                 \
+  P void nagp::ihgp_adf8b_kernel<7, false> NAGP_SIG_IHA;                                                                 \
+  P void nagp::ihgp_adf8b_kernel<1, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8b_kernel<2, true> NAGP_SIG_IHA;            \
+  P void nagp::ihgp_adf8b_kernel<3, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8b_kernel<4, true> NAGP_SIG_IHA;            \
+  P void nagp::ihgp_adf8b_kernel<5, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8b_kernel<6, true> NAGP_SIG_IHA;            \
+  P void nagp::ihgp_adf8b_kernel<7, true> NAGP_SIG_IHA;
+#define NAGP_LIST_IHA8(P) NAGP_LIST_IHA8D(P) NAGP_LIST_IHA8B(P)
+// the three-barrier schedule with the stamps compiled in: the instantiations a plan takes under NAGP_STAMPS
 #define NAGP_LIST_IHA8S(P)                                                                                                 \
-  P void nagp::ihgp_adf8_kernel<1, false, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, false, true> NAGP_SIG_IHA;  \
-  P void nagp::ihgp_adf8_kernel<3, false, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, false, true> NAGP_SIG_IHA;  \
-  P void nagp::ihgp_adf8_kernel<5, false, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, false, true> NAGP_SIG_IHA;
+  P void nagp::ihgp_adf8_kernel<1, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, true> NAGP_SIG_IHA;              \
+  P void nagp::ihgp_adf8_kernel<3, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, true> NAGP_SIG_IHA;              \
+  P void nagp::ihgp_adf8_kernel<5, true> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, true> NAGP_SIG_IHA;
 
 // the three-barrier schedule with K and PAD of Q / 2Q / v fixed (nagp_qform.hpp), plain and stamped: one translation unit per form
 #define NAGP_LIST_IHA8K_S(P, ST, QF)                                                                                        \
-  P void nagp::ihgp_adf8_kernel<1, false, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, false, ST, QF> NAGP_SIG_IHA;  \
-  P void nagp::ihgp_adf8_kernel<3, false, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, false, ST, QF> NAGP_SIG_IHA;  \
-  P void nagp::ihgp_adf8_kernel<5, false, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, false, ST, QF> NAGP_SIG_IHA;
+  P void nagp::ihgp_adf8_kernel<1, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<2, ST, QF> NAGP_SIG_IHA;          \
+  P void nagp::ihgp_adf8_kernel<3, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<4, ST, QF> NAGP_SIG_IHA;          \
+  P void nagp::ihgp_adf8_kernel<5, ST, QF> NAGP_SIG_IHA; P void nagp::ihgp_adf8_kernel<6, ST, QF> NAGP_SIG_IHA;
 #define NAGP_LIST_IHA8K(P, QF) NAGP_LIST_IHA8K_S(P, false, QF) NAGP_LIST_IHA8K_S(P, true, QF)
 #define NAGP_LIST_IHA8K4(P) NAGP_LIST_IHA8K(P, nagp::QF_K4)
 #define NAGP_LIST_IHA8K8(P) NAGP_LIST_IHA8K(P, nagp::QF_K8)

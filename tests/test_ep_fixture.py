@@ -392,7 +392,7 @@ _DIRECT, _TAB, _SEQ0, _SEQ1 = 'table form of stage 1b 0', 'table form of stage 1
 _ROLE = ('a', 'a2', 'b', 'c', 'd')                 # the cases the role layout serves
 IHGP_VARIANTS = {
     'default': ({}, None, CASES[:-1]),                                                      # what each case is there for: see _default_words
-    'tables': ({'NAGP_IH_TABLES': '1'}, [_ROLE8, _TAB], _ROLE),                             # ihgp_adf8_kernel, table form of stage 1b
+    'tables': ({'NAGP_IH_TABLES': '1'}, [_ROLE8, _TAB], _ROLE),                             # ihgp_adf8b_kernel, table form of stage 1b
     'no-roles': ({'NAGP_IH_ROLES': '0'}, [_SP, 'role-specialised waves 0'], _ROLE),         # ihgp_adf_kernel
     'general': ({'NAGP_NO_SPARSE': '1'}, [_NOSP, 'role-specialised waves 0', 'staged form: 0', _SEQ0], CASES[:-1]),      # ihgp_filter_kernel, affine scans behind it
     'ring-4': ({'NAGP_IH_KB': '4'}, [_ROLE8, 'ring 4 steps'], ('a',)),

@@ -275,7 +275,7 @@ def test_kernel_ladders_are_written_once_in_the_kernels_header():
                 'rts_compose_kernel', 'rts_boundary_kernel', 'rts_apply_kernel',
                 'rts_compose_mfma_kernel', 'rts_boundary_mfma_kernel', 'rts_apply_mfma_kernel', 'rts_big_kernel', 'rts_big_phi_kernel',
                 'ep_site_kernel', 'ep_site_sp_kernel', 'ep_site_sq_kernel',
-                'ihgp_filter_kernel', 'ihgp_adf_kernel', 'ihgp_adf8_kernel', 'ihgp_adf8sq_kernel',
+                'ihgp_filter_kernel', 'ihgp_adf_kernel', 'ihgp_adf8_kernel', 'ihgp_adf8b_kernel', 'ihgp_adf8sq_kernel',
                 'ihgp_aff_compose_kernel', 'ihgp_aff_boundary_kernel', 'ihgp_aff_apply_kernel', 'ihgp_scan_kernel']
     named = re.compile(r'\b(%s)\b' % '|'.join(families))
     with_args = re.compile(r'\b(%s)\s*<' % '|'.join(families))

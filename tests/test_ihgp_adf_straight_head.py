@@ -1,7 +1,7 @@
 """The serial tail and head of the three-barrier schedule of ihgp_adf8_kernel (direct form, at most six components): the straight-line
 table look-up (csrc/nagp_lookup.hpp; one branch, for finite R beyond the grid), H PP H' selected from three entries read beside the grid
 words, the outputs' sums in one batch of LDS reads, ttau / tnu / the W row read ahead of B5, the gain of a clamped site by a select, and the
-stamps as instantiations of their own (NAGP_STAMPS).  The arithmetic of a step is unchanged; the table form (NAGP_IH_TABLES=1) keeps the
+stamps as instantiations of their own (NAGP_STAMPS).  The arithmetic of a step is unchanged; the table form (NAGP_IH_TABLES=1, ihgp_adf8b_kernel) keeps the
 earlier code and is the cross-check inside the same build.
 
 The cases through the oracle are chosen for what the look-up meets (counted on the oracle's R, site-steps of D + N sites x T steps):

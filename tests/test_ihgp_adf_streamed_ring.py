@@ -2,7 +2,7 @@
 4 steps is circular, slot k mod kb serves step k.  In the window between B5 of step k and B2 of step k + 1 four worker waves write the
 inputs of step k + 1 into their slot (loaded one window earlier), load the inputs of step k + 2 and flush the outputs of step k - 1; the
 first step is filled ahead of the loop, the last one flushed behind it.  The table form (NAGP_IH_TABLES=1) and seven components keep the
-block ring (fill, kb steps, flush): the table form is the cross-check inside the same build.
+block ring (ihgp_adf8b_kernel: fill, kb steps, flush): the table form is the cross-check inside the same build.
 
 Every case runs through the public interface, asserts (NAGP_STAMPS=1) that the plan chose the role kernel, and is compared with the
 NumPy oracle and with the table form at the tolerances tests/test_gpu_parity.py applies to these sweeps, or bit for bit with another

@@ -1,7 +1,9 @@
-"""Stage 1b of the role-specialised IHGP ADF sweep (ihgp_adf8_kernel, nagp_momsp.hpp) in its two forms:
+"""Stage 1b of the role-specialised IHGP ADF sweep (nagp_momsp.hpp) in its two forms:
 
-  direct (the product)             sum_d a_d mu_d = v . lk_p,   sum_d a_d^2 s2_d = lk_p' Q lk_p      (msr_stage1b_direct)
-  tables (NAGP_IH_TABLES=1)        the same two numbers as centre + deviations: s0 + sum ve, q0 + sum t1 + cross terms (msp_stage1b)
+  direct (the product)             sum_d a_d mu_d = v . lk_p,   sum_d a_d^2 s2_d = lk_p' Q lk_p      (msr_stage1b_direct;
+                                   ihgp_adf8_kernel, at seven components ihgp_adf8b_kernel<7, false>)
+  tables (NAGP_IH_TABLES=1)        the same two numbers as centre + deviations: s0 + sum ve, q0 + sum t1 + cross terms (msp_stage1b;
+                                   ihgp_adf8b_kernel<CD, true>)
 
 with Q = W' diag(s2) W, v = W' mu and lk_p the link values at the coordinates of sigma point p (likModulatorNMFPower.m:44-47).
 

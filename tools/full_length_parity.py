@@ -7,7 +7,7 @@ chunk-pipelined schedule, the parallel-in-time scans -- against the COMPILED res
 
 cases (bench.py WORKLOADS, seed 1000 = the segment rank 0 times; cfg2audio / cfg4audio = bench.py's cfg2 / cfg4 themselves: the decoded audio
 files BASELINE names, cfg2 with the drivers' damping 0.1):
-  cfg3     ihgp_ep_modulator_nmf, T = 200 000, 32 ch / 6 comps, p = 7, 3 sweeps          (north_star's target sentence)
+  cfg3     ihgp_ep_modulator_nmf, T = 200 000, 32 ch / 6 comps, p = 7, 3 sweeps          (north_star's target sentence; ihgp_adf8_kernel)
   cfg2     gf_ep_modulator_nmf, T = 84 010 (the length of audio/speech_74.wav; prior sample), 16 ch / 3 comps, p = 9, 3 sweeps
   cfg4     gf_giekf_modulator_nmf, T = 88 200 (the length of audio/stim312_wind.wav; prior sample), 24 ch / 3 comps, g_iter = 3, l_iter = 1
   cfg5seg  gf_ep_modulator_nmf_constraints model (S = 146), one segment cut to T = 20 000, p = 7, 3 sweeps

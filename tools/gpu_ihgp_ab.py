@@ -1,4 +1,5 @@
-"""Developer probe: the IHGP ADF sweep in the sparse-point form (ihgp_adf_kernel) against the generic kernel
+"""Developer probe: the IHGP ADF sweep in the sparse-point form (ihgp_adf_kernel; with role-specialised waves ihgp_adf8_kernel, and
+ihgp_adf8b_kernel for the shape with seven components) against the generic kernel
 (NAGP_NO_SPARSE=1) on the same inputs.  python tools/gpu_ihgp_ab.py [T] [D N p ...]"""
 import os, sys
 os.environ.setdefault('NAGP_DEVELOPER', '1')      # developer tool: libnagp.so reads its switches only with this set
