@@ -2,158 +2,8 @@
 // nagp_api_entry.hpp; the plan struct, the error helpers and the developer switches live in nagp_api.hip itself).
 // Plan creation: shape checks, kernel / LDS / slot policy, model packing, cubature tables, device buffers; destroy, upload.
 
-// ---------------------------------------------------------------------------------------------
-// Member and term lists of the role layout's cubature sums (nagp_momsp.hpp, msr_sums / msr_reduce), built once per plan from the
-// static cubature codes.  Bins: S_k (k = 0, 1, 2), Ck(j,c), C2(j,c; j',c'), each cut into chunks of <= 64 members on an aligned
-// group of 1, 2 or 4 lanes.  Level-2 outputs: U_j, E_j, P_jj, g1_j, G2_j, P_jj', S_k, each <= 4 MSR_KT terms bin * table * table.
-// The bins of a dimension (and its outputs), of a dimension pair and of a total go to ONE worker wave (their level 2 reads its own
-// bins), first fit by decreasing size.  Returns false when the rule does not fit the six worker waves.
-static bool msr_build_desc(int CD, int nd, int c0, int npt, const std::vector<unsigned char>& code, std::vector<int>& dsc) {
-  const MspLay l = msp_layout(CD, 1, 1);      // (the offsets used here do not depend on D)
-  const int zero = l.zero, one = l.one, mone = l.part + MSR_MONE;
-  struct Bin { int k; std::vector<int> pts; std::vector<int> slot; };      // slot: level-1 result of each chunk
-  struct Term { int bin, fa, fb; };
-  struct Out { std::vector<Term> t; int slot = -1; };
-  struct Grp { std::vector<int> bins, outs; int n1 = 0, n2 = 0; };
-  std::vector<Bin> bins; std::vector<Out> outs; std::vector<Grp> grps;
-  auto pw2 = [](int n) { return n <= 1 ? 1 : (n <= 2 ? 2 : 4); };
-  auto chunks = [](const Bin& b) { return std::max(1, ((int)b.pts.size() + 63) / 64); };
-  auto chunk_lanes = [&](const Bin& b, int q) { const int n = std::min(64, (int)b.pts.size() - 64 * q); return pw2((n + MSR_NMEM - 1) / MSR_NMEM); };
-  auto nterms = [&](const Out& o) { int n = 0; for (const Term& t : o.t) n += chunks(bins[t.bin]); return n; };
-  auto add_bin = [&](int k, std::vector<int> pts) { bins.push_back({k, std::move(pts), {}}); return (int)bins.size() - 1; };
-  auto add_out = [&](Grp& g) { outs.push_back(Out{}); g.outs.push_back((int)outs.size() - 1); return (int)outs.size() - 1; };
-  auto cd = [&](int p, int j) { return (int)code[(size_t)p * CD + j]; };
-  const int lk = l.lk, e = l.e;
-  std::vector<int> oU(CD, -1), oE(CD, -1), oPd(CD, -1), oG1(CD, -1), oG2(CD, -1), oS(3, -1);
-  std::vector<std::vector<int>> oP(CD, std::vector<int>(CD, -1));
-  for (int j = 0; j < CD; ++j) {      // dimension j: C0, C1, C2 (j, c) and the outputs U, E, P_jj, g1, G2
-    Grp g;
-    oU[j] = add_out(g); oE[j] = add_out(g); oPd[j] = add_out(g); oG1[j] = add_out(g); oG2[j] = add_out(g);
-    for (int c = 0; c < nd; ++c) {
-      if (c == c0) continue;
-      std::vector<int> pts;
-      for (int p = 0; p < npt; ++p) if (cd(p, j) == c) pts.push_back(p);
-      if (pts.empty()) continue;
-      const int t = j * nd + c;
-      const int b0 = add_bin(0, pts), b1 = add_bin(1, pts), b2 = add_bin(2, pts);
-      g.bins.insert(g.bins.end(), {b0, b1, b2});
-      outs[oU[j]].t.push_back({b1, e + t, one});
-      outs[oE[j]].t.push_back({b2, e + t, one});
-      outs[oPd[j]].t.push_back({b2, e + t, e + t});
-      outs[oG1[j]].t.push_back({b0, l.xg + t, one});
-      outs[oG2[j]].t.push_back({b0, l.xg2 + t, one});
-      outs[oG2[j]].t.push_back({b0, l.xg2 + j * nd + c0, mone});
-    }
-    grps.push_back(g);
-  }
-  for (int j = 0; j < CD; ++j)        // dimension pair j < j2: C2 (j, c; j2, c2) and P_jj2
-    for (int j2 = j + 1; j2 < CD; ++j2) {
-      Grp g;
-      oP[j][j2] = add_out(g);
-      for (int c = 0; c < nd; ++c)
-        for (int cc = 0; cc < nd; ++cc) {
-          if (c == c0 || cc == c0) continue;
-          std::vector<int> pts;
-          for (int p = 0; p < npt; ++p) if (cd(p, j) == c && cd(p, j2) == cc) pts.push_back(p);
-          if (pts.empty()) continue;
-          const int b = add_bin(2, pts);
-          g.bins.push_back(b);
-          outs[oP[j][j2]].t.push_back({b, e + j * nd + c, e + j2 * nd + cc});
-        }
-      grps.push_back(g);
-    }
-  for (int k = 0; k < 3; ++k) {       // totals
-    Grp g;
-    std::vector<int> pts(npt);
-    for (int p = 0; p < npt; ++p) pts[p] = p;
-    const int b = add_bin(k, pts);
-    g.bins.push_back(b);
-    oS[k] = add_out(g);
-    outs[oS[k]].t.push_back({b, one, one});
-    grps.push_back(g);
-  }
-  for (Grp& g : grps) {
-    for (int b : g.bins) for (int q = 0; q < chunks(bins[b]); ++q) g.n1 += chunk_lanes(bins[b], q);
-    for (int o : g.outs) {
-      const int n = nterms(outs[o]);
-      if (n > 4 * MSR_KT) return false;
-      g.n2 += pw2((n + MSR_KT - 1) / MSR_KT);
-    }
-  }
-  // first fit by decreasing level-1 lanes
-  std::vector<int> order(grps.size());
-  for (size_t i = 0; i < order.size(); ++i) order[i] = (int)i;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return grps[a].n1 > grps[b].n1; });
-  std::vector<std::vector<int>> wg(MSR_NWK);
-  int used1[MSR_NWK] = {0}, used2[MSR_NWK] = {0};
-  for (int gi : order) {
-    int w = 0;
-    while (w < MSR_NWK && (used1[w] + grps[gi].n1 > 64 || used2[w] + grps[gi].n2 > 64)) ++w;
-    if (w == MSR_NWK) return false;
-    wg[w].push_back(gi); used1[w] += grps[gi].n1; used2[w] += grps[gi].n2;
-  }
-  dsc.assign((size_t)msr_desc_ints(), zero);
-  for (int L = 0; L < MSR_NL; ++L) { dsc[(size_t)L * MSR_DW + MSR_NMEM] = 0; dsc[(size_t)L * MSR_DW + MSR_NMEM + 1 + 3 * MSR_KT] = 0; }
-  const int grp_flags[5] = {0, 0, 1, 0, 3};      // by group size
-  for (int w = 0; w < MSR_NWK; ++w) {
-    // level 1: chunks by decreasing group size (aligned groups)
-    struct Ch { int b, q, G; };
-    std::vector<Ch> ch;
-    for (int gi : wg[w]) for (int b : grps[gi].bins) for (int q = 0; q < chunks(bins[b]); ++q) ch.push_back({b, q, chunk_lanes(bins[b], q)});
-    std::stable_sort(ch.begin(), ch.end(), [](const Ch& a, const Ch& b) { return a.G > b.G; });
-    int lane = 0;
-    for (const Ch& c : ch) {
-      Bin& b = bins[c.b];
-      const int base = b.k == 0 ? l.c0 : (b.k == 1 ? l.c1 : l.c2);
-      const int n = std::min(64, (int)b.pts.size() - 64 * c.q);
-      for (int i = 0; i < n; ++i) {      // member i -> lane i % G, slot i / G
-        const int L = w * 64 + lane + i % c.G;
-        dsc[(size_t)L * MSR_DW + i / c.G] = base + b.pts[64 * c.q + i];
-      }
-      for (int i = 0; i < c.G; ++i) dsc[(size_t)(w * 64 + lane + i) * MSR_DW + MSR_NMEM] = grp_flags[c.G];
-      if ((int)b.slot.size() <= c.q) b.slot.resize(c.q + 1, -1);
-      b.slot[c.q] = l.part + w * 64 + lane;
-      lane += c.G;
-    }
-    // level 2: outputs by decreasing group size
-    struct Oc { int o, G; };
-    std::vector<Oc> oc;
-    for (int gi : wg[w]) for (int o : grps[gi].outs) oc.push_back({o, pw2((nterms(outs[o]) + MSR_KT - 1) / MSR_KT)});
-    std::stable_sort(oc.begin(), oc.end(), [](const Oc& a, const Oc& b) { return a.G > b.G; });
-    lane = 0;
-    for (const Oc& c : oc) {
-      std::vector<Term> ts;      // chunks expanded
-      for (const Term& t : outs[c.o].t)
-        for (int q = 0; q < chunks(bins[t.bin]); ++q) ts.push_back({bins[t.bin].slot[q], t.fa, t.fb});
-      for (size_t i = 0; i < ts.size(); ++i) {
-        int* d = &dsc[(size_t)(w * 64 + lane + (int)i / MSR_KT) * MSR_DW + MSR_NMEM + 1 + 3 * ((int)i % MSR_KT)];
-        d[0] = ts[i].bin; d[1] = ts[i].fa; d[2] = ts[i].fb;
-      }
-      for (int i = 0; i < c.G; ++i) dsc[(size_t)(w * 64 + lane + i) * MSR_DW + MSR_NMEM + 1 + 3 * MSR_KT] = grp_flags[c.G];
-      outs[c.o].slot = l.part + MSR_NL + w * 64 + lane;
-      lane += c.G;
-    }
-  }
-  // msr_reduce: acc[o] = p + c d + a b + s f g
-  auto L2 = [&](int o) { return (o >= 0 && !outs[o].t.empty()) ? outs[o].slot : zero; };
-  auto l0 = [&](int j) { return lk + j * nd + c0; };
-  const int nq = CD * (CD + 1) / 2;
-  for (int o = 0; o < msp_nacc(CD); ++o) {
-    int* r = &dsc[(size_t)MSR_NL * MSR_DW + (size_t)o * MSR_RW];      // p, a, b, c, d, s, f, g (zero word by default)
-    if (o < CD) { r[0] = L2(oU[o]); r[5] = L2(oS[1]); r[6] = l0(o); r[7] = one; }
-    else if (o < CD + nq) {
-      int q = o - CD, j = 0;
-      while (q >= CD - j) { q -= CD - j; ++j; }
-      const int j2 = j + q;
-      r[0] = (j == j2) ? L2(oPd[j]) : L2(oP[j][j2]);
-      r[1] = l0(j2); r[2] = L2(oE[j]); r[3] = l0(j); r[4] = L2(oE[j2]);
-      r[5] = L2(oS[2]); r[6] = l0(j); r[7] = l0(j2);
-    } else if (o < 2 * CD + nq) r[0] = L2(oG1[o - CD - nq]);
-    else if (o < 3 * CD + nq) { const int j = o - 2 * CD - nq; r[0] = L2(oG2[j]); r[5] = L2(oS[0]); r[6] = l.xg2 + j * nd + c0; r[7] = one; }
-    else r[0] = L2(oS[0]);
-  }
-  return true;
-}
+// Member and term lists of the role layout's cubature sums: msr_build_desc, nagp_msr_desc.hpp (host only; a stand-alone program reads it too)
+#include "nagp_msr_desc.hpp"
 
 // ---------------------------------------------------------------------------------------------
 static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, const nagp_ihgp_tables* tables,

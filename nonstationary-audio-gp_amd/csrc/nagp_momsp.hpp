@@ -21,50 +21,22 @@
 #pragma once
 #include "nagp_dev.hpp"
 #include "nagp_qform.hpp"
+#include "nagp_msr_desc.hpp"
 
 namespace nagp {
 
 constexpr int MSP_NT = 256;   // threads per workgroup the stages are written for
-constexpr int MSP_NW = 4;
 constexpr int MSP_NPS = 2;    // sigma points per lane in stage 1b
-constexpr int MSP_NST = 20;   // MFMA steps per wave in stage 2 (4 points each)
 constexpr int MSP_DT = 16;    // sub-bands per lane of a 4-lane group in stage A (D <= 64)
 constexpr int MSP_MAXCD = 7;  // 2*CD + 2 <= 16 rows of the MFMA block
-constexpr int MSP_TS = 64;    // stride of the (dimension, coordinate) tables: CD*nd <= 63, entry 63 of e / t1 / ve stays zero
-constexpr int MSP_CS = 4 * MSP_NW * MSP_NST + 1;   // stride of c0 / c1 / c2: every point an MFMA step can address, zero beyond n_pts
 
 typedef const double __attribute__((address_space(3))) * msp_rp;   // LDS read pointer (32-bit, register resident)
 typedef double __attribute__((address_space(3))) * msp_wp;
 
 // terms per lane of the 4-lane groups that form Q and v (stage A): the next of 4, 8, 16 that covers D sub-bands -- msp_qterms, nagp_qform.hpp
 
-// LDS workspace (offsets in doubles).  Tables lk | xg | xg2 | e | t1 | ve, MSP_TS entries each.
-struct MspLay { int lk, xg, xg2, e, t1, ve, one, zero, Q, Q2, v, q0, s0, c0, c1, c2, part, acc, marg, wwt, total; };
-// LAY 0: the 256-thread layout (four waves share every stage); LAY 1: the role layout of 512 threads (nagp_ihgp.hpp:
-// two serial waves, six worker waves; `part` holds the results of the bin sums, msr_sums)
-constexpr int MSR_NWK = 6;     // worker waves of the role layout
-constexpr int MSR_NMEM = 16;   // members of a bin sum per lane (bins of up to 64 members span 2 or 4 lanes)
-constexpr int MSR_NMARG = 32;  // marginal sums (non-centre (dimension, coordinate) pairs) of nagp_momsq.hpp
-constexpr int MSR_CS = 64 * MSR_NWK + 1;      // one weight per worker lane
-__host__ __device__ inline MspLay msp_layout(int CD, int D, int LAY = 0) {
-  MspLay l;
-  const int cs = LAY ? MSR_CS : MSP_CS, nparts = LAY ? MSR_NWK : MSP_NW;
-  l.lk = 0; l.xg = MSP_TS; l.xg2 = 2 * MSP_TS; l.e = 3 * MSP_TS; l.t1 = 4 * MSP_TS; l.ve = 5 * MSP_TS;
-  l.zero = l.e + MSP_TS - 1;                     // e[63] (t1[63], ve[63] are zero as well)
-  l.one = 6 * MSP_TS;
-  l.Q = l.one + 1; l.Q2 = l.Q + CD * CD; l.v = l.Q2 + CD * CD; l.q0 = l.v + CD; l.s0 = l.q0 + 1;
-  int o = (l.s0 + 2) & ~1;
-  l.c0 = o; l.c1 = o + cs; l.c2 = o + 2 * cs;
-  o = (o + 3 * cs + 1) & ~1;
-  l.part = o; o += nparts * 256;
-  l.acc = o; o += 128;
-  l.marg = o; o += LAY ? MSR_NMARG : 0;
-  l.wwt = o; o += msp_qterms(D) * 192;            // static W products of stage A, [q][lane of waves 1..3], zero for sub-bands >= D
-  l.total = o;
-  return l;
-}
+// LDS workspace: MspLay, msp_layout and the constants of the role layout (LAY = 1), nagp_msr_desc.hpp
 __host__ __device__ inline size_t msp_lds_doubles(int CD, int D, int LAY = 0) { return (size_t)msp_layout(CD, D, LAY).total; }
-__host__ __device__ inline int msp_nacc(int CD) { return CD + CD * (CD + 1) / 2 + 2 * CD + 1; }   // u, R (upper), g1, g2, Z
 
 // 1/x by the hardware estimate and two Newton steps (~1 ulp)
 // (x = 0, inf or of underflow size: the refinement is NaN -- callers on such values branch to true divisions)
@@ -669,15 +641,10 @@ __device__ __forceinline__ void msp_outputs_b(msp_rp acc, int jmod, const double
 // Level 1: each worker lane adds <= MSR_NMEM weights of one bin (bins of up to 64 members span an aligned group of 2 or 4
 // lanes, combined by DPP); level 2: each worker lane forms <= MSR_KT products bin * table * table of bins of ITS OWN wave
 // (behind msp_wave_fence, no barrier) -- U, E, P, g1, G2, S; msr_reduce on the serial waves combines them as above.  The
-// member and term lists are static: the host builds them once per plan (msr_build_desc, nagp_api_plan.hpp) into MomSp::bdesc.
+// member and term lists are static: the host builds them once per plan (msr_build_desc, nagp_msr_desc.hpp) into MomSp::bdesc.
 constexpr int MSR_NT = 512;
 constexpr int MSR_W0 = 2;      // first worker wave
-constexpr int MSR_KT = 4;      // level-2 terms per lane (outputs with more span an aligned group of 2 or 4 lanes)
-constexpr int MSR_DW = MSR_NMEM + 1 + 3 * MSR_KT + 1;   // descriptor ints per worker lane: members | group flags | terms | group flags
-constexpr int MSR_RW = 8;      // descriptor ints per lane of msr_reduce: p, a, b, c, d, s, f, g  ->  p + c d + a b + s f g
-constexpr int MSR_NL = 64 * MSR_NWK;                    // worker lanes; level-1 results at part + L, level-2 results at part + MSR_NL + L
-constexpr int MSR_MONE = 2 * MSR_NL;                    // part + MSR_MONE: the constant -1
-__host__ __device__ inline int msr_desc_ints() { return MSR_NL * MSR_DW + 64 * MSR_RW; }
+// (MSR_KT, MSR_DW, MSR_RW, MSR_NL, MSR_MONE, msr_desc_ints and the second copy of the lists: nagp_msr_desc.hpp)
 
 template <int CD>
 struct MsrS {
@@ -706,7 +673,8 @@ __device__ __forceinline__ void msr_init(int CD, int D, double* ws) {
 }
 
 template <int CD>
-__device__ __forceinline__ void msr_setup_S(MsrS<CD>& x, const MomCfg& c, const MomSp& sp, const double* fmu, const double* HPH, double* ws) {
+__device__ __forceinline__ void msr_setup_S(MsrS<CD>& x, const MomCfg& c, const MomSp& sp, const double* fmu, const double* HPH, double* ws,
+                                             int dbase = 0 /* copy of the lists: 0 or msr_desc_w_base() */) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nd = c.nd, D = c.D, TN = CD * nd;
   const MspLay l = msp_layout(CD, D, 1);
@@ -727,7 +695,7 @@ __device__ __forceinline__ void msr_setup_S(MsrS<CD>& x, const MomCfg& c, const 
     x.a_out = (msp_wp)(ws + t);
   }
   {
-    const int* d = sp.bdesc + (size_t)MSR_NL * MSR_DW + (size_t)lane * MSR_RW;
+    const int* d = sp.bdesc + dbase + (size_t)MSR_NL * MSR_DW + (size_t)lane * MSR_RW;
 #pragma unroll
     for (int i = 0; i < MSR_RW; ++i) x.r_p[i] = (msp_rp)(ws + d[i]);
     const int ab = (wave == 1) ? 64 : 0;
@@ -736,10 +704,32 @@ __device__ __forceinline__ void msr_setup_S(MsrS<CD>& x, const MomCfg& c, const 
   }
 }
 
+// the cubature sums' part of a worker lane's state: its members and terms (host lists, msr_build_desc; offsets in doubles from ws, unused
+// entries address the zero word).  dbase: the copy of the lists, 0 or msr_desc_w_base() (nagp_msr_desc.hpp)
+template <class X>
+__device__ __forceinline__ void msr_setup_sums(X& x, const int* bdesc, int dbase, const MspLay& l, double* ws) {
+  const int lane = threadIdx.x & 63, wr = ((int)threadIdx.x >> 6) - MSR_W0;
+  const bool worker = wr >= 0 && wr < MSR_NWK;
+  const int L = worker ? wr * 64 + lane : 0;
+  const int* d = bdesc + dbase + (size_t)L * MSR_DW;
+#pragma unroll
+  for (int k = 0; k < MSR_NMEM; ++k) x.s_mem[k] = (msp_rp)(ws + d[k]);
+  x.s_grp = d[MSR_NMEM];
+  x.s_out = (msp_wp)(ws + l.part + L);
+#pragma unroll
+  for (int t = 0; t < MSR_KT; ++t) {
+    x.t_bin[t] = (msp_rp)(ws + d[MSR_NMEM + 1 + 3 * t]);
+    x.t_fa[t] = (msp_rp)(ws + d[MSR_NMEM + 2 + 3 * t]);
+    x.t_fb[t] = (msp_rp)(ws + d[MSR_NMEM + 3 + 3 * t]);
+  }
+  x.t_grp = d[MSR_NMEM + 1 + 3 * MSR_KT];
+  x.t_out = (msp_wp)(ws + l.part + MSR_NL + L);
+}
+
 // qv = false: Q / 2Q / v are formed on serial wave 0 (msr_setup_Q, msr_qv_serial), which then owns the wwt region; no worker lane takes a part
 template <int CD>
 __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const MomSp& sp, const double* Wl /* LDS D x CD */,
-                                             const double* fmu, const double* HPH, double* ws, bool qv = true) {
+                                             const double* fmu, const double* HPH, double* ws, bool qv = true, int dbase = 0) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave - MSR_W0;     // wr = 0 .. 5
   const int nd = c.nd, D = c.D, npt = c.n_pts;
   const MspLay l = msp_layout(CD, D, 1);
@@ -817,23 +807,8 @@ __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const 
     for (int j = 0; j < CD; ++j) x.d_lk[j] = ok ? (msp_rp)(ws + l.lk + j * nd + c.code[(size_t)p * CD + j]) : zero;
     x.d_qv = (msp_rp)(ws + l.Q) + opaque_zero();
   }
-  // ---- cubature sums: this lane's members and terms (host lists; offsets in doubles from ws, unused entries address the zero word)
-  {
-    const int L = (wr >= 0 && wr < MSR_NWK) ? wr * 64 + lane : 0;
-    const int* d = sp.bdesc + (size_t)L * MSR_DW;
-#pragma unroll
-    for (int k = 0; k < MSR_NMEM; ++k) x.s_mem[k] = (msp_rp)(ws + d[k]);
-    x.s_grp = d[MSR_NMEM];
-    x.s_out = (msp_wp)(ws + l.part + L);
-#pragma unroll
-    for (int t = 0; t < MSR_KT; ++t) {
-      x.t_bin[t] = (msp_rp)(ws + d[MSR_NMEM + 1 + 3 * t]);
-      x.t_fa[t] = (msp_rp)(ws + d[MSR_NMEM + 2 + 3 * t]);
-      x.t_fb[t] = (msp_rp)(ws + d[MSR_NMEM + 3 + 3 * t]);
-    }
-    x.t_grp = d[MSR_NMEM + 1 + 3 * MSR_KT];
-    x.t_out = (msp_wp)(ws + l.part + MSR_NL + L);
-  }
+  // ---- cubature sums: this lane's members and terms
+  msr_setup_sums(x, sp.bdesc, dbase, l, ws);
 }
 
 // ---- Q / 2Q / v on serial wave 0 (the three-barrier schedule of ihgp_adf8_kernel): the nq + CD outputs of msr_setup_W's 4-lane groups on
