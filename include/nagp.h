@@ -700,6 +700,69 @@ typedef struct nagp_recon_out {     /* caller-allocated, any pointer may be NULL
 int nagp_reconstruct_sources(int32_t D, int32_t N, int64_t T, const double* Eft, const double* Varft, const double* Wnmf,
                              const nagp_recon_opts* opts, nagp_recon_out* out);
 
+/* Joint posterior draws of a full-covariance EP run -- gf_ep_modulator.m, gf_ep_modulator_nmf.m, gf_ep_modulator_nmf_constraints.m in
+ * predict mode -- whole state paths, correlated in time.  The drivers draw sub_samp / mod_samp independently per time step from Eft / Varft
+ * (demo_nonstationary_filterbank.m:226-258, noise_reduction_speech.m:107-145; nagp_reconstruct* restates that): error bars on anything that
+ * couples time steps (the energy of a separated source over a note, a filled gap of missing_data_music.m) need joint draws, and a gap can be
+ * filled with texture only by one -- the argument made for the filterbank above.
+ * The law.  The last forward pass of a run (gf_ep_modulator_nmf.m:126-184) is a linear recursion in the sites (ttau, tnu) the run returned,
+ * and the RTS smoother on top of it (:207-234) defines one Gaussian over the state path.  Forward, from m = 0, P = Pinf:
+ *     k > 0 (and k = 0 with predict_at_k1):  m = A m,  P = A P A' + Q;
+ *     where y_k is not NaN, with fmu = H m, W = P H', HPH = diag(H P H') and the sites of step k (:159-176; no mom call anywhere: the
+ *     returned sites hold the refresh of step T-1):
+ *       sites with ttau == 0:  z = ttau HPH + 1,  K = W ttau / z,  m = m - W (ttau fmu - tnu) / z,  P = P - K W'  (K = 0: P stays);
+ *       the other sites:       K = W / (HPH + 1 / ttau)  (diagonal innovation),  m = m + K (tnu / ttau - fmu),  P = P - (K H) P;
+ *     MF_k = m, PF_k = P.
+ * Per step k < T-1, independent of the other steps:
+ *     PSkp = A PF_k A' + Q  (its lower triangle, as chol(., 'lower') reads it),  L = chol(PSkp), after a failure once more with
+ *     sqrt(1e-4) 0.5 I added (:216-223 with rand -> 0.5), counted in counters[0];   G_k = PF_k A' / L' / L  (the two triangular solves);
+ *     C_k = (I - G_k A) PF_k (I - G_k A)' + G_k Q G_k'  (lower triangle),   Lc_k = chol(C_k): a pivot <= 0 zeroes its column and is counted
+ *     in counters[1] -- never a NaN, never silent;   Lc_{T-1} = chol(PF_{T-1}) likewise.
+ * Draw i:
+ *     x_{T-1} = MF_{T-1} + Lc_{T-1} z_{T-1},      x_k = MF_k + G_k (x_{k+1} - A MF_k) + Lc_k z_k    (k = T-2 .. 0),
+ *     z_k[j] = z[(i T + k) S + j] when the caller passes its normals, else normals(T, j, n_draws, seed)[k, i]: the counter-based generator of
+ *     nagp_reconstruct with the counter word "site" set to the state index j, as nagp_fastfb_sample uses it.  Draw i does not depend on
+ *     n_draws or on how the draws are batched on the device.
+ * The marginals of this chain are exactly the MS_k, PS_k (hence Eft, Varft) of the run, its lag-one covariances G_k PS_{k+1}.
+ * Outputs (each may be NULL, not all four):  Xdraw, n_draws blocks of S x T column-major;  Fdraw, n_draws blocks of M x T,
+ *     Fdraw_i[n, k] = h_val[n] x_k[block_offsets[n]];  MS (S x T), the chain with every z = 0: the RTS means;
+ *     Sdraw (n_draws x T, needs sig):  Sdraw_i[k] = sum_d a_d z_d with z_d = Fdraw_i[d, k], g_n = Fdraw_i[D + n, k] and
+ *     a_d = W_d.link(g) (NAGP_AMP_LINEAR) or sqrt(W_d.link(g)) (NAGP_AMP_SQRT), link as nagp_link: the amplitudes of nagp_reconstruct_sources
+ *     on the draw's own values (gf_ep_modulator: D = N, Wnmf = I).  sig uses the model's D and N (D + N = M).
+ * counters (2, may be NULL): jitter retries of PSkp, clamped pivots of C_k and PF_{T-1}.  Both are zero on every model the suite runs.
+ * nagp_ep_sample_timings: device time of the last call on this thread in ms (HIP events): the filter, the factorisation, the draws (the mean
+ * chain and every device batch).
+ * Limits, all decided on the host before any device call:
+ * NAGP_EUNSUPPORTED: a block of more than 8 states; S > 80 -- the factorisation of a step keeps three S x S operands (3 * 8 S^2 bytes) in
+ *   the 160 KiB LDS of one workgroup, and the filter P, M staged rows and M gain columns (8 (S^2 + 2 S M) bytes and change).
+ * NAGP_ENOMEM: the per-step storage does not fit the device-memory budget of a call, 48 GiB: a call takes
+ *     8 (T (2 S^2 + 2 S + 2 M + 1) + 3 S^2 + 2 sum_n b_n^2 + M + D N + 8) + 4 (2 M + 2 + S) + 4096 bytes   (PF_k / G_k, Lc_k, MF, MS, the sites, y)
+ *   and every draw 8 T ([z: S] + [Xdraw: S] + [Fdraw or Sdraw: M] + [Sdraw: 1]) bytes; the draws run in device batches of as many as fit
+ *   (whole blocks of 16 when more than 16 do).  There is no checkpoint scheme: a T beyond the budget is refused.
+ * NAGP_EINVAL: a NULL model, ttau, tnu or y, or a NULL array of the model; T or n_draws < 1; S or M < 1, M > S, block_offsets not strictly
+ *   ascending from 0 to S; a negative or non-finite ttau; a non-finite tnu; Sdraw without sig; sig with a NULL or non-finite Wnmf, an unknown
+ *   amplitude or link kind, or D + N != M; no output at all.
+ * NAGP_ENOTPD (after the run): PSkp not positive definite even with the jitter, where MATLAB's chol throws.
+ * Out of scope: the EKF family (nagp_giekf_run: its filter is not a function of sites; it could take (MF, PF) later); the
+ * infinite-horizon family (no per-step covariances: the law of a draw is not defined there); the mixture drivers, whose rule
+ * (NAGP_FLAG_MIXTURE_RULE) has not been checked against the fixed-site step above and which the Python and MATLAB wrappers therefore do
+ * not offer; per-source signal draws (Fdraw is enough to form them). */
+typedef struct nagp_epsample_sig {
+  const double* Wnmf;   /* D x N column-major */
+  int32_t amp_kind;     /* nagp_amp */
+  int32_t link_kind;    /* nagp_link */
+  double link_shift;    /* softplus shift */
+} nagp_epsample_sig;
+int nagp_ep_sample(const nagp_model* model, const double* ttau, const double* tnu /* M x T column-major */,
+                   const double* y /* T: only which entries are NaN is read */, int64_t T,
+                   int32_t predict_at_k1, int32_t n_draws, uint64_t seed,
+                   const double* z /* optional: caller's normals, n_draws x T x S, draw-major then column-major S x T; NULL = generator */,
+                   const nagp_epsample_sig* sig /* optional: Wnmf, amp kind, link kind, shift for Sdraw; NULL = no Sdraw */,
+                   double* Xdraw /* n_draws x (S x T) */, double* Fdraw /* n_draws x (M x T) */,
+                   double* Sdraw /* n_draws x T */, double* MS /* S x T */,
+                   int64_t* counters /* 2: PSkp jitter retries, clamped pivots of C_k */, int32_t device);
+int nagp_ep_sample_timings(double* ms /* 3: filter, factor, draw */);
+
 /* Batched / device-resident form: n_problems independent problems of identical shape
  * (S, M, block structure, T) -- audio segments or hyper-parameter replicas -- run concurrently. */
 int nagp_plan_create(nagp_plan** plan, int32_t n_problems, const nagp_model* models,

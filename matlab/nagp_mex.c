@@ -21,6 +21,11 @@
  *   [MS, sum_v2] = nagp_mex('fastfb', A, AKHA, HA, K, G ([] = filter only), y [,device])                       nagp_fastfb_run
  *   [Ydraw, Xdraw, MS] = nagp_mex('fastfb_sample', A, AKHA, HA, K, G, H, R, Lp, Lq, y, n_draws, seed [,device])   nagp_fastfb_sample
  *                                    Ydraw T x n_draws, Xdraw S x T x n_draws (computed only when asked for), MS S x T
+ *   [Fdraw, Xdraw, Sdraw, MS, counters] = nagp_mex('ep_sample', model, ttau, tnu, y, predict_at_k1, n_draws, seed, z, sig [,device])   nagp_ep_sample
+ *                                    joint posterior draws of a full-covariance EP run from its sites: ttau, tnu M x T; z [] (the generator) or
+ *                                    S x T x n_draws normals of the caller; sig [] or a struct Wnmf (D x N), amp_kind, link_kind, link_shift;
+ *                                    Fdraw M x T x n_draws, Xdraw S x T x n_draws, Sdraw T x n_draws ([] without sig), MS S x T, counters 2 x 1
+ *                                    (Xdraw, Sdraw, MS computed only when asked for)
  *   [lik, MS, Pcov] = nagp_mex('slowfb', A, Q, H, P0, block, y, vary, filter_only, cov, sub_idx [,device])       nagp_slowfb_run
  *                                    y, vary T x n_series; cov 0: none, 1: Pcov = marginal variances S x T x n_series, 2: Pcov =
  *                                    P(sub_idx, sub_idx, k), n_sub x n_sub x T x n_series (sub_idx int32, 0-based, ascending; [] unless cov = 2);
@@ -257,6 +262,38 @@ static void cmd_fastfb_sample(int nlhs, mxArray* plhs[], int nrhs, const mxArray
   if (nlhs > 2) plhs[2] = mxCreateDoubleMatrix(S, T, mxREAL);
   fail_if(nagp_fastfb_sample((int32_t)S, A, AK, HA, K, G, H, mxGetScalar(prhs[7]), Lp, Lq, y, (int64_t)T, nd, (uint64_t)mxGetScalar(prhs[12]),
                              mxGetPr(plhs[0]), nlhs > 1 ? mxGetPr(plhs[1]) : NULL, nlhs > 2 ? mxGetPr(plhs[2]) : NULL, dev));
+}
+
+static void cmd_ep_sample(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
+  /* ('ep_sample', model, ttau, tnu, y, predict_at_k1, n_draws, seed, z, sig [,device]) -> [Fdraw, Xdraw, Sdraw, MS, counters]: joint posterior
+     draws of a full-covariance EP run by forward filtering with its sites and backward sampling; states, signal and means only when asked for */
+  nagp_model m; nagp_epsample_sig sg; const nagp_epsample_sig* psg = NULL;
+  size_t n, T; const double *tt, *tn, *y, *z; int32_t dev, nd; int64_t cnt[2] = {0, 0}; mwSize d3[3]; int want_s;
+  if (nrhs < 10 || nrhs > 11 || nlhs > 5) mexErrMsgIdAndTxt("nagp:arg", "usage: [Fdraw,Xdraw,Sdraw,MS,counters] = nagp_mex('ep_sample',model,ttau,tnu,y,predict_at_k1,n_draws,seed,z,sig[,device])");
+  read_model(prhs[1], &m);
+  y = dvec(prhs[4], "y", &T);
+  nd = (int32_t)mxGetScalar(prhs[6]);
+  if (!y || nd < 1) mexErrMsgIdAndTxt("nagp:arg", "y must not be empty and n_draws must be at least 1");
+  tt = dvec(prhs[2], "ttau", &n); if (n != (size_t)m.M * T) mexErrMsgIdAndTxt("nagp:arg", "ttau must be M x T");
+  tn = dvec(prhs[3], "tnu", &n); if (n != (size_t)m.M * T) mexErrMsgIdAndTxt("nagp:arg", "tnu must be M x T");
+  z = dvec(prhs[8], "z", &n); if (z && n != (size_t)m.S * T * (size_t)nd) mexErrMsgIdAndTxt("nagp:arg", "z must be S x T x n_draws or []");
+  if (!mxIsEmpty(prhs[9])) {
+    sg.Wnmf = doubles(prhs[9], "Wnmf", 1, &n);
+    if (n != (size_t)m.D * m.N) mexErrMsgIdAndTxt("nagp:arg", "sig.Wnmf must be D x N");
+    sg.amp_kind = (int32_t)scalar_or(prhs[9], "amp_kind", 0); sg.link_kind = (int32_t)scalar_or(prhs[9], "link_kind", 0);
+    sg.link_shift = scalar_or(prhs[9], "link_shift", 0);
+    psg = &sg;
+  }
+  dev = nrhs > 10 ? (int32_t)mxGetScalar(prhs[10]) : 0;
+  want_s = nlhs > 2 && psg;
+  d3[0] = (mwSize)m.M; d3[1] = T; d3[2] = (mwSize)nd; plhs[0] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL);
+  if (nlhs > 1) { d3[0] = (mwSize)m.S; plhs[1] = mxCreateNumericArray(3, d3, mxDOUBLE_CLASS, mxREAL); }
+  if (nlhs > 2) plhs[2] = want_s ? mxCreateDoubleMatrix(T, (mwSize)nd, mxREAL) : mxCreateDoubleMatrix(0, 0, mxREAL);
+  if (nlhs > 3) plhs[3] = mxCreateDoubleMatrix((mwSize)m.S, T, mxREAL);
+  if (nlhs > 4) plhs[4] = mxCreateDoubleMatrix(2, 1, mxREAL);
+  fail_if(nagp_ep_sample(&m, tt, tn, y, (int64_t)T, (int32_t)mxGetScalar(prhs[5]), nd, (uint64_t)mxGetScalar(prhs[7]), z, psg, nlhs > 1 ? mxGetPr(plhs[1]) : NULL,
+                         mxGetPr(plhs[0]), want_s ? mxGetPr(plhs[2]) : NULL, nlhs > 3 ? mxGetPr(plhs[3]) : NULL, cnt, dev));
+  if (nlhs > 4) { mxGetPr(plhs[4])[0] = (double)cnt[0]; mxGetPr(plhs[4])[1] = (double)cnt[1]; }
 }
 
 static void cmd_slowfb(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
@@ -685,6 +722,7 @@ void mexFunction(int nlhs, mxArray* plhs[], int nrhs, const mxArray* prhs[]) {
     if (!strcmp(cmd, "iekf_update1")) cmd_iekf_update1(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fastfb")) cmd_fastfb(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "fastfb_sample")) cmd_fastfb_sample(nlhs, plhs, nrhs, prhs);
+    else if (!strcmp(cmd, "ep_sample")) cmd_ep_sample(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "slowfb")) cmd_slowfb(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "nmf_fp")) cmd_nmf_fp(nlhs, plhs, nrhs, prhs);
     else if (!strcmp(cmd, "pstft_obj")) cmd_pstft_obj(nlhs, plhs, nrhs, prhs);

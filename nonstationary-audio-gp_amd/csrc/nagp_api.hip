@@ -6,6 +6,7 @@
 #include "nagp_inst.hpp"
 #include "nagp_recon.hpp"
 #include "nagp_fbsample.hpp"
+#include "nagp_epsample.hpp"
 #include "nagp_slowfb.hpp"
 #include "nagp_nmf.hpp"
 #include "nagp_pstft.hpp"
@@ -20,6 +21,7 @@
 // every templated kernel is instantiated in one of the inst_*.hip translation units
 NAGP_LIST_ALL(extern template __global__)
 NAGP_LIST_FBSAMPLE(extern template __global__)
+NAGP_LIST_EPSAMPLE(extern template __global__)
 NAGP_LIST_SLOWFB(extern template __global__)
 NAGP_LIST_NMF(extern template __global__)
 NAGP_LIST_PSTFT(extern template __global__)
@@ -56,7 +58,7 @@ static thread_local std::string g_last_error;
 // and the scripts under tools/ set it; bench.py and the MEX gateway never do).  The switches that make results meaningless (phase-skipping
 // timing probes) and the test hooks that replace devices or fail allocations say so on stderr once when they are active.
 // read_dev_switches() is the only reader of the environment: nagp_plan_create takes one snapshot into the plan (nagp_plan::dev), which
-// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run, nagp_fastfb_sample, nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj, nagp_gppad_create, nagp_gppad_cas_create, nagp_nmf_temp_create, nagp_sebf_conv, nagp_sebf_fit_create and nagp_tnmf_create one per call.
+// everything after it reads; nagp_batch_run takes one for itself and its workers' plans, nagp_fastfb_run, nagp_fastfb_sample, nagp_ep_sample, nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj, nagp_gppad_create, nagp_gppad_cas_create, nagp_nmf_temp_create, nagp_sebf_conv, nagp_sebf_fit_create and nagp_tnmf_create one per call.
 struct DevSwitches {
   // presence switches: on when the variable is set to anything
   bool no_wide = false;          // NAGP_NO_WIDE
@@ -86,10 +88,10 @@ struct DevSwitches {
   int chunks = 12;               // NAGP_CHUNKS (>= 1): smoother chunks per sweep
   int pipeline_slots = 0;        // NAGP_PIPELINE_SLOTS (>= 1; at most nc - 1 at the use)
   int mom_chunk = 0;             // NAGP_MOM_CHUNK (>= 64)
-  // NAGP_<FBS|SFB|NMF|PSTFT|SEGP|GPPAD|NMFT|SEBF>_BUDGET_MB (>= 1): the device-memory budget in MiB, instead of the <...>_BUDGET_BYTES of its file, of nagp_fastfb_sample,
-  // nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj and of the per-evaluation buffers of a nagp_gppad / nagp_gppad_cas (the GPPAD slot) / nagp_nmf_temp / nagp_sebf_fit / nagp_tnmf handle and of nagp_sebf_conv (budget_bytes, nagp_api_layout.hpp)
-  enum Budget { FBS, SFB, NMF, PSTFT, SEGP, GPPAD, NMFT, SEBF, N_BUDGETS };
-  int budget_mb[N_BUDGETS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  // NAGP_<FBS|SFB|NMF|PSTFT|SEGP|GPPAD|NMFT|SEBF|EPS>_BUDGET_MB (>= 1): the device-memory budget in MiB, instead of the <...>_BUDGET_BYTES of its file, of nagp_fastfb_sample,
+  // nagp_slowfb_run, nagp_nmf_fp, nagp_pstft_obj, nagp_segp_obj and of the per-evaluation buffers of a nagp_gppad / nagp_gppad_cas (the GPPAD slot) / nagp_nmf_temp / nagp_sebf_fit / nagp_tnmf handle and of nagp_sebf_conv, and (the EPS slot) of nagp_ep_sample (budget_bytes, nagp_api_layout.hpp)
+  enum Budget { FBS, SFB, NMF, PSTFT, SEGP, GPPAD, NMFT, SEBF, EPS, N_BUDGETS };
+  int budget_mb[N_BUDGETS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
   int kb_f = 0;                  // NAGP_KB_F (1 .. 16)
   int ih_kb = 0;                 // NAGP_IH_KB (4, 8 or 16; anything else: not set): depth of the I/O ring of ihgp_adf8_kernel / ihgp_adf8b_kernel, where it fits
   int filter_dbg = 0;            // NAGP_FILTER_DBG
@@ -129,7 +131,7 @@ static DevSwitches read_dev_switches() {
   if ((v = env("NAGP_CHUNKS"))) s.chunks = std::max(1, atoi(v));
   if ((v = env("NAGP_PIPELINE_SLOTS"))) s.pipeline_slots = std::max(1, atoi(v));
   if ((v = env("NAGP_MOM_CHUNK"))) s.mom_chunk = std::max(64, atoi(v));
-  static const char* const budget_env[DevSwitches::N_BUDGETS] = {"NAGP_FBS_BUDGET_MB", "NAGP_SFB_BUDGET_MB", "NAGP_NMF_BUDGET_MB", "NAGP_PSTFT_BUDGET_MB", "NAGP_SEGP_BUDGET_MB", "NAGP_GPPAD_BUDGET_MB", "NAGP_NMFT_BUDGET_MB", "NAGP_SEBF_BUDGET_MB"};
+  static const char* const budget_env[DevSwitches::N_BUDGETS] = {"NAGP_FBS_BUDGET_MB", "NAGP_SFB_BUDGET_MB", "NAGP_NMF_BUDGET_MB", "NAGP_PSTFT_BUDGET_MB", "NAGP_SEGP_BUDGET_MB", "NAGP_GPPAD_BUDGET_MB", "NAGP_NMFT_BUDGET_MB", "NAGP_SEBF_BUDGET_MB", "NAGP_EPS_BUDGET_MB"};
   for (int i = 0; i < DevSwitches::N_BUDGETS; ++i) if ((v = env(budget_env[i]))) s.budget_mb[i] = std::max(1, atoi(v));
   if ((v = env("NAGP_KB_F"))) s.kb_f = std::max(1, std::min(16, atoi(v)));
   if ((v = env("NAGP_IH_KB"))) { const int kb = atoi(v); s.ih_kb = (kb == 4 || kb == 8 || kb == 16) ? kb : 0; }
@@ -451,6 +453,7 @@ struct Timed {
 #include "nagp_api_batch.hpp"
 #include "nagp_api_entry.hpp"
 #include "nagp_api_fastfb.hpp"
+#include "nagp_api_epsample.hpp"
 #include "nagp_api_slowfb.hpp"
 #include "nagp_api_nmf.hpp"
 #include "nagp_api_pstft.hpp"

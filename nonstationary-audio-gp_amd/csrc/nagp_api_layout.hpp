@@ -32,6 +32,21 @@ inline FbsBlock fbs_block(size_t S, size_t T, size_t ns, size_t nb) {
   Layout l; return {l.take(SS), l.take(SS), l.take(SS), l.take(SS), l.take(SS), l.take(S), l.take(S), l.take(S), l.take(T), l.take(ns * SSP), l.take(SSP), l.take(SSP),
           l.take(SSP + 8), l.take(nb * TS), l.take(nb * TS), l.take(nb * T), l.take(nb * T), l.take(nb * ns * S), l.take(nb * ns * S), l.total(0)};
 }
+// nagp_ep_sample: A | Q | P0 | Ab | Qb | h_val | off, boff, blk (int) | W | ttau | tnu | y | MF | PF / G | Lc | MS | counters | per batch: z | X | F | Sdraw
+// (z with the caller's normals, X / F / Sdraw when asked for; F also behind Sdraw)
+struct EpsBlock { size_t A, Q, p0, ab, qb, h, idx, w, tt, tn, y, mf, pg, lc, ms, cnt, z, x, f, sd, total; };
+inline size_t eps_fixed_bytes(size_t S, size_t M, size_t T, size_t nb2, size_t DN) {
+  return 8 * (T * (2 * S * S + 2 * S + 2 * M + 1) + 3 * S * S + 2 * nb2 + M + DN + 8) + 4 * (2 * M + 2 + S) + 4096;
+}
+inline size_t eps_draw_bytes(size_t S, size_t M, size_t T, bool z, bool x, bool f, bool sd) {
+  return std::max<size_t>(8, 8 * T * ((z ? S : 0) + (x ? S : 0) + (f || sd ? M : 0) + (sd ? 1 : 0)));
+}
+inline EpsBlock eps_block(size_t S, size_t M, size_t T, size_t nb2, size_t DN, bool z, bool x, bool f, bool sd, size_t nb) {
+  const size_t SS = S * S;
+  Layout l; return {l.take(SS), l.take(SS), l.take(SS), l.take(nb2), l.take(nb2), l.take(M), l.take((2 * M + 2 + S) / 2 + 1), l.take(DN), l.take(T * M), l.take(T * M), l.take(T),
+          l.take(T * S), l.take(T * SS), l.take(T * SS), l.take(T * S), l.take(4), l.take(z ? nb * T * S : 0), l.take(x ? nb * T * S : 0), l.take(f || sd ? nb * T * M : 0),
+          l.take(sd ? nb * T : 0), l.total(2)};
+}
 // nagp_slowfb_run: Ab | Qb | P0 | H | sub (int) | per batch: y | vary | lik | flag (int) | pm | pP | v | 1/s | K | r | N | MS | Pdiag | Psub
 // (v .. N only for the smoother, Pdiag when asked for; n ints lie in n / 2 + 1 doubles)
 struct SfbBlock { size_t ab, qb, p0, h, sub, y, vr, lik, fl, pm, pP, v, si, K, r, N, ms, pd, ps, total; };

@@ -30,3 +30,4 @@ from .tnmf import (basis2SEGP, getObj_fitSE_basis_func, getObj_nmf_log_norm, get
                    SebfFitHandle, fitSEGP_BF, fitSEGP_BF_many, randtnmf)
 from .train import nlml_batch, fd_value_and_gradient  # noqa: F401
 from .recon import reconstruct_signal, reconstruct_sources  # noqa: F401
+from .epsample import gf_ep_sample, ep_sample, ep_sample_timings  # noqa: F401

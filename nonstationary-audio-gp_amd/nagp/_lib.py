@@ -75,6 +75,10 @@ class ReconOut(C.Structure):
     _fields_ = [('Esig', c_dp), ('Vsig', c_dp), ('Esrc', c_dp), ('Vsrc', c_dp), ('Eenv', c_dp), ('Eft_mod', c_dp), ('Varft_mod', c_dp)]
 
 
+class EpSampleSig(C.Structure):
+    _fields_ = [('Wnmf', c_dp), ('amp_kind', C.c_int32), ('link_kind', C.c_int32), ('link_shift', C.c_double)]
+
+
 EXPORTS = ['nagp_version', 'nagp_device_count', 'nagp_strerror', 'nagp_last_error', 'nagp_ep_run',
            'nagp_ihgp_run', 'nagp_giekf_run', 'nagp_plan_create', 'nagp_plan_upload_y', 'nagp_plan_execute',
            'nagp_plan_timings', 'nagp_plan_download', 'nagp_plan_device_bytes', 'nagp_plan_destroy', 'nagp_plan_upload_sites',
@@ -87,7 +91,7 @@ EXPORTS = ['nagp_version', 'nagp_device_count', 'nagp_strerror', 'nagp_last_erro
            'nagp_tnmf_obj', 'nagp_tnmf_create', 'nagp_tnmf_eval', 'nagp_tnmf_destroy', 'nagp_tnmf_timings',
            'nagp_gppad_cas_obj', 'nagp_gppad_cas_create', 'nagp_gppad_cas_eval', 'nagp_gppad_cas_destroy', 'nagp_gppad_cas_timings',
            'nagp_gppad_lap_create', 'nagp_gppad_lap_hess', 'nagp_gppad_lap_apply', 'nagp_gppad_lap_eig', 'nagp_gppad_lap_varx', 'nagp_gppad_lap_obj',
-           'nagp_gppad_lap_destroy', 'nagp_gppad_lap_timings']
+           'nagp_gppad_lap_destroy', 'nagp_gppad_lap_timings', 'nagp_ep_sample', 'nagp_ep_sample_timings']
 NMFT_NONE, NMFT_TG, NMFT_IG = 0, 1, 2
 
 
@@ -223,6 +227,10 @@ def lib():
     L.nagp_fastfb_sample.argtypes = [C.c_int32, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp, C.c_double, c_dp, c_dp, c_dp, C.c_int64, C.c_int32, C.c_uint64,
                                      c_dp, c_dp, c_dp, C.c_int32]
     L.nagp_fastfb_sample.restype = C.c_int
+    L.nagp_ep_sample.argtypes = [C.POINTER(Model), c_dp, c_dp, c_dp, C.c_int64, C.c_int32, C.c_int32, C.c_uint64, c_dp, C.POINTER(EpSampleSig),
+                                 c_dp, c_dp, c_dp, c_dp, c_lp, C.c_int32]
+    L.nagp_ep_sample.restype = C.c_int
+    L.nagp_ep_sample_timings.argtypes = [c_dp]; L.nagp_ep_sample_timings.restype = C.c_int
     L.nagp_slowfb_run.argtypes = [C.c_int32, C.c_int32, c_dp, c_dp, c_dp, c_dp, C.c_int32, c_dp, c_dp, C.c_int64, C.c_int32, C.c_int32, c_ip,
                                   c_dp, c_dp, c_dp, c_dp, C.c_int32]
     L.nagp_slowfb_run.restype = C.c_int

@@ -77,6 +77,8 @@ class Plan:
         assert len(ys) == self.B and all(y.size == self.T for y in ys)
         arr = (L.c_dp * self.B)(*[L.dptr(y) for y in ys])
         L.check(L.lib().nagp_plan_upload_y(self._h, arr))
+        self._missing = [np.isnan(y) for y in ys]         # what sample() needs of the observations: which steps are missing
+        self._executed = False
 
     def upload_sites(self, ttau0=None, tnu0=None):
         """Warm start: initial site parameters (lists of M x T arrays, e.g. the ttau / tnu a previous call returned) in place
@@ -90,6 +92,7 @@ class Plan:
 
     def execute(self):
         L.check(L.lib().nagp_plan_execute(self._h))
+        self._executed = True
 
     def timings(self):
         t = L.Timings()
@@ -109,6 +112,24 @@ class Plan:
         arr = (L.Out * self.B)(*[L.Out(nlZ=nlz[q].ctypes.data_as(L.c_dp)) for q in range(self.B)])
         L.check(L.lib().nagp_plan_download(self._h, arr))
         return nlz
+
+    def sample(self, n_draws, seed=0, states=False, signal=None):
+        """Joint posterior draws of every problem of an executed KIND_GF_EP plan in predict mode (nagp_ep_sample on the sites the plan
+        holds): a list of (Fdraw, Xdraw or None, Sdraw or None, MS) per problem, as nagp.ep_sample returns them.  Refused for the other
+        kinds, for nlml mode, for plans with NAGP_FLAG_MIXTURE_RULE (the mixture drivers: under that rule the filter calls mom in every
+        sweep and the last sweep refreshes no site behind it, so the sites the plan holds have not been shown to be the ones its last
+        forward pass used -- the law of a draw would not be the plan's posterior) and before the plan has run on the uploaded data."""
+        from .epsample import ep_sample
+        if self.kind != L.KIND_GF_EP or self.opts.mode != L.MODE_PREDICT:
+            raise L.NagpError('libnagp: unsupported shape (%d): joint draws exist for KIND_GF_EP plans in predict mode' % -2)
+        if self.opts.flags & L.FLAG_MIXTURE_RULE:
+            raise L.NagpError('libnagp: unsupported shape (%d): joint draws are not offered for plans with FLAG_MIXTURE_RULE (the mixture drivers): '
+                              'their sites have not been shown to be those of the last forward pass, so the draws would not follow the plan\'s posterior' % -2)
+        if not getattr(self, '_executed', False):
+            raise L.NagpError('libnagp: invalid argument (%d): upload and execute the plan before sampling from it' % -1)
+        outs = self.download(want_MS=False)
+        return [ep_sample(p, o.ttau, o.tnu, np.where(m, np.nan, 0.0), n_draws, seed, self.opts.predict_at_k1, states, signal, device=self.opts.device)
+                for p, o, m in zip(self.probs, outs, self._missing)]
 
     def device_bytes(self):
         return int(L.lib().nagp_plan_device_bytes(self._h))
