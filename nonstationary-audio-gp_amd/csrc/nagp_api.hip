@@ -45,6 +45,7 @@ NAGP_LIST_SEBF(extern template __global__)
 #include <map>
 #include <memory>
 #include <thread>
+#include <tuple>
 #include <vector>
 
 #include <rccl/rccl.h>
@@ -83,6 +84,7 @@ struct DevSwitches {
   bool ih_roles = true;          // NAGP_IH_ROLES: off when the value starts with '0'
   bool ih_tables = false;        // NAGP_IH_TABLES: on when the value starts with '1' (table form of stage 1b: ihgp_adf8b_kernel)
   bool ih_qform = true;          // NAGP_IH_QFORM: off when the value starts with '0' (every D runs the run-time form of Q / 2Q / v, nagp_qform.hpp)
+  bool ih_place = true;          // NAGP_IH_PLACE: off when the value starts with '0' (ihgp_adf8_kernel reads the second copy of the lists, the weights at identity positions: msr_place_weights)
   int gain_form = 0;            // NAGP_GAIN_FORM: 0 = the plan's rule, 1 = solve, 2 = inv
   // numeric switches (0: not set, unless said otherwise)
   int chunks = 12;               // NAGP_CHUNKS (>= 1): smoother chunks per sweep
@@ -127,6 +129,7 @@ static DevSwitches read_dev_switches() {
   if ((v = env("NAGP_IH_ROLES"))) s.ih_roles = v[0] != '0';
   if ((v = env("NAGP_IH_TABLES"))) s.ih_tables = v[0] == '1';
   if ((v = env("NAGP_IH_QFORM"))) s.ih_qform = v[0] != '0';
+  if ((v = env("NAGP_IH_PLACE"))) s.ih_place = v[0] != '0';
   if ((v = env("NAGP_GAIN_FORM"))) s.gain_form = !strcmp(v, "solve") ? 1 : (!strcmp(v, "inv") ? 2 : 0);
   if ((v = env("NAGP_CHUNKS"))) s.chunks = std::max(1, atoi(v));
   if ((v = env("NAGP_PIPELINE_SLOTS"))) s.pipeline_slots = std::max(1, atoi(v));
@@ -204,6 +207,7 @@ struct nagp_plan {
   int a8_gf = 0, a8_tpt = 1, a8_st = 0, kb_a8 = 16; size_t lds_a8 = 0;   // ADF sweep of the gf filter with role-specialised waves (gf_adf8_kernel)
   int seq_ih = 0;      // developer switch NAGP_IH_SEQ in force: the sequential kernels (general ADF filter, ihgp_scan_kernel) in every sweep instead of the affine scans
   int sp_ih8 = 0; size_t lds_sp8 = 0;   // the role-specialised 512-thread form of the same sweep (ihgp_adf8_kernel, ihgp_adf8b_kernel)
+  int place_cyc[4] = {0, 0, 0, 0};      // modelled LDS cycles of the bin sums' member reads and of the weight stores: second copy | the copy ihgp_adf8_kernel reads (msr_place_weights)
   int qf_sp = 0;                        // ... its form of Q / 2Q / v on wave 0 (QForm, nagp_qform.hpp; the three-barrier schedule)
   hipStream_t stream = nullptr;
   // chunk-pipelined smoother (gf / giekf): while the sequential filter occupies one CU per problem, the parallel smoother kernels

@@ -5,6 +5,27 @@
 // Member and term lists of the role layout's cubature sums: msr_build_desc, nagp_msr_desc.hpp (host only; a stand-alone program reads it too)
 #include "nagp_msr_desc.hpp"
 
+// The placed copy of the lists and its position tables (msr_place_weights), searched once per rule and process: plans of one rule share it.
+// place = false (NAGP_IH_PLACE=0): the second copy and identity positions, the lists ihgp_adf8_kernel read before there was a placement.
+static void placed_lists(int CD, int nd, int c0, int npt, const std::vector<unsigned char>& code, const std::vector<int>& bd, bool place,
+                         std::vector<int>& placed, int cyc[4]) {
+  struct Entry { std::vector<int> placed; int cyc[4]; };
+  typedef std::tuple<int, int, int, int, std::vector<unsigned char>> Key;
+  static std::mutex mu;
+  static std::map<Key, Entry> cache;
+  if (!place) { msr_place_weights(CD, npt, bd, placed, cyc, 0); return; }
+  std::lock_guard<std::mutex> lk(mu);
+  const Key key(CD, nd, c0, npt, code);
+  auto it = cache.find(key);
+  if (it == cache.end()) {
+    Entry e;
+    msr_place_weights(CD, npt, bd, e.placed, e.cyc);
+    it = cache.emplace(key, std::move(e)).first;
+  }
+  placed = it->second.placed;
+  std::copy(it->second.cyc, it->second.cyc + 4, cyc);
+}
+
 // ---------------------------------------------------------------------------------------------
 static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, const nagp_ihgp_tables* tables,
                        int64_t T, const nagp_opts* o, const DevSwitches& dev) {
@@ -259,6 +280,10 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
         // the member / term lists of the role layout's cubature sums (<= one sigma point per worker lane)
         std::vector<int> bd;
         if (o->n_pts <= 64 * MSR_NWK && msr_build_desc(o->cub_dim, (int)xd.size(), c0, o->n_pts, code, bd)) {
+          // behind the two copies: the copy ihgp_adf8_kernel reads and its position tables (msr_desc_p_base(), msr_desc_pos_base())
+          std::vector<int> placed;
+          placed_lists(o->cub_dim, (int)xd.size(), c0, o->n_pts, code, bd, dev.ih_place, placed, p->place_cyc);
+          bd.insert(bd.end(), placed.begin(), placed.end());
           double* db = nullptr;
           PLAN_TRY(dalloc(p, &db, (bd.size() + 1) / 2 + 1, false));
           PLAN_HIP(hipMemcpyAsync(db, bd.data(), bd.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
@@ -620,7 +645,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
     }
     p->seq_ih = dev.ih_seq && !p->sq_ih && !p->sp_ih && !p->src_f;
     if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);
-    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B), table form of stage 1b %d, Q/v form %s, sequential kernels in every sweep %d\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8, (int)(p->sp_ih8 && dev.ih_tables), qform_name(p->qf_sp), p->seq_ih);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B), table form of stage 1b %d, Q/v form %s, weights placed %d (LDS cycles of member reads + weight stores %d + %d, second copy %d + %d), sequential kernels in every sweep %d\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8, (int)(p->sp_ih8 && dev.ih_tables), qform_name(p->qf_sp), (int)dev.ih_place, p->place_cyc[2], p->place_cyc[3], p->place_cyc[0], p->place_cyc[1], p->seq_ih);
     PLAN_TRY(set_kernel(p->k.ih_filter, pick_ih_filter(mom_variant(mc), p->src_f, sh.BS == 8), p->lds_ih));
     for (int mode = 0; mode < 2; ++mode) {      // the affine scans and the sequential scan use no dynamic LDS
       PLAN_TRY(set_kernel(p->k.aff_compose[mode], pick_aff_compose(mode, sh.BS), 0));

@@ -713,11 +713,14 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   __syncthreads();
   if (wave >= MSR_W0) {
     // ================= worker role: the parallel stages of the cubature; the same barriers as the serial role below
-    MsrW<CD> xw;
-    msr_setup_W<CD>(xw, mc, sp, ld.sW, ld.fmu, ld.HPH, ld.ws, false, msr_desc_w_base());
+    // the placed copy of the lists and its position tables: the point's three weights each where the bin sums' reads collide least (with
+    // NAGP_IH_PLACE=0 the plan hands in the second copy and identity positions there)
+    MsrW<CD, true> xw;
+    msr_setup_W<CD>(xw, mc, sp, ld.sW, ld.fmu, ld.HPH, ld.ws, false, msr_desc_p_base(), sp.bdesc + msr_desc_pos_base());
     // Q | 2Q | v of the weights behind ONE address register: every word of the region is then read through an instruction offset, where
     // the compiler otherwise rebuilds an address per pair of reads every step
     asm volatile("" : "+v"(xw.d_qv));
+    asm volatile("" : "+v"(xw.p_c[0]), "+v"(xw.p_c1[0]), "+v"(xw.p_c2[0]));      // (three stores through three registers, no address rebuilt per step)
     // developer diagnostics (NAGP_STAMPS): time lines of worker (NAGP_STAMP_WORKER & 7) in stamps[8..15] and of the last worker in
     // stamps[16..23]
     const int wk_slot = (wave == MSR_W0 + (ip.dbg_wave & 7)) ? 8 : ((wave == MSR_W0 + MSR_NWK - 1) ? 16 : -1);
@@ -816,7 +819,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   }
   // ================= serial role (waves 0 and 1)
   MsrS<CD> x;
-  msr_setup_S<CD>(x, mc, sp, ld.fmu, ld.HPH, ld.ws, msr_desc_w_base());      // (the reduction reads the level-2 slots of the workers' copy of the lists)
+  msr_setup_S<CD>(x, mc, sp, ld.fmu, ld.HPH, ld.ws, msr_desc_p_base());      // (the reduction reads the level-2 slots of the workers' copy of the lists)
   MsrQ<CD> xq;                                       // Q / 2Q / v on wave 0
   MsrRT rt;                                          // table words of the reduction, read ahead of B5
   msr_setup_Q<CD>(xq, mc, ld.sW, ld.fmu, ld.HPH, ld.ws);

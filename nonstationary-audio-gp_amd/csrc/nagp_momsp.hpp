@@ -472,9 +472,15 @@ __device__ __forceinline__ void msr_stage1b_direct(const X& x, double sn2a, doub
   gauss_terms<LE0>(y, sam, sn2a + sa2, pdf, q, inv);
   const double w0 = x.p_wn[0] * pdf;
   if (x.p_ok[0]) {
-    x.p_c[0][0] = w0;
-    x.p_c[0][X::CS] = w0 * q;
-    x.p_c[0][2 * X::CS] = w0 * (q * q - inv);
+    if constexpr (X::PLACED) {
+      x.p_c[0][0] = w0;
+      x.p_c1[0][0] = w0 * q;
+      x.p_c2[0][0] = w0 * (q * q - inv);
+    } else {
+      x.p_c[0][0] = w0;
+      x.p_c[0][X::CS] = w0 * q;
+      x.p_c[0][2 * X::CS] = w0 * (q * q - inv);
+    }
   }
 }
 
@@ -652,12 +658,15 @@ struct MsrS {
   double xdc; msp_rp a_mu, a_s2, a_l0[CD], a_l0own, a_qrow, a_qjj, a_v; msp_wp a_out;
   msp_rp r_p[MSR_RW]; msp_wp r_dst; msp_rp accp;
 };
-template <int CD>
+// PL: the point's three weights are stored through three addresses of their own, p_c / p_c1 / p_c2 (the placed copy of the lists and its
+// position tables, nagp_msr_desc.hpp: msr_place_weights); otherwise at p_c + k CS, and p_c1 / p_c2 have no reader
+template <int CD, bool PL = false>
 struct MsrW {
   static constexpr int NPS = 1, CS = MSR_CS;
+  static constexpr bool PLACED = PL;
   int q_kind; msp_rp q_ww, q_src; msp_wp q_out0, q_out1, q_out2, q_out3;
   int b_kind; msp_rp b_p0, b_p1, b_p2;
-  msp_rp p_e[1][MSP_NZ], p_q[1][6]; msp_wp p_c[1]; double p_wn[1]; bool p_ok[1]; int p_any[1];   // (p_e, p_q: table form of stage 1b)
+  msp_rp p_e[1][MSP_NZ], p_q[1][6]; msp_wp p_c[1], p_c1[1], p_c2[1]; double p_wn[1]; bool p_ok[1]; int p_any[1];   // (p_e, p_q: table form of stage 1b)
   msp_rp d_lk[CD], d_qv;                                              // direct form of stage 1b: this point's link entries; Q | 2Q | v (uniform)
   msp_rp s_mem[MSR_NMEM]; msp_wp s_out; int s_grp;                    // level 1: members, result slot, group flags (1: lane ^ 1, 2: lane ^ 2)
   msp_rp t_bin[MSR_KT], t_fa[MSR_KT], t_fb[MSR_KT]; msp_wp t_out; int t_grp;   // level 2
@@ -727,9 +736,11 @@ __device__ __forceinline__ void msr_setup_sums(X& x, const int* bdesc, int dbase
 }
 
 // qv = false: Q / 2Q / v are formed on serial wave 0 (msr_setup_Q, msr_qv_serial), which then owns the wwt region; no worker lane takes a part
-template <int CD>
-__device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const MomSp& sp, const double* Wl /* LDS D x CD */,
-                                             const double* fmu, const double* HPH, double* ws, bool qv = true, int dbase = 0) {
+// pos (PL only): the position tables of the copy at dbase, pos[k * MSR_NL + p] = where in c_k the weight k of point p sits
+template <int CD, bool PL>
+__device__ __forceinline__ void msr_setup_W(MsrW<CD, PL>& x, const MomCfg& c, const MomSp& sp, const double* Wl /* LDS D x CD */,
+                                             const double* fmu, const double* HPH, double* ws, bool qv = true, int dbase = 0,
+                                             const int* pos = nullptr) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wr = wave - MSR_W0;     // wr = 0 .. 5
   const int nd = c.nd, D = c.D, npt = c.n_pts;
   const MspLay l = msp_layout(CD, D, 1);
@@ -800,7 +811,14 @@ __device__ __forceinline__ void msr_setup_W(MsrW<CD>& x, const MomCfg& c, const 
         x.p_q[0][pi] = (tj[r] >= 0 && tj[s_] >= 0) ? (msp_rp)(ws + l.Q2 + (tj[r] >> 6) * CD + (tj[s_] >> 6)) : zero;
         ++pi;
       }
-    x.p_c[0] = (msp_wp)(ws + l.c0 + p);
+    if constexpr (PL) {
+      x.p_c[0] = (msp_wp)(ws + l.c0 + pos[p]);
+      x.p_c1[0] = (msp_wp)(ws + l.c1 + pos[MSR_NL + p]);
+      x.p_c2[0] = (msp_wp)(ws + l.c2 + pos[2 * MSR_NL + p]);
+    } else {
+      x.p_c[0] = (msp_wp)(ws + l.c0 + p);
+      x.p_c1[0] = x.p_c[0] + MSR_CS; x.p_c2[0] = x.p_c[0] + 2 * MSR_CS;
+    }
     x.p_wn[0] = ok ? c.wn[p] : 0.0;
     // direct form: the link entry of every dimension at this point's coordinate code (the centre's code where pdesc names none)
 #pragma unroll

@@ -288,4 +288,136 @@ inline bool msr_build_desc(int CD, int nd, int c0, int npt, const std::vector<un
   return true;
 }
 
+// ---------------------------------------------------------------------------------------------
+// The placed copy.  What still collides in the second copy is WHERE a point's three weights sit inside c0 / c1 / c2: point p at offset p in
+// all three, so the three bins of a (dimension, coordinate) read the same points one pair of banks apart, and the five chunks of a total
+// read points 64 doubles apart, on the same banks.  The writer of the weights (msr_stage1b_direct) stores through a per-lane address and
+// the readers (msr_sums) load through per-lane member addresses, so a position table per kind of weight, pos[k][p] in [0, MSR_NL), moves
+// the weights without moving anything else: MspLay, MSR_CS and the lists' lanes, slots, terms and flags stay.  Which number is added to
+// which, and in which order, does not change.
+//   [msr_desc_p_base(), + msr_desc_ints())       the second copy with every member c_k + p rewritten to c_k + pos[k][p]
+//   [msr_desc_pos_base(), + 3 MSR_NL)            pos[0] | pos[1] | pos[2], each a permutation of [0, MSR_NL) (beyond the points: the slots left over)
+// both behind the two copies of msr_build_desc in the plan's buffer; msr_place_weights returns them as one vector of msr_placed_ints().
+NAGP_QF_HD inline int msr_desc_p_base() { return msr_desc_w_ints(); }
+NAGP_QF_HD inline int msr_desc_pos_base() { return msr_desc_p_base() + msr_desc_ints(); }
+NAGP_QF_HD inline int msr_placed_ints() { return msr_desc_ints() + 3 * MSR_NL; }
+NAGP_QF_HD inline int msr_desc_p_ints() { return msr_desc_w_ints() + msr_placed_ints(); }
+
+// LDS cycles of the three weight stores (ds_write_b64, counted as a read is: per half of a wave, the most addresses on one pair of banks)
+// of every worker wave that holds a point: lane = point - 64 wave, lanes without a point do not store.  pos: 3 x MSR_NL.
+inline int msr_store_cycles(int CD, int npt, const int* pos) {
+  const MspLay l = msp_layout(CD, 1, 1);
+  int total = 0;
+  for (int k = 0; k < 3; ++k)
+    for (int h = 0; 32 * h < npt; ++h) {
+      int cnt[32] = {0}, mx = 0;
+      for (int p = 32 * h; p < std::min(npt, 32 * h + 32); ++p) mx = std::max(mx, ++cnt[(l.c0 + k * MSR_CS + pos[k * MSR_NL + p]) & 31]);
+      total += mx;
+    }
+  return total;
+}
+
+constexpr int MSR_PLACE_MOVES = 24000;   // proposals of the search: about 2 ms of plan creation, once per rule and process
+constexpr int MSR_PLACE_STORE_W = 1;     // weight of a store cycle against a read cycle in the search's cost
+
+// Position tables and placed copy for the lists dsc_in (msr_build_desc's vector).  A hill-climb over swaps of two positions of one kind of
+// weight, from the identity; the cost is msr_member_cycles of the placed copy plus MSR_PLACE_STORE_W * msr_store_cycles, evaluated
+// incrementally: per read or store and half of a wave a count per pair of banks (the members of one half are different addresses but for
+// the zero word, so a count is a number of addresses), and a swap touches only the halves that hold one of the two points.  Integer
+// arithmetic and a generator of its own: the same tables on every host.  Where the search does not lower the cost, the placed copy is the
+// second copy and the positions are the identity.  Returns the cost's two parts through cyc (before: reads, stores; after: reads, stores).
+inline void msr_place_weights(int CD, int npt, const std::vector<int>& dsc_in, std::vector<int>& placed, int cyc[4] = nullptr,
+                              int moves = MSR_PLACE_MOVES, int store_w = MSR_PLACE_STORE_W) {
+  const MspLay l = msp_layout(CD, 1, 1);
+  const int* D1 = dsc_in.data() + msr_desc_w_base();
+  placed.assign((size_t)msr_placed_ints(), 0);
+  std::copy(D1, D1 + msr_desc_ints(), placed.begin());
+  int* const pos = placed.data() + msr_desc_ints();
+  for (int k = 0; k < 3; ++k) for (int i = 0; i < MSR_NL; ++i) pos[k * MSR_NL + i] = i;
+  const int reads0 = msr_member_cycles(D1), stores0 = msr_store_cycles(CD, npt, pos);
+  if (cyc) { cyc[0] = cyc[2] = reads0; cyc[1] = cyc[3] = stores0; }
+  // halves: the reads (wave, slot, half), then the stores (kind, wave, half)
+  constexpr int NRH = MSR_NWK * MSR_NMEM * 2, NH = NRH + 3 * MSR_NWK * 2;
+  struct Half { unsigned char cnt[32]; int mx, wt; };
+  std::vector<Half> hv(NH);
+  for (int i = 0; i < NH; ++i) { std::fill(hv[i].cnt, hv[i].cnt + 32, (unsigned char)0); hv[i].mx = 0; hv[i].wt = i < NRH ? 1 : store_w; }
+  std::vector<std::vector<int>> in(3 * MSR_NL);            // item (k, p) -> the halves that hold it
+  auto bank = [&](int k, int slot) { return (l.c0 + k * MSR_CS + slot) & 31; };
+  for (int w = 0; w < MSR_NWK; ++w)
+    for (int s = 0; s < MSR_NMEM; ++s)
+      for (int i = 0; i < 64; ++i) {
+        const int a = D1[(size_t)(w * 64 + i) * MSR_DW + s], hid = (w * MSR_NMEM + s) * 2 + i / 32;
+        if (a == l.zero) { hv[hid].cnt[a & 31] = 1; continue; }      // (one address however many lanes read it)
+        std::vector<int>& v = in[(a - l.c0) / MSR_CS * MSR_NL + (a - l.c0) % MSR_CS];
+        if (std::find(v.begin(), v.end(), hid) == v.end()) { v.push_back(hid); ++hv[hid].cnt[a & 31]; }
+      }
+  for (int k = 0; k < 3; ++k)
+    for (int p = 0; p < npt; ++p) { const int hid = NRH + (k * MSR_NWK + p / 64) * 2 + (p % 64) / 32; in[k * MSR_NL + p].push_back(hid); ++hv[hid].cnt[bank(k, p)]; }
+  auto hmax = [](const Half& h) { int m = 0; for (int b = 0; b < 32; ++b) m = std::max(m, (int)h.cnt[b]); return m; };
+  for (Half& h : hv) h.mx = hmax(h);
+  std::vector<int> inv(3 * MSR_NL, -1);                    // (k, slot) -> the point there
+  for (int k = 0; k < 3; ++k) for (int p = 0; p < npt; ++p) inv[k * MSR_NL + p] = p;
+  std::vector<int> mark(NH, -1), touched, nmx;
+  unsigned long long rng = 0x9E3779B97F4A7C15ull;
+  auto rnd = [&](int n) { rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17; return (int)((rng >> 16) % (unsigned)n); };
+  std::vector<std::vector<int>> held(NH);                  // half -> its items
+  for (int i = 0; i < 3 * MSR_NL; ++i) for (int hid : in[i]) held[hid].push_back(i);
+  for (int it = 0; it < moves; ++it) {
+    // the point to move: one of a busiest pair of banks of a half drawn at random (every other proposal), or any point
+    int k = rnd(3), p = rnd(npt);
+    if (it & 1) {
+      const int hid = rnd(NH), n = (int)held[hid].size();
+      if (n == 0 || hv[hid].mx < 2) continue;
+      const int i0 = rnd(n);
+      int found = -1;
+      for (int i = 0; i < n && found < 0; ++i) {
+        const int item = held[hid][(i0 + i) % n], kk = item / MSR_NL;
+        if (hv[hid].cnt[bank(kk, pos[item])] == hv[hid].mx) found = item;
+      }
+      if (found < 0) continue;      // (the busiest pair holds the zero word and one point less)
+      k = found / MSR_NL; p = found % MSR_NL;
+    }
+    const int b = rnd(MSR_NL), a = pos[k * MSR_NL + p], q = inv[k * MSR_NL + b];
+    const int ba = bank(k, a), bb = bank(k, b);
+    if (ba == bb) continue;
+    touched.clear();
+    int d2 = 0;      // the same move's change of the sum of squared counts: what ranks two moves that leave every busiest pair as busy
+    auto shift = [&](int pt, int from, int to) {
+      for (int hid : in[k * MSR_NL + pt]) {
+        d2 += hv[hid].wt * (2 * ((int)hv[hid].cnt[to] - (int)hv[hid].cnt[from]) + 2);
+        --hv[hid].cnt[from]; ++hv[hid].cnt[to];
+        if (mark[hid] != it) { mark[hid] = it; touched.push_back(hid); }
+      }
+    };
+    shift(p, ba, bb);
+    if (q >= 0) shift(q, bb, ba);
+    int delta = 0;
+    nmx.clear();
+    for (int hid : touched) { nmx.push_back(hmax(hv[hid])); delta += hv[hid].wt * (nmx.back() - hv[hid].mx); }
+    if (delta < 0 || (delta == 0 && d2 <= 0)) {
+      for (size_t i = 0; i < touched.size(); ++i) hv[touched[i]].mx = nmx[i];
+      pos[k * MSR_NL + p] = b; inv[k * MSR_NL + b] = p; inv[k * MSR_NL + a] = q;
+      if (q >= 0) pos[k * MSR_NL + q] = a;
+    } else {
+      for (int hid : in[k * MSR_NL + p]) { ++hv[hid].cnt[ba]; --hv[hid].cnt[bb]; }
+      if (q >= 0) for (int hid : in[k * MSR_NL + q]) { ++hv[hid].cnt[bb]; --hv[hid].cnt[ba]; }
+    }
+  }
+  // positions beyond the points: the slots no point took, in rising order (each table stays a permutation of [0, MSR_NL))
+  for (int k = 0; k < 3; ++k) {
+    int p = npt;
+    for (int s = 0; s < MSR_NL; ++s) if (inv[k * MSR_NL + s] < 0) pos[k * MSR_NL + p++] = s;
+  }
+  for (int L = 0; L < MSR_NL; ++L)
+    for (int s = 0; s < MSR_NMEM; ++s) {
+      int& a = placed[(size_t)L * MSR_DW + s];
+      if (a != l.zero) { const int k = (a - l.c0) / MSR_CS; a = l.c0 + k * MSR_CS + pos[k * MSR_NL + (a - l.c0) % MSR_CS]; }
+    }
+  const int reads1 = msr_member_cycles(placed.data()), stores1 = msr_store_cycles(CD, npt, pos);
+  if (reads1 + store_w * stores1 >= reads0 + store_w * stores0) {
+    std::copy(D1, D1 + msr_desc_ints(), placed.begin());
+    for (int k = 0; k < 3; ++k) for (int i = 0; i < MSR_NL; ++i) pos[k * MSR_NL + i] = i;
+  } else if (cyc) { cyc[2] = reads1; cyc[3] = stores1; }
+}
+
 }  // namespace nagp
