@@ -209,6 +209,7 @@ struct nagp_plan {
   int sp_ih8 = 0; size_t lds_sp8 = 0;   // the role-specialised 512-thread form of the same sweep (ihgp_adf8_kernel, ihgp_adf8b_kernel)
   int place_cyc[4] = {0, 0, 0, 0};      // modelled LDS cycles of the bin sums' member reads and of the weight stores: second copy | the copy ihgp_adf8_kernel reads (msr_place_weights)
   int qf_sp = 0;                        // ... its form of Q / 2Q / v on wave 0 (QForm, nagp_qform.hpp; the three-barrier schedule)
+  int thr_ok = 0; double thr_us = 0.0;  // ... its look-up from ttau: the grid gave a proved threshold table (lookup_thresholds); microseconds of the search, 0 on a cache hit
   hipStream_t stream = nullptr;
   // chunk-pipelined smoother (gf / giekf): while the sequential filter occupies one CU per problem, the parallel smoother kernels
   // of the chunks it has finished (rts_gain + the compose pass) run on `stream2` on the rest of the chip

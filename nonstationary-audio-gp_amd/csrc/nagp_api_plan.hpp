@@ -26,6 +26,28 @@ static void placed_lists(int CD, int nd, int c0, int npt, const std::vector<unsi
   std::copy(it->second.cyc, it->second.cyc + 4, cyc);
 }
 
+// The threshold table of the look-up from ttau (lookup_thresholds, nagp_lookup.hpp), searched once per grid and process.  us: the time
+// of the search in microseconds, 0 when the grid was in the cache.
+static bool grid_thresholds(const double* r, int NG, double lr0, double inv_dlr, std::vector<double>& ext, double& us) {
+  struct Entry { std::vector<double> ext; bool ok; };
+  static std::mutex mu;
+  static std::map<std::vector<double>, Entry> cache;
+  std::lock_guard<std::mutex> lk(mu);
+  const std::vector<double> key(r, r + NG);
+  us = 0.0;
+  auto it = cache.find(key);
+  if (it == cache.end()) {
+    Entry e;
+    e.ext.resize((size_t)lookup_thr_doubles(NG));
+    const auto t0 = std::chrono::steady_clock::now();
+    e.ok = lookup_thresholds(r, NG, lr0, inv_dlr, e.ext.data());
+    us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
+    it = cache.emplace(key, std::move(e)).first;
+  }
+  ext = it->second.ext;
+  return it->second.ok;
+}
+
 // ---------------------------------------------------------------------------------------------
 static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, const nagp_ihgp_tables* tables,
                        int64_t T, const nagp_opts* o, const DevSwitches& dev) {
@@ -571,13 +593,18 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
       }
     }
     PLAN_TRY(dalloc(p, &p->d_tab, ht.size(), false));
-    PLAN_TRY(dalloc(p, &p->d_r, NG, false));
-    PLAN_HIP(hipMemcpyAsync(p->d_tab, ht.data(), ht.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    PLAN_HIP(hipMemcpyAsync(p->d_r, tables[0].r_grid, (size_t)NG * sizeof(double), hipMemcpyHostToDevice, p->stream));
-    PLAN_HIP(hipStreamSynchronize(p->stream));
-    p->tb.NG = NG; p->tb.r = p->d_r; p->tb.base = p->d_tab;
+    p->tb.NG = NG; p->tb.base = p->d_tab;
     p->tb.lr0 = std::log10(tables[0].r_grid[0]);
     p->tb.inv_dlr = (double)(NG - 1) / (std::log10(tables[0].r_grid[NG - 1]) - p->tb.lr0);
+    // behind the grid: the steps of the index as a function of ttau, t_beyond, t_inf and the seed's integers (ihgp_adf8_kernel)
+    std::vector<double> hr(tables[0].r_grid, tables[0].r_grid + NG), ext;
+    p->thr_ok = grid_thresholds(tables[0].r_grid, NG, p->tb.lr0, p->tb.inv_dlr, ext, p->thr_us) ? 1 : 0;
+    hr.insert(hr.end(), ext.begin(), ext.end());
+    PLAN_TRY(dalloc(p, &p->d_r, hr.size(), false));
+    PLAN_HIP(hipMemcpyAsync(p->d_tab, ht.data(), ht.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    PLAN_HIP(hipMemcpyAsync(p->d_r, hr.data(), hr.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
+    PLAN_HIP(hipStreamSynchronize(p->stream));
+    p->tb.r = p->d_r;
   }
 
   // ---- LDS sizes / kernel attributes
@@ -613,7 +640,8 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
         // role-specialised waves (ihgp_adf8_kernel; seven components and the table form: ihgp_adf8b_kernel): two serial + six worker waves, one sigma point per worker lane, the cubature sums from bin sums (msr_build_desc)
         // (its workspace is the larger one: where it alone does not fit, it gives up the same residents in the same order -- only one of the
         // two kernels is launched, so the ring and the table setting are that kernel's)
-        if (p->sp.bdesc && dev.ih_roles) {
+        // (the three-barrier kernel looks its tables up from ttau: a grid without a proved threshold table runs the four-wave kernel)
+        if (p->sp.bdesc && dev.ih_roles && (p->thr_ok || dev.ih_tables || o->cub_dim > 6)) {
           const int kb0 = p->kb_sp, hph0 = p->hph_sp;
           auto need8 = [&]() { return ihgp_adf8_lds_doubles(sh, o->cub_dim, p->tb.NG, p->hph_sp, p->kb_sp) * sizeof(double) + 16; };
           if (need8() > 156 * 1024) p->kb_sp = 8;
@@ -645,7 +673,7 @@ static int plan_create(nagp_plan** out, int32_t B, const nagp_model* models, con
     }
     p->seq_ih = dev.ih_seq && !p->sq_ih && !p->sp_ih && !p->src_f;
     if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep, square-root amplitudes in the staged form: %d (LDS %zu B, ring %d steps, hph table in LDS %d)\n", p->sq_ih, p->lds_sq, p->kb_sq, p->hph_sq);
-    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B), table form of stage 1b %d, Q/v form %s, weights placed %d (LDS cycles of member reads + weight stores %d + %d, second copy %d + %d), sequential kernels in every sweep %d\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8, (int)(p->sp_ih8 && dev.ih_tables), qform_name(p->qf_sp), (int)dev.ih_place, p->place_cyc[2], p->place_cyc[3], p->place_cyc[0], p->place_cyc[1], p->seq_ih);
+    if (dev.stamps) fprintf(stderr, "[nagp plan] ihgp ADF sweep in the sparse-point form: %d (LDS %zu B, ring %d steps, hph table in LDS %d), role-specialised waves %d (LDS %zu B), table form of stage 1b %d, Q/v form %s, weights placed %d (LDS cycles of member reads + weight stores %d + %d, second copy %d + %d), look-up thresholds proved %d (searched in %.0f us), sequential kernels in every sweep %d\n", p->sp_ih, p->lds_sp, p->kb_sp, p->hph_sp, p->sp_ih8, p->lds_sp8, (int)(p->sp_ih8 && dev.ih_tables), qform_name(p->qf_sp), (int)dev.ih_place, p->place_cyc[2], p->place_cyc[3], p->place_cyc[0], p->place_cyc[1], p->thr_ok, p->thr_us, p->seq_ih);
     PLAN_TRY(set_kernel(p->k.ih_filter, pick_ih_filter(mom_variant(mc), p->src_f, sh.BS == 8), p->lds_ih));
     for (int mode = 0; mode < 2; ++mode) {      // the affine scans and the sequential scan use no dynamic LDS
       PLAN_TRY(set_kernel(p->k.aff_compose[mode], pick_aff_compose(mode, sh.BS), 0));

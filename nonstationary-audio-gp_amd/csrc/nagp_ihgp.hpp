@@ -316,8 +316,11 @@ __host__ __device__ inline size_t ihgp_adf_lds_doubles(const Shape& s, int CD, i
   return (size_t)s.D * s.N + 2 * 68 + NG + (hph_lds ? (size_t)s.M * NG : 0) + ihgp_adf_ring_doubles(s, kb) + (s.S + 1) / 2 + 2 +
          msp_lds_doubles(CD, s.D);
 }
+// (ih_thr_tail: the steps of the look-up from ttau, NG - 1 doubles behind the state map of ihgp_adf8_kernel; an even count keeps the
+// workspace behind it 16-byte aligned)
+__host__ __device__ inline int ih_thr_tail(int NG) { return NG + (NG & 1); }
 __host__ __device__ inline size_t ihgp_adf8_lds_doubles(const Shape& s, int CD, int NG, int hph_lds, int kb) {
-  return ihgp_adf_lds_doubles(s, CD, NG, hph_lds, kb) - msp_lds_doubles(CD, s.D) + msp_lds_doubles(CD, s.D, 1);
+  return ihgp_adf_lds_doubles(s, CD, NG, hph_lds, kb) - msp_lds_doubles(CD, s.D) + msp_lds_doubles(CD, s.D, 1) + ih_thr_tail(NG);
 }
 
 // [~,ind] = min(abs(r-R)) as nearest_idx_lds, with a three-point window around the seed: the seed's error (0.003 in log10,
@@ -642,6 +645,27 @@ __device__ __forceinline__ void ih_window_pick(int mid, double r0, double r1, do
   } else if (!hph_in_lds) hph = g_hph[idx];      // (issued ahead of the ring stores; first used, and so waited for, where the head stores HPH)
 }
 
+// The look-up inside the loop, from ttau alone (nagp_lookup.hpp: lookup_mid_bits, lookup_pick_thr): the two steps tau[mid - 1], tau[mid]
+// in place of the three grid words, and a pick that waits for no division.  ttau <= t_inf (R = Inf): index 0 and its H PP H' (h_first, a
+// register of the launch).  R itself is read only on the side path t_inf < ttau <= t_beyond (finite R beyond the grid, lookup_tail).
+__device__ __forceinline__ void ih_thr_reads(msp_rp p_thr, msp_rp p_hph, bool hph_in_lds, int mid, double& ta, double& tb, double& h0, double& h1, double& h2) {
+  ta = p_thr[mid - 1]; tb = p_thr[mid];
+  if (hph_in_lds) { h0 = p_hph[mid - 1]; h1 = p_hph[mid]; h2 = p_hph[mid + 1]; }
+}
+__device__ __forceinline__ void ih_thr_pick(int mid, double ta, double tb, double h0, double h1, double h2, double h_first, msp_rp p_rg, msp_rp p_hph,
+                                            const double* g_hph, bool hph_in_lds, double t_beyond, double t_inf, int NG, double ttau, double R, int& idx,
+                                            double& hph) {
+  const int sel = lookup_pick_thr(ta, tb, ttau);
+  const bool at_inf = ttau <= t_inf;
+  idx = at_inf ? 0 : mid - 1 + sel;
+  hph = (sel == 0) ? h0 : ((sel == 1) ? h1 : h2);
+  hph = at_inf ? h_first : hph;
+  if (ttau <= t_beyond && !at_inf) {
+    idx = lookup_tail(p_rg, NG, R);
+    hph = hph_in_lds ? p_hph[idx] : g_hph[idx];
+  } else if (!hph_in_lds && !at_inf) hph = g_hph[idx];      // (issued ahead of the ring stores; first used, and so waited for, where the head stores HPH)
+}
+
 // The same sweep with role-specialised waves (nagp_momsp.hpp, role layout): 512 threads, waves 0 / 1 as above, waves 2..7 run the
 // parallel stages of the cubature in their own loop.  A wave holds the registers of its role only, which is what lets two
 // waves share a SIMD.
@@ -662,11 +686,14 @@ __device__ __forceinline__ void ih_window_pick(int mid, double r0, double r1, do
 //   level-2 results (part)     workers, B4 .. B5                    msr_reduce_bins, behind B5                   B2, B4 of step k+1
 //   c0 / c1 / c2, acc          as in ihgp_adf8b_kernel              (weights B2 .. B4, level 1 B4 .. B5; acc: one wave)
 //   wwt (static products)      wave 0, once                         wave 0                                       same lane
-//   W rows, look-up grid, H PP H' table: written ahead of the loop (one __syncthreads), read-only in it -- wave 0 reads its row of W
-//     between B4 and B5, both serial waves three grid words and three table entries round the seed in the site update (one batch of reads)
-// The look-up of step k+1 is seeded from ttau (lookup_mid_ttau_c, nagp_lookup.hpp) straight behind the clamp of the site update: the seed,
-// the address and the six reads run beside the exact division R = 1 / ttau and are waited for where R arrives, ahead of the ring stores;
-// behind R only the branch beyond the grid (finite R > rmax: lookup_tail), the pick among the three and the selects are left.
+//   W rows, look-up grid and its threshold table, H PP H' table: written ahead of the loop (one __syncthreads), read-only in it -- wave 0
+//     reads its row of W between B4 and B5, both serial waves two thresholds and three table entries round the seed in the site update
+//     (one batch of reads; the grid words only on the side path beyond the grid)
+// The look-up of step k+1 comes from ttau alone (nagp_lookup.hpp), straight behind the clamp of the site update: the window's centre from
+// the bit pattern of ttau by integer operations (lookup_mid_bits), two steps of the grid's threshold table and three table entries in one
+// batch of reads, the index as the count of steps at or above ttau.  The gain is (tnu - fmu ttau) / (1 + HPH ttau).  The exact division
+// R = 1 / ttau stands ahead of the ring stores in program order and feeds them, Rprev and the side branch beyond the grid (finite
+// R > rmax, entered by t_inf < ttau <= t_beyond: lookup_tail); nothing on the straight path waits for it.
 // The serial tail waits for none of its ring stores: no LDS read of the straight path is issued behind them, and the loop reads
 // no kernel argument in the head or the site update (a scalar load there would bring an lgkmcnt(0) for the stores with it): the look-up's
 // constants are copied into vector registers ahead of the loop.
@@ -706,10 +733,12 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   const int S = sh.S, M = sh.M, D = sh.D, NG = tb.NG, KB = ip.kb;
   const int64_t T = sh.T;
   IhLds ld;
-  ih_lds_setup(ld, lds, sh, b, mc, tb, ip, CD, 0, tid, NT);
+  ih_lds_setup(ld, lds, sh, b, mc, tb, ip, CD, ih_thr_tail(NG), tid, NT);
   IhRows gr;                                         // (the streamed ring: the I/O lanes of the worker role fill and flush it)
   ih_rows(gr, sh, b);
   msr_init(CD, D, ld.ws);
+  // the steps tau[NG - 1] of the look-up from ttau (lookup_thresholds: the plan uploads them behind the grid), read-only in the loop
+  for (int i = tid; i < NG - 1; i += NT) ld.tail[i] = tb.r[NG + i];
   __syncthreads();
   if (wave >= MSR_W0) {
     // ================= worker role: the parallel stages of the cubature; the same barriers as the serial role below
@@ -843,18 +872,22 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   double lk_lr0 = tb.lr0, lk_inv = tb.inv_dlr, lk_rmax = ld.rmax;
   int lk_ng2 = NG - 2;
   asm volatile("" : "+v"(lk_lr0), "+v"(lk_inv), "+v"(lk_rmax), "+v"(lk_ng2));
-  double lk_c1, lk_c0;                               // the seed from ttau: its two folded constants
-  lookup_seed_consts(tb.lr0, tb.inv_dlr, lk_c1, lk_c0);
-  asm volatile("" : "+v"(lk_c1), "+v"(lk_c0));
+  // the look-up from ttau (nagp_lookup.hpp): t_beyond, t_inf and the seed's two integers from the table behind the grid; the steps
+  // themselves are in LDS (p_thr), and the lane's H PP H' of index 0 -- what a site with ttau <= t_inf (R = Inf) selects -- is a register
+  double lk_tbey = tb.r[2 * NG - 1], lk_tinf = tb.r[2 * NG];
+  unsigned int lk_c1 = (unsigned int)tb.r[2 * NG + 1]; int lk_c0 = (int)tb.r[2 * NG + 2];
+  asm volatile("" : "+v"(lk_tbey), "+v"(lk_tinf), "+v"(lk_c1), "+v"(lk_c0));
+  const msp_rp p_thr = (msp_rp)ld.tail + opaque_zero();
   const bool hph_in_lds = ip.hph_lds != 0;
+  double lk_h0 = hph_in_lds ? ln.p_hph[0] : ln.g_hph[0];
+  asm volatile("" : "+v"(lk_h0));
 
   // head of step k: table look-up, A m, the cubature's inputs (wave 0, no barrier).  IN_LOOP: k > 0 is known (the tables of k = 0 are the
   // prologue's).  The straight-line look-up (nagp_lookup.hpp) -- one branch, for finite R beyond the grid; the three grid words and,
   // with the H PP H' table in LDS, its three entries round the seed in ONE batch of LDS reads, the index selects among them.
-  // The window of the look-up is seeded from ttau (lookup_mid_ttau_c) in the site update, beside the division R = 1 / ttau: the seed, the
-  // address and the reads of the three grid words and, with the H PP H' table in LDS, its three entries are under way when R arrives;
-  // behind R only the branch beyond the grid, the pick among the three and the selects are left.  The prologue's head (k_start > 0:
-  // R of step k_start - 1 from memory) seeds from R as before -- the same window or one that holds the same minimiser.
+  // Inside the loop the look-up is the site update's, from ttau (ih_thr_reads / ih_thr_pick): the head only takes its index and H PP H'.
+  // The prologue's head (k_start > 0: R of step k_start - 1 from memory) seeds from R and picks among three grid words as before -- the
+  // same index (tests/test_ihgp_lookup_thresholds_host.py).
   double hph = 0.0, wc[4] = {0, 0, 0, 0}, Am[4] = {0, 0, 0, 0}, fmun = 0.0;
   int w_mid = 1;
   double w_r0 = 0.0, w_r1 = 0.0, w_r2 = 0.0, w_h0 = 0.0, w_h1 = 0.0, w_h2 = 0.0;
@@ -905,11 +938,34 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
   asm volatile("" : "+v"(accp));
   // wave 0: the static products of the second-moment contraction (msp_outputs_b), CD (CD + 1) / 2 registers of this copy of the loop
   // for the whole launch (zero on a lane without a sub-band)
+  // D <= 32: the outputs on both halves of wave 0 (msp_outputs_h) -- lane d + 32 holds sub-band d's products as well, each half keeps the
+  // static coefficients of its own terms in those registers and reads its own words of the sums (accp_h).  Decided once per launch: by the
+  // form of Q / 2Q / v where that fixes D (K4: 16, K8: 32, K16-pad: more than 32), otherwise a scalar the loop branches on.
+  constexpr int HALF_CT = (QF == QF_K4 || QF == QF_K8) ? 1 : ((QF == QF_K16P) ? 0 : -1);
+  int half_s = (D <= 32) ? 1 : 0;
+  if constexpr (HALF_CT < 0) {      // (opaque, so that the loop does not read D from the kernel's arguments again; uniform by the read of the first lane)
+    asm volatile("" : "+v"(half_s));
+    half_s = __builtin_amdgcn_readfirstlane(half_s);
+  }
+  const bool half = (WT == 0) && ((HALF_CT >= 0) ? (HALF_CT == 1) : (half_s != 0));
+  const bool upper = lane >= 32;
+  msp_rp accp_h = accp;
   double pw[(WT == 0) ? CD * (CD + 1) / 2 : 1] = {0.0};
   if constexpr (WT == 0) {
-    msp_wproducts<CD>(wrow, (ip.dbg_wave & 64) != 0, pw);
+    if (half) {
+      const int hd = lane & 31;
+      double wh[CD];
+#pragma unroll
+      for (int j = 0; j < CD; ++j) wh[j] = (hd < D) ? ld.sW[hd * CD + j] : 0.0;
+      msp_wproducts<CD>(wh, (ip.dbg_wave & 64) != 0, pw);
+      msp_half_coeffs<CD>(wh, upper, pw);
+      accp_h = accp + (upper ? msp_half_terms<CD>() : 0);
+    } else {
+      msp_wproducts<CD>(wrow, (ip.dbg_wave & 64) != 0, pw);
+    }
 #pragma unroll
     for (int q = 0; q < CD * (CD + 1) / 2; ++q) asm volatile("" : "+v"(pw[q]));
+    asm volatile("" : "+v"(accp_h));
   }
   // the cubature's inputs of a step straight behind its head, each from this wave's own fmu / HPH stores (msp_wave_fence)
   auto qv_or_link = [&]() __attribute__((always_inline)) {
@@ -940,7 +996,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       {
         t_old = ln.p_tt[ko]; n_old = ln.p_tn[ko];
 #pragma unroll
-        for (int j = 0; j < CD; ++j) wr[j] = (WT == 0) ? p_w[j] : 0.0;      // (2 CD registers of wave 0's copy, free again behind the outputs)
+        for (int j = 0; j < CD; ++j) wr[j] = (WT == 0 && !half) ? p_w[j] : 0.0;      // (2 CD registers of wave 0's copy, free again behind the outputs; the half-wave form holds the row among its coefficients)
         msr_reduce_tab<CD>(x, rt);
       }
       lds_barrier();                 // B5
@@ -948,9 +1004,12 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
       {
         msr_reduce_bins<CD>(x, rt);
         msp_wave_fence();
+        double Z = 0.0, d1 = 0.0, d2 = 0.0;
+        if constexpr (WT == 0) {
+          if (half) msp_outputs_h<CD>(accp, accp_h, pw, upper, ld.pEP1, mc.jitter, Z, d1, d2);      // every lane of the wave: the swap reads the upper half
+        }
         if (ln.act) {
-          double Z, d1, d2;
-          msp_outputs_b<CD, WT == 0>(accp, ln.n - D, wr, pw, ld.pEP1, mc.jitter, Z, d1, d2);
+          if (!(WT == 0 && half)) msp_outputs_b<CD, WT == 0>(accp, ln.n - D, wr, pw, ld.pEP1, mc.jitter, Z, d1, d2);
           if (stamp) { asm volatile("" :: "v"(d2)); IH_STAMP(4); }
           // site update (:265-266): -d2/(1+d2 HPH), (d1 - fmu d2)/(1+d2 HPH) through one reciprocal
           const double r1 = rcp_nr(fma(d2, hph, 1.0));
@@ -959,18 +1018,19 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
           if (!(tnew > 0.0)) ++ln.n_clamped;
           tnew = max0(tnew);                                               // :274 (NaN -> 0, C-3)
           {                                                                // beside the division; ahead of the ring stores
-            w_mid = lookup_mid_ttau_c(lk_ng2, lk_c1, lk_c0, tnew);
-            ih_window_reads(ln.p_rg, ln.p_hph, hph_in_lds, w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2);
+            w_mid = lookup_mid_bits(lk_ng2, lk_c1, lk_c0, tnew);
+            ih_thr_reads(p_thr, ln.p_hph, hph_in_lds, w_mid, w_r0, w_r1, w_h0, w_h1, w_h2);
           }
-          double Rn = 1.0 / tnew;                                          // R = 1/ttau: the look-up key and an output, exact division
+          double Rn = 1.0 / tnew;                                          // R = 1/ttau, exact division: an output (ring, Rprev) and the key of the
+          // side path beyond the grid; neither the gain nor the straight look-up waits for it
           // (for tnew > 0 the reference's R(:,k) = 1./ttau before the clamp is this value; otherwise :287 overwrites it with Inf)
           // R = inf: ttau = 0, or ttau of underflow size (1/ttau overflows while ys = tnu/ttau stays finite): the reference's
-          // (ys - fmu)/(HPH + R) is 0 there; the reciprocal form below would multiply inf by 0
-          double g = 0.0;                                                  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292)
-          {                                                                // by a select: clamped sites are every-step business
-            double gx = fma(nnew, Rn, -fmun) * rcp_nr(hph + Rn);
-            asm volatile("" : "+v"(gx));
-            g = (Rn < INFINITY) ? gx : 0.0;
+          // (ys - fmu)/(HPH + R) is 0 there.  ttau <= t_inf says the same as R = inf (lookup_thresholds finds t_inf with this division)
+          double g = 0.0;                                                  // (ys - fmu)/(HPH + R), ys = tnu/ttau (:277, :289-292), both sides
+          {                                                                // times ttau: (tnu - fmu ttau)/(1 + HPH ttau)
+            double gx = fma(-fmun, tnew, nnew) * rcp_nr(fma(hph, tnew, 1.0));
+            asm volatile("" : "+v"(gx));                                   // by a select: clamped sites are every-step business
+            g = (tnew > lk_tinf) ? gx : 0.0;
           }
           typedef double d2v __attribute__((ext_vector_type(2)));
           d2v m01, m23;
@@ -978,7 +1038,7 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
           m01.x = ln.mreg[0]; m01.y = ln.mreg[1]; m23.x = ln.mreg[2]; m23.y = ln.mreg[3];
           // the look-up of step k+1 from the window read above: ahead of the ring stores, so that the wait for the window takes no store
           // with it, and behind the gain in program order, so that the window's reads have the division and the gain's chain to return in
-          ih_window_pick(w_mid, w_r0, w_r1, w_r2, w_h0, w_h1, w_h2, ln.p_rg, ln.p_hph, ln.g_hph, hph_in_lds, lk_rmax, lk_ng2 + 2, Rn, w_idx, hph);
+          ih_thr_pick(w_mid, w_r0, w_r1, w_h0, w_h1, w_h2, lk_h0, ln.p_rg, ln.p_hph, ln.g_hph, hph_in_lds, lk_tbey, lk_tinf, lk_ng2 + 2, tnew, Rn, w_idx, hph);
           ln.p_tt[ko] = tnew; ln.p_tn[ko] = nnew; ln.p_R[ko] = Rn;
           typedef d2v __attribute__((address_space(3))) * lds_d2p;
           lds_d2p mf = (lds_d2p)(ln.p_MF + 4 * ko);

@@ -626,6 +626,63 @@ __device__ __forceinline__ void msp_outputs_b(msp_rp acc, int jmod, const double
   d2 = fma(-d1, d1, Zinv * s2);
 }
 
+// msp_outputs_b<CD, true> on both halves of wave 0 (D <= 32: lanes 32 .. 63 carry no sub-band of their own).  The CD + CD (CD + 1) / 2 terms
+// of a sub-band -- w_j u_j, then P_q R_q in the order of the acc layout -- are split between lane d, which takes the first NL =
+// msp_half_terms (all of s1 = w'u and the first NL - CD terms of s2), and lane d + 32, which takes the rest of s2.  Each lane reads only
+// its own NL words (acc_lane = acc + NL on the upper half) against NL static coefficients (msp_half_coeffs; the lane's registers for pw
+// hold them); the upper half's partial sum comes down with v_permlane32_swap_b32 and one addition follows.  s1 is msp_outputs_b's,
+// operation for operation; s2 is the same sum in another order of roundings.  Every lane of the wave calls this (the swap reads the upper
+// half); Z, d1, d2 mean something on lanes d < D only.
+template <int CD>
+__host__ __device__ constexpr int msp_half_terms() { return (CD + CD * (CD + 1) / 2 + 1) / 2; }
+template <int CD>
+__device__ __forceinline__ void msp_half_coeffs(const double* wrow, bool upper, double* pw /* [CD (CD + 1) / 2]: the products in, the lane's coefficients out */) {
+  constexpr int nq = CD * (CD + 1) / 2, NT = CD + nq, NL = msp_half_terms<CD>();
+  double c[NT];
+#pragma unroll
+  for (int j = 0; j < CD; ++j) c[j] = wrow[j];
+#pragma unroll
+  for (int q = 0; q < nq; ++q) c[CD + q] = pw[q];
+#pragma unroll
+  for (int i = 0; i < nq; ++i) pw[i] = (i < NL) ? (upper ? ((NL + i < NT) ? c[NL + i] : 0.0) : c[i]) : 0.0;
+}
+template <int CD>
+__device__ __forceinline__ void msp_outputs_h(msp_rp acc, msp_rp acc_lane, const double* hc, bool upper, double pEP, double jitter, double& Z, double& d1, double& d2) {
+  constexpr int nq = CD * (CD + 1) / 2, NT = CD + nq, NL = msp_half_terms<CD>();
+  static_assert(NL >= CD && NL <= nq, "the lower half holds all of s1; the coefficients fit the registers of the products");
+  double av[NL];
+  double Zs = acc[3 * CD + nq];
+#pragma unroll
+  for (int i = 0; i < NL; ++i) av[i] = acc_lane[i];
+  asm volatile("" : "+v"(Zs));
+#pragma unroll
+  for (int i = 0; i < NL; ++i) asm volatile("" : "+v"(av[i]));
+  if constexpr ((NT & 1) != 0) av[NL - 1] = upper ? 0.0 : av[NL - 1];      // the upper half has one term less: its last word is not one of R's
+  Z = pEP * __builtin_fmax(Zs, jitter);
+  const double Zinv = pEP * rcp_nr(Z);
+  double a0 = 0.0, a1 = 0.0;      // the first CD terms: s1 on the lower half
+#pragma unroll
+  for (int j = 0; j < CD; ++j) { if (j & 1) a1 = fma(hc[j], av[j], a1); else a0 = fma(hc[j], av[j], a0); }
+  const double pa = a0 + a1;
+  double b0 = 0.0, b1 = 0.0;      // the others: terms of s2 on both halves
+#pragma unroll
+  for (int i = CD; i < NL; ++i) { if (i & 1) b1 = fma(hc[i], av[i], b1); else b0 = fma(hc[i], av[i], b0); }
+  const double pb = b0 + b1;
+  const double t = pa + pb;       // the upper half's share of s2
+  typedef unsigned int u2v __attribute__((ext_vector_type(2)));
+  unsigned long long tb;
+  __builtin_memcpy(&tb, &t, 8);
+  const unsigned int tlo = (unsigned int)tb, thi = (unsigned int)(tb >> 32);
+  // (the swap exchanges lanes 32 .. 63 of its first operand with lanes 0 .. 31 of its second: the second result holds, on lane l < 32, lane l + 32)
+  const u2v slo = __builtin_amdgcn_permlane32_swap(tlo, tlo, false, false), shi = __builtin_amdgcn_permlane32_swap(thi, thi, false, false);
+  const unsigned long long ub = ((unsigned long long)shi.y << 32) | slo.y;
+  double tu;
+  __builtin_memcpy(&tu, &ub, 8);
+  const double s1 = pa, s2 = pb + tu;
+  d1 = Zinv * s1;
+  d2 = fma(-d1, d1, Zinv * s2);
+}
+
 // =====================================================================================================================
 // Role layout (LAY = 1): 512 threads.  Waves 0 and 1 carry the serial stages of the caller (wave 1 also evaluates the link
 // tables and e -- with t1 / ve in the table form of stage 1b); waves 2 .. 7 carry the parallel ones: Q / 2Q / v on waves 2..4 (three-barrier schedule of ihgp_adf8_kernel: on wave 0, msr_qv_serial),
