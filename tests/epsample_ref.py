@@ -78,13 +78,16 @@ def chol_retry(P):
     return Lc, 1, bad == 0
 
 
-def backward_factors(model, PF):
+def backward_factors(model, PF, retry_steps=None):
     """per step k < T-1: G_k = PF_k A' / L' / L with L = chol(A PF_k A' + Q), Lc_k = chol((I - G A) PF_k (I - G A)' + G Q G');
-    Lc_{T-1} = chol(PF_{T-1}).  Returns G (T x S x S, G[T-1] = 0), Lc (T x S x S), counters [retries, clamped]."""
+    Lc_{T-1} = chol(PF_{T-1}).  Returns G (T x S x S, G[T-1] = 0), Lc (T x S x S), counters [retries, clamped]; the steps that took
+    the jitter retry are appended to retry_steps."""
     A, Q = model['A'], model['Q']; T, S, _ = PF.shape
     G = np.zeros((T, S, S)); Lc = np.zeros((T, S, S)); cnt = np.zeros(2, np.int64); I = np.eye(S)
     for k in range(T - 1):
         L, r, _ = chol_retry(A @ PF[k] @ A.T + Q); cnt[0] += r
+        if r and retry_steps is not None:
+            retry_steps.append(k)
         B = PF[k] @ A.T
         X = np.linalg.solve(L, B.T).T                      # B / L'
         G[k] = np.linalg.solve(L.T, X.T).T                 # X / L
@@ -121,7 +124,8 @@ def sample(model, ttau, tnu, y, predict_at_k1, n_draws, seed=0, z=None, sig=None
     A = model['A']; S = A.shape[0]
     c = np.asarray(model['offsets'])[:-1]; h = np.asarray(model['h_val'], float)
     MF, PF = fixed_site_filter(model, y, ttau, tnu, predict_at_k1)
-    G, Lc, cnt = backward_factors(model, PF)
+    steps = []
+    G, Lc, cnt = backward_factors(model, PF, steps)
     if z is None:
         z = generator_normals(T, S, n_draws, seed)
     z = np.concatenate([np.asarray(z, float).reshape(n_draws, T, S), np.zeros((1, T, S))])      # the last one is the mean chain
@@ -134,4 +138,4 @@ def sample(model, ttau, tnu, y, predict_at_k1, n_draws, seed=0, z=None, sig=None
     MS = X[n_draws]; X = X[:n_draws]
     F = h[None, :, None] * X[:, c, :]
     Sd = None if sig is None else signal(F, len(c) - np.asarray(sig[0]).shape[1], *sig)
-    return X, F, Sd, MS, cnt, dict(MF=MF, PF=PF, G=G, Lc=Lc)
+    return X, F, Sd, MS, cnt, dict(MF=MF, PF=PF, G=G, Lc=Lc, retry_steps=np.array(steps, np.int64))
