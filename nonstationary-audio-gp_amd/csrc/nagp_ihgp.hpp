@@ -666,6 +666,16 @@ __device__ __forceinline__ void ih_thr_pick(int mid, double ta, double tb, doubl
   } else if (!hph_in_lds && !at_inf) hph = g_hph[idx];      // (issued ahead of the ring stores; first used, and so waited for, where the head stores HPH)
 }
 
+// y = A x for the lane's 4 x 4 block, two chains of two terms per row (the order of additions of the head of ihgp_adf8_kernel)
+__device__ __forceinline__ void ih_a4_times(const double* A4, const double* x, double* y) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    double a0 = A4[4 * i] * x[0], a1 = A4[4 * i + 1] * x[1];
+    a0 = fma(A4[4 * i + 2], x[2], a0); a1 = fma(A4[4 * i + 3], x[3], a1);
+    y[i] = a0 + a1;
+  }
+}
+
 // The same sweep with role-specialised waves (nagp_momsp.hpp, role layout): 512 threads, waves 0 / 1 as above, waves 2..7 run the
 // parallel stages of the cubature in their own loop.  A wave holds the registers of its role only, which is what lets two
 // waves share a SIMD.
@@ -676,8 +686,12 @@ __device__ __forceinline__ void ih_thr_pick(int mid, double ta, double tb, doubl
 // The two serial chains run side by side from B5 to B2; no barrier puts one behind the other.  Without a barrier between the tail of
 // step k and the cubature inputs of step k+1, every LDS region is ordered by construction:
 //   region                     writer (step k+1)                    last reader (step k)                         ordered by
-//   fmu / HPH, sub-bands       wave 0, head                         wave 0, msr_qv_serial                        same wave
-//   fmu / HPH, modulators      wave 1, head                         wave 1, msp_link                             same wave
+//   fmu, sub-bands             wave 0, tail, behind the gain        wave 0, msr_qv_serial                        same wave
+//   HPH, sub-bands             wave 0, head                         wave 0, msr_qv_serial                        same wave
+//   fmu, modulators            wave 1, tail, behind the gain        wave 1, msp_link                             same wave
+//   HPH, modulators            wave 1, head                         wave 1, msp_link                             same wave
+//     (fmu of step k+1 is stored behind B5(k); its readers of step k ran ahead of B2(k).  The tail of the last step stores an fmu that
+//      nothing reads: the word is the lane's own.  The prologue's head stores both fmu and HPH of the first step.)
 //     (msr_qv_serial never uses an entry beyond the sub-bands: with D = 4K it reads none, otherwise it discards what it read)
 //   Q / 2Q / v                 wave 0, B5(k) .. B2(k+1)             workers' weights, B2(k) .. B4(k)             B4, B5
 //   link tables lk / xg / xg2  wave 1, B5(k) .. B2(k+1)             workers' weights and level 2 of msr_sums, both ahead of B5(k);    B5
@@ -694,6 +708,13 @@ __device__ __forceinline__ void ih_thr_pick(int mid, double ta, double tb, doubl
 // batch of reads, the index as the count of steps at or above ttau.  The gain is (tnu - fmu ttau) / (1 + HPH ttau).  The exact division
 // R = 1 / ttau stands ahead of the ring stores in program order and feeds them, Rprev and the side branch beyond the grid (finite
 // R > rmax, entered by t_inf < ttau <= t_beyond: lookup_tail); nothing on the straight path waits for it.
+// The prediction stands one fma behind the gain g.  With m_k = Am_k + wc_k g the next prediction is A m_k = A Am_k + (A wc_k) g, and both
+// products are known from the head of step k on: the serial waves form P1 = A Am_k, P2 = A wc_k, pa = h P1[0], pb = h P2[0] between B4 and
+// B5, where they wait for the bin sums (beside msr_reduce_tab; 42 f64 operations off the chain B5 -> B2).  Behind the gain's select:
+// fmu_{k+1} = fma(pb, g, pa), its store, then Am_{k+1} = fma(P2, g, P1) and m_k = fma(wc_k, g, Am_k) for the ring (MF, fm).  The head
+// inside the loop keeps the index, the load of wc and H PP H'; the prologue's head (k_start > 0 included) forms A m from the stored mean
+// as before, and the first step's window takes its operands from that.  A (Am + wc g) and A Am + (A wc) g round differently: the sweep
+// is held by the oracle and the multi-precision fixture (tests/test_ihgp_adf_early_inputs.py), not by the bits of the commit before.
 // The serial tail waits for none of its ring stores: no LDS read of the straight path is issued behind them, and the loop reads
 // no kernel argument in the head or the site update (a scalar load there would bring an lgkmcnt(0) for the stores with it): the look-up's
 // constants are copied into vector registers ahead of the loop.
@@ -825,6 +846,15 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
         if (k + 1 < T) { carry = *i_g; i_g += i_gs; }
       }
       __syncthreads();
+      // Workers 2 and 3 (waves 4, 5) share their SIMDs with the serial waves, which are the older waves there and win the vector issue
+      // whenever both have an instruction ready.  Measured (profiles/r25_cfg3_early_inputs.txt, sections 2 and 3): with the priority their
+      // bin sums take 60 - 90 cycles less and their wait at B5 grows by as much -- they are NOT the last waves at B4 or B5 (workers 4 and
+      // 5 are) -- and the plain instantiation's execute is 0.6 - 0.8 % shorter, 1.5 % with the prediction's window; no stamped slot shows
+      // why.  Raised once for the launch; between B5 and B2 these two workers are idle and the serial waves have the SIMD.
+      // Whoever changes the worker loop or what the serial waves do between B2 and B5: repeat the two A/Bs that hold this line, with
+      // inst_iha8k8 alone rebuilt (tools/ab_libs.sh, bench.py --workload cfg3 --steps 3 --warmup 1) -- the parent's step with the line
+      // against without it, and this step with it against without it (the prediction's window loses 1.1 - 1.5 % without it).
+      if (wave == MSR_W0 + 2 || wave == MSR_W0 + 3) __builtin_amdgcn_s_setprio(1);
       for (; k < T; ++k) {
         wstep((int)(k & KM));
         // the window B5(k) .. B2(k+1): store the inputs of step k+1, load those of step k+2 (ahead of the stores below: the wait for a
@@ -914,14 +944,14 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
 #pragma unroll
         for (int i = 0; i < 4; ++i) wc[i] = w[i];
       }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        double a0 = ln.A4[4 * i] * ln.mreg[0], a1 = ln.A4[4 * i + 1] * ln.mreg[1];
-        a0 = fma(ln.A4[4 * i + 2], ln.mreg[2], a0); a1 = fma(ln.A4[4 * i + 3], ln.mreg[3], a1);
-        Am[i] = a0 + a1;
+      if constexpr (!decltype(IN_LOOP)::value) {
+        // the prologue forms A m and fmu directly; inside the loop both come from the prediction's operands (lambda step, below):
+        // the step before has stored fmu straight behind its gain and holds A m in Am
+        ih_a4_times(ln.A4, ln.mreg, Am);
+        fmun = ln.hn * Am[0];
+        *ln.p_fmu = fmun;
       }
-      fmun = ln.hn * Am[0];
-      *ln.p_fmu = fmun; *ln.p_HPH = hph;
+      *ln.p_HPH = hph;
       if (stamp) { IH_STAMP(7); }
     }
   };
@@ -999,6 +1029,17 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
         for (int j = 0; j < CD; ++j) wr[j] = (WT == 0 && !half) ? p_w[j] : 0.0;      // (2 CD registers of wave 0's copy, free again behind the outputs; the half-wave form holds the row among its coefficients)
         msr_reduce_tab<CD>(x, rt);
       }
+      // The prediction's operands, formed here where the serial waves wait for the bin sums: with m_k = A m_{k-1} + wc g the next
+      // prediction is A m_k = A (A m_{k-1}) + (A wc) g, and both products are known since the head of this step (wc: its load has long
+      // returned).  P1 = A Am, P2 = A wc, pa = h P1[0], pb = h P2[0]: behind the gain, fmu of step k+1 is ONE fma (pb, g, pa), and
+      // A m_k = fma(P2, g, P1) follows off the chain.  Pinned ahead of B5, so that none of it is scheduled into the tail.
+      double P1[4], P2[4], pa, pb;
+      ih_a4_times(ln.A4, Am, P1);
+      ih_a4_times(ln.A4, wc, P2);
+      pa = ln.hn * P1[0]; pb = ln.hn * P2[0];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(P1[i]), "+v"(P2[i]));
+      asm volatile("" : "+v"(pa), "+v"(pb));
       lds_barrier();                 // B5
       IH_STAMP(2);
       {
@@ -1034,7 +1075,13 @@ __global__ void __launch_bounds__(MSR_NT) ihgp_adf8_kernel(Shape sh, Bufs b, Mom
           }
           typedef double d2v __attribute__((ext_vector_type(2)));
           d2v m01, m23;
-          ln.mreg[0] = fma(wc[0], g, Am[0]); ln.mreg[1] = fma(wc[1], g, Am[1]); ln.mreg[2] = fma(wc[2], g, Am[2]); ln.mreg[3] = fma(wc[3], g, Am[3]);
+          // fmu of step k+1: one fma behind the gain, and its store ahead of everything else that reads g (at k + 1 == T the store has
+          // no reader: the word is the lane's own).  The mean of this step -- for the ring only -- and A m of the next follow.
+          fmun = fma(pb, g, pa);
+          *ln.p_fmu = fmun;
+          asm volatile("" : "+v"(g));
+#pragma unroll
+          for (int i = 0; i < 4; ++i) { ln.mreg[i] = fma(wc[i], g, Am[i]); Am[i] = fma(P2[i], g, P1[i]); }
           m01.x = ln.mreg[0]; m01.y = ln.mreg[1]; m23.x = ln.mreg[2]; m23.y = ln.mreg[3];
           // the look-up of step k+1 from the window read above: ahead of the ring stores, so that the wait for the window takes no store
           // with it, and behind the gain in program order, so that the window's reads have the division and the gain's chain to return in
